@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark of the FusionDepth training hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, warm up, time K steps (one window: `ms_per_step` is the time of one of
+them), write the last timed step's results if --dump-outputs is given, print the line.  --full adds everything else the line
+can carry: the roofline probes, the other BASELINE configurations (each in its own process), the CPU baseline of the oracle
+trainer, the held-out AbsRel before / after the steps and, with N > 1, the timing of the gradient exchange.
 
 N > 1 works both ways: under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (one rank per GPU, RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), and as a plain ``python bench.py --gpus N``, which re-launches itself
@@ -50,6 +55,11 @@ ARITH_NOTE = ("fp32 storage, fp32 accumulate; products fp32-exact (f32 MFMA) exc
               "the 3x3 layers: bf16x3 split, six products, fp32 accumulate (fp32-equal error vs float64; fd_tuning.limb_1x1 = "
               "limb_conv = wino_wgrad_limb = 0 restores the f32 kernels)")
 PEAK_HBM_GBS = 8000.0
+# --dump-outputs: an array above this many elements is written as a fixed seeded sample of them (the flat parameter buffer at the
+# default configuration).  Only the four disparity scales and the parameters can be that large, so a dump stays below 64 MB
+# whatever the size and batch (about 16 MB at the default configuration)
+DUMP_MAX_ELEMS = 1 << 21
+DUMP_SEED = 20261016
 
 
 def parse():
@@ -61,21 +71,27 @@ def parse():
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--batch_size", type=int, default=12, help="per-process --batch_size of the reference trainer")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need (roofline probes, "
+                    "`other_configs`, CPU baseline, held-out AbsRel, N > 1: exchange timing); off by default")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR", help="after the timed steps, write what the "
+                    "last one computed as DIR/<name>.npy (float32): its loss terms, disparity maps and poses, and the parameters after "
+                    "its Adam update (arrays above %d elements as a fixed seeded sample)" % DUMP_MAX_ELEMS)
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python on the four module streams (the default since round 5)")
     ap.add_argument("--graph", action="store_true", help="replay a captured hipGraph of the step instead (slower on ROCm 7.2; rounds 1-4 chose between the two "
                     "during the untimed warm-up; the replay never won)")
     ap.add_argument("--no_stack", action="store_true", help="run the accumulated micro-batches sequentially (reference order) "
                     "instead of as one stacked pass with grouped BatchNorm")
-    ap.add_argument("--no_roofline", action="store_true")
+    ap.add_argument("--no_roofline", action="store_true", help="with --full: skip the roofline probes")
     ap.add_argument("--share_device", action="store_true", help="testing aid: with --gpus N on a box with fewer devices, let the N "
                     "ranks share them over gloo (FD_DIST_BACKEND=gloo) instead of refusing; such a line is not a scaling measurement")
     ap.add_argument("--pool", type=int, default=0, help="distinct pre-generated step batches (default: one per step incl. warm-up, "
                     "at most 48)")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each (every window bracketed by barrier + "
-                    "synchronize); value / ms_per_step are the MEDIAN window's, min / max are reported beside them")
-    ap.add_argument("--no_other_configs", action="store_true", help="skip the short runs of the other BASELINE configurations "
-                    "(ResNet-50 batch 8, 1024x320 batch 8, Refiner, Completor) that the 1-GPU line carries as `other_configs`")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each (every window bracketed by barrier + "
+                    "synchronize); value / ms_per_step are the MEDIAN window's, min / max are reported beside them.  Default 1: "
+                    "--steps is the number of timed steps")
+    ap.add_argument("--no_other_configs", action="store_true", help="with --full: skip the short runs of the other BASELINE "
+                    "configurations (ResNet-50 batch 8, 1024x320 batch 8, Refiner, Completor) that the 1-GPU line carries as `other_configs`")
     ap.add_argument("--other_steps", type=int, default=10, help="timed steps per window of each `other_configs` entry (3 windows, median "
                                                               "reported; 5 untimed steps before them)")
     ap.add_argument("--_other", default=None, help=argparse.SUPPRESS)      # child mode: run ONE `other_configs` entry, print its JSON
@@ -477,13 +493,17 @@ def run_other_config(args):
     print(json.dumps(res), flush=True)
 
 
-def dp_probe(tr, step_fn, t_step, barrier, reps=3):
-    """Multi-rank only, after the timed region: how many ranks answered, what the gradient exchange costs on its own and how
-    much of it the backward pass hides.  exposed = (step with exchange) - (step without); overlap_frac = 1 - exposed / allreduce."""
-    world = dist.get_world_size()
-    n_over = tr.grad_sync.n_overlapped                      # of the last timed step
+def ranks_answered():
+    """Multi-rank only, after the timed region: how many ranks answered, over which backend."""
     ones = torch.ones(1, device="cuda")
     dist.all_reduce(ones)
+    return {"ranks_seen": int(ones.item()), "backend": dist.get_backend()}
+
+
+def dp_probe(tr, step_fn, t_step, barrier, reps=3):
+    """Multi-rank only, after the timed region (--full): what the gradient exchange costs on its own and how much of it the
+    backward pass hides.  exposed = (step with exchange) - (step without); overlap_frac = 1 - exposed / allreduce."""
+    n_over = tr.grad_sync.n_overlapped                      # of the last timed step
     g = tr.flat.flat_grad
     barrier()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -508,7 +528,7 @@ def dp_probe(tr, step_fn, t_step, barrier, reps=3):
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     ar_ms, t_nocomm = float(tt[0]), float(tt[1])
     exposed_ms = max(0.0, 1e3 * (t_step - t_nocomm))
-    return {"ranks_seen": int(ones.item()), "backend": dist.get_backend(), "allreduce_ms": ar_ms,
+    return {"allreduce_ms": ar_ms,
             "allreduce_bytes": int(g.numel()) * 4, "allreduce_buckets": len(tr.grad_sync.buckets),
             "buckets_overlapped": n_over, "ms_per_step_no_exchange": 1e3 * t_nocomm,
             "exposed_exchange_ms": exposed_ms, "overlap_frac": max(0.0, min(1.0, 1.0 - exposed_ms / ar_ms)) if ar_ms > 0 else None}
@@ -532,6 +552,33 @@ def self_launch(args):
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     print("[bench] --gpus %d without a torchrun environment: launching %s" % (args.gpus, " ".join(cmd[1:9])), file=sys.stderr, flush=True)
     sys.exit(subprocess.call(cmd, env=env))
+
+
+def dump_outputs(folder, tr, losses):
+    """--dump-outputs: what the last timed step computed, one float32 ``<name>.npy`` per array - the loss dict train_step returns
+    (``loss_0`` = losses["loss/0"], ...), the disparity pyramid and relative poses of its forward pass (``disp_<s>``,
+    ``cam_T_cam_0_<f>``; eager path only, the captured graph keeps no outputs) and the flat parameter buffer after its Adam update
+    (``params``).  An array above DUMP_MAX_ELEMS elements is flattened and sampled at sorted indices drawn once from a fixed seed,
+    so the same arguments give the same file set and the same elements."""
+    import numpy as np
+    arrays = {k.replace("/", "_"): v for k, v in losses.items() if torch.is_tensor(v)}
+    io = getattr(tr, "_last_io", None)
+    if io is not None:
+        for k, v in io[1].items():
+            if isinstance(k, tuple) and k[0] in ("disp", "cam_T_cam") and torch.is_tensor(v):
+                arrays["_".join(str(p) for p in k)] = v
+    arrays["params"] = tr.flat.flat_param
+    os.makedirs(folder, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(folder, name + ".npy"), a)
+        total += a.nbytes
+    print("[bench] --dump-outputs: %d arrays, %.1f MB in %s" % (len(arrays), total / 2 ** 20, folder), file=sys.stderr, flush=True)
 
 
 def main():
@@ -572,7 +619,6 @@ def main():
             for f in (-1, 1):
                 mb.pop(("T_gt", f), None)
         pool.append((mbs_i, tr.stack_micro_batches(mbs_i) if tr.stack_microbatches else mbs_i))
-    val_batch = synthetic.make_scene_batch(tr.batch_size, args.height, args.width, seed=99991 + rank)
     mbs, eager_in = pool[0]
     cursor = [0]
 
@@ -605,7 +651,12 @@ def main():
         return (time.perf_counter() - t) / n
 
     barrier(); barrier()          # the first collective builds the communicator (seconds): keep it out of every measurement
-    abs_rel_before = float(tr.val_metrics([val_batch])["de/abs_rel"])
+    if args.full:
+        # held-out scene (its ground truth kept) for AbsRel before / after the steps; the random state is put back, so that
+        # a --full run trains on exactly what a plain run does
+        with torch.random.fork_rng(devices=[torch.cuda.current_device()]):
+            val_batch = synthetic.make_scene_batch(tr.batch_size, args.height, args.width, seed=99991 + rank)
+            abs_rel_before = float(tr.val_metrics([val_batch])["de/abs_rel"])
     # Launch path: eager issue on the four module streams.  Rounds 1-4 timed a hipGraph replay of the step against it during the
     # warm-up and took the faster one; the replay has lost every such trial since round 1 (round 5, profiles/round5_eager_vs_trial.log:
     # 22.4 vs 19.1 ms per step - hipGraphLaunch costs the host more per kernel node than the eager launch it replaces, and its
@@ -623,9 +674,10 @@ def main():
         step_fn()
     for _ in range(max(args.warmup, 0 if launch == "eager" else 2)):     # graph mode: 1 eager warm-up + 1 capture/replay
         step_fn()
-    # K timed steps, bracketed by barrier + synchronize on both sides - `--windows` times over (default 3): a window of 20 steps is
-    # 0.4 s, short enough for clock ramps and neighbours on the box to move it by a few percent, so the line reports the MEDIAN
-    # window (value, ms_per_step) with the fastest / slowest beside it.  Every window is the MAX over ranks.
+    # K timed steps, bracketed by barrier + synchronize on both sides - one window by default, so that --steps is the number of timed
+    # steps.  --windows M repeats the window M times and reports the MEDIAN one (value, ms_per_step) with the fastest / slowest beside
+    # it: a window of 20 steps is 0.4 s, short enough for clock ramps and neighbours on the box to move it by a few percent.  Every
+    # window is the MAX over ranks.
     win, win_host, win_ranks = [], [], []
     for _ in range(max(args.windows, 1)):
         barrier()
@@ -652,6 +704,8 @@ def main():
     order = sorted(range(len(win)), key=lambda i: win[i])
     mid = order[len(order) // 2]                 # the median window (an even count: the slower of the two middle ones)
     dt, t_host = win[mid], win_host[mid]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, losses)
     images = args.steps * opt.batch_size * world
     loss_val = float(losses["loss"].detach())
     # The SI-log term of a scale is NaN by definition when no LiDAR return passes its validity mask (mean / variance of an
@@ -662,7 +716,6 @@ def main():
     n_steps_run = tr.adam_step_count
     flat64 = tr.flat.flat_param.double()
     param_checksum = [float(flat64.sum()), float(flat64.abs().sum())]        # equal between two runs of one build: the step is deterministic
-    abs_rel_after = float(tr.val_metrics([val_batch])["de/abs_rel"])
     rank_spread = None
     if win_ranks[mid]:
         own = [1e3 * a / args.steps for a, _ in win_ranks[mid]]
@@ -689,8 +742,9 @@ def main():
                    "micro_batches": "stacked (grouped BatchNorm)" if tr.stack_microbatches else "sequential"},
         "final_loss": loss_val if loss_val == loss_val else None, "final_loss_photometric": photo_val,
         "params_finite": params_finite, "optimizer_steps_run": n_steps_run, "distinct_step_batches": n_pool, "param_checksum": param_checksum,
-        "abs_rel_heldout_scene": {"before": abs_rel_before, "after": abs_rel_after},
     }
+    if args.full:
+        result["abs_rel_heldout_scene"] = {"before": abs_rel_before, "after": float(tr.val_metrics([val_batch])["de/abs_rel"])}
     key = (args.num_layers, args.height, args.width)
     if key in CONV_GFLOP_FWD_BWD:
         tf = CONV_GFLOP_FWD_BWD[key] * 1e9 * (images / world) / dt / 1e12
@@ -698,13 +752,16 @@ def main():
         result["step_conv_tflops_per_gpu"] = tf
     if world > 1:
         result["rank_spread"] = rank_spread
-        result.update(dp_probe(tr, step_fn, dt / args.steps, barrier))
+        result.update(ranks_answered())
+        if args.full:
+            result.update(dp_probe(tr, step_fn, dt / args.steps, barrier))
         if result["ranks_seen"] != args.gpus or (result["backend"] != "nccl" and not args.share_device):
             sys.exit("bench.py: %d ranks answered over %r, expected %d over nccl (= RCCL)" % (result["ranks_seen"], result["backend"], args.gpus))
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result.update(roofline_probes(args, tr, eager_in if tr.stack_microbatches else mbs[0]))
         print("[bench] roofline probes done", file=sys.stderr, flush=True)
-    if rank == 0 and world == 1 and not args.no_other_configs and (args.num_layers, args.height, args.width, args.batch_size) == (18, 192, 640, 12):
+    if (rank == 0 and world == 1 and args.full and not args.no_other_configs
+            and (args.num_layers, args.height, args.width, args.batch_size) == (18, 192, 640, 12)):
         del tr, pool, eager_in, mbs, val_batch, step_fn
         import gc
         gc.collect(); torch.cuda.empty_cache()
@@ -713,7 +770,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     # rank 0 alone (N > 1: after the process group is gone - the other ranks have left, no collective waits on the CPU run)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline_1thread"], result["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -60,7 +61,10 @@ def golden():
 
     def load(name):
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLD, name + ".npz")))
+            # a set above 1 MiB is stored as <name>.npz + <name>.part1.npz, ... (make_golden.save)
+            cache[name] = {}
+            for path in [os.path.join(GOLD, name + ".npz")] + sorted(glob.glob(os.path.join(GOLD, name + ".part*.npz"))):
+                cache[name].update(np.load(path))
         return cache[name]
 
     return load

@@ -79,10 +79,30 @@ def npy(t):
     return t.detach().cpu().numpy()
 
 
+PART_BYTES = 960 << 10      # a committed file stays below 1 MiB: larger sets go to <name>.npz + <name>.part1.npz, ... (conftest merges them)
+
+
 def save(name, **arrays):
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote %-28s %8.1f KiB  (%d arrays)" % (name + ".npz", os.path.getsize(path) / 1024, len(arrays)))
+    import glob
+    import io
+    import zlib
+    for old in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, v in arrays.items():                  # greedy, in the given order, by each array's deflated size
+        buf = io.BytesIO()
+        np.save(buf, np.asarray(v))
+        n = len(zlib.compress(buf.getvalue())) + 256
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for i, part in enumerate(parts):
+        fname = name + (".part%d" % i if i else "") + ".npz"
+        path = os.path.join(HERE, fname)
+        np.savez_compressed(path, **part)
+        print("wrote %-28s %8.1f KiB  (%d arrays)" % (fname, os.path.getsize(path) / 1024, len(part)))
 
 
 def put_grad(out, key, g):

@@ -79,7 +79,7 @@ def test_bench_two_ranks_reports_the_exchange(tmp_path, backend):
     env = dict(os.environ, FD_DIST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--height", "64", "--width", "96", "--batch_size", "2", "--no_roofline", "--no_cpu_baseline"]
+           "--height", "64", "--width", "96", "--batch_size", "2", "--full", "--no_roofline", "--no_cpu_baseline"]
     if backend == "gloo":
         cmd.append("--share_device")         # two ranks on the one GPU of the test box: allowed only when asked for
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=400)
@@ -98,7 +98,7 @@ def _bench_plain(extra, timeout=500, lean=True):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "64",
-           "--width", "96", "--batch_size", "2"] + (["--no_roofline", "--no_cpu_baseline"] if lean else []) + extra
+           "--width", "96", "--batch_size", "2"] + (["--no_roofline", "--no_cpu_baseline"] if lean else ["--full"]) + extra
     return subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
 
 
@@ -125,7 +125,7 @@ def test_plain_bench_gpus2_launches_its_own_ranks():
 
 
 def test_bench_gpus2_line_carries_roofline_and_cpu_baseline():
-    """the N > 1 line must be complete the first time a multi-GPU node runs it - `roofline` (rank 0's probes)
+    """the N > 1 line of --full must be complete the first time a multi-GPU node runs it - `roofline` (rank 0's probes)
     and `cpu_baseline` (rank 0, after the process group is gone so that no collective waits on a CPU run) next to the exchange figures."""
     import torch
     r = _bench_plain([] if torch.cuda.device_count() >= 2 else ["--share_device"], timeout=900, lean=False)
