@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FD_LIBFDHIP") or os.path.join(_HERE, "libfdhip.so")   # FD_LIBFDHIP: ablation builds (scripts/)
-ABI_VERSION = 4
+ABI_VERSION = 5
 PHOTO_OUT_FLOATS = 96        # FD_PHOTO_OUT_FLOATS
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -151,6 +151,12 @@ SIGNATURES = {
     "fd_replay_function_name": ("i", "s"),
     "fd_replay_function_signature": ("i", "s"),
     "fd_replay": ("pippip", "i"),
+    "fd_gdc_prepare_ws_bytes": ("ii", "l"),
+    "fd_gdc_prepare": ("ppii" "dddddddd" "pppp", "i"),
+    "fd_gdc_ws_bytes": ("iii", "l"),
+    "fd_gdc_build": ("ppp" "iiiii" "ddddddd" "pp", "i"),
+    "fd_gdc_cg_iters": ("piiiip", "i"),
+    "fd_gdc_finish": ("ppp" "iiiii" "ppp", "i"),
 }
 
 _lock = threading.Lock()

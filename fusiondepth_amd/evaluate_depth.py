@@ -4,7 +4,7 @@
   * ``batch_post_process_disparity(l_disp, r_disp)``  evaluate_depth.py:62-70   (fd_post_process_disparity, float64 like numpy)
   * ``evaluate_predictions(pred_disps, gt_depths, ...)``  the per-image loop of ``evaluate`` (evaluate_depth.py:344-478):
     resize the predicted disparity to the ground-truth size, invert, Eigen mask + Garg crop, ``pred_depth_scale_factor``,
-    median scaling, clamp to [1e-3, 80], metrics, mean over images.
+    median scaling, optional GDC (--eval_gdc, gdc.py), clamp to [1e-3, 80], metrics, mean over images.
 Model loading, the dataset walk, colour-mapped PNG dumps and the per-semantic-class breakdown of the reference script are
 outside the hot path.  No CPU fallback: tensors must live on the GPU.
 """
@@ -46,9 +46,26 @@ def garg_crop(gt_height, gt_width):
     return np.array([0.40810811 * gt_height, 0.99189189 * gt_height, 0.03594771 * gt_width, 0.96405229 * gt_width]).astype(np.int32)
 
 
-def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False):
+def gdc_range(random_sample=-1, nbeams=4):
+    """evaluate_depth.py:391-396: the pitch range (degrees) GDC considers for the sparse input."""
+    if random_sample == -1:
+        return (-0.1, 4.0)
+    if nbeams > 4:
+        return (-10, 10)
+    return (-1.5, 9)
+
+
+def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False,
+                         eval_gdc=False, beam_depths=None, calibs=None, random_sample=-1, nbeams=4):
     """evaluate_depth.py:344-478.  ``pred_disps``: [N,h,w] device tensor (or list); ``gt_depths``: list of [H_i,W_i] arrays /
-    tensors (KITTI ground truth has per-drive sizes).  Returns (mean of the 7 metrics over the images, per-image scaling ratios)."""
+    tensors (KITTI ground truth has per-drive sizes).  Returns (mean of the 7 metrics over the images, per-image scaling ratios).
+    ``eval_gdc`` (--eval_gdc, evaluate_depth.py:387-405): after median scaling, correct each prediction with GDC against
+    ``beam_depths[i]`` (the sparse LiDAR map at ground-truth size, 0 = no point) and ``calibs[i]`` (``kitti_utils.Calibration``),
+    with the reference's settings and pitch range (``gdc_range(random_sample, nbeams)``)."""
+    if eval_gdc:
+        from .gdc import GDC
+        if beam_depths is None or calibs is None:
+            raise ValueError("evaluate_predictions: eval_gdc needs beam_depths and calibs")
     errors, ratios = [], []
     for i in range(len(gt_depths)):
         gt = torch.as_tensor(gt_depths[i], dtype=torch.float32).cuda()
@@ -71,6 +88,11 @@ def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_s
             ratio = _median(gt[mask]) / _median(pred_depth[mask])
             ratios.append(float(ratio))
             pred_depth = pred_depth * ratio
+        if eval_gdc:
+            gtd = torch.as_tensor(beam_depths[i], dtype=torch.float64).cuda().clone()
+            gtd[gtd == 0] = -1
+            pred_depth = GDC(pred_depth, gtd, calibs[i], W_tol=3e-5, recon_tol=5e-4, k=10, method="cg",
+                             consider_range=gdc_range(random_sample, nbeams), idx=i)
         pred, g = torch.clamp(pred_depth[mask], MIN_DEPTH, MAX_DEPTH), gt[mask]
         errors.append(compute_errors(g, pred))
     return np.array(errors).mean(0), np.array(ratios)

@@ -1,0 +1,175 @@
+"""Graph-based depth correction (GDC) on the GPU: ``gdc_old.py:74-250`` ``GDC`` of the reference, on the kernels of
+``csrc/gdc.hip`` (``fd_gdc_*``, include/fdhip.h).
+
+``GDC(pred_depth, gt_depth, calib, ...)`` corrects a dense predicted depth map against sparse LiDAR: the pixels of the pred
+cloud inside a pitch range become nodes of a k-NN graph; each node's depth is an affine combination of its neighbours'
+(locally linear reconstruction weights); the pseudo-LiDAR depths are re-solved so that the same weights reconstruct them
+from the LiDAR depths, by conjugate gradient on the normal equations.  It makes the ``inf_gdc`` maps the Refiner trains
+against (``python -m fusiondepth_amd.inf_gdc``) and runs the ``--eval_gdc`` evaluation mode
+(``evaluate_depth.evaluate_predictions(eval_gdc=True)``).
+
+Step for step as the reference (back-projection, masks, compaction, k-NN, weights, A and b, scipy 1.15's ``cg`` loop,
+write-back), all in float64.  Where it cannot match exactly:
+
+  * pitch test: ``asin`` of the device math library vs numpy's may differ in the last bit, so a pixel whose pitch lies
+    within ~1e-12 rad of a bound of ``consider_range`` can fall on the other side.  Back-projection and the other masks are
+    computed without FMA contraction and are bit-identical to numpy's.
+  * k-NN: exact (brute force over all points); ties are broken by (distance, index), a k-d tree's order among exactly equal
+    distances is unspecified.  Exact ties do not occur on real data.
+  * weights: the (k+2)x(k+2) system of gdc_old.py:178-188 is solved in closed form, not by LU.  Its solution
+    w = B (B^T B)^-1 (x_i, 1) with B = [x_nb, 1] does not depend on ``W_tol`` (it cancels analytically), so ``W_tol`` only
+    changes the rounding of the reference's LU; here w_j = 1/k + (x_i - m)(x_j - m) / sum_l (x_l - m)^2, m = mean(x_nb),
+    which agrees with LU to ~1e-9 relative where the system is not near-singular.  "Exactly singular" = all k neighbours
+    at one depth.
+  * CG: the same recurrence, scalars and stopping test as scipy's ``cg`` (``rtol=recon_tol, atol=0``, the criterion the
+    removed ``tol=`` keyword meant), sparse products summed in scipy's order; the dot products are fixed two-level trees,
+    not numpy's BLAS ``dot``, so iterates agree to rounding (~1e-8 relative after 50 iterations), not bit for bit, and the
+    stopping iteration can differ by one or two where ||r|| crosses the threshold within rounding.
+  * ``method='gmres'`` (the signature default) is solved by the same CG on the same symmetric positive definite operator
+    A^T A, with a one-time warning; every caller of the reference passes ``'cg'``.
+  * ``subsample=True`` (a random permutation) and ``verbose=True`` (writes open3d point clouds) raise NotImplementedError.
+  * failure (fewer than k + 1 points, an exactly singular weight system) returns ``pred_depth`` unchanged with
+    ``status = "failed"`` instead of raising - the reference's callers catch the exception and keep the input depth.
+
+Device tensors only (no CPU fallback).  One host read after the masks (the point counts size the workspace) and one every
+``POLL`` CG iterations (the ``done`` flag); the stopping iteration is exact because every kernel returns at once after it.
+"""
+import collections
+import ctypes
+import warnings
+
+import numpy as np
+import torch
+
+from . import functional as FD
+from ._lib import call, query, stream
+
+POLL = 32            # CG iterations enqueued between two reads of the solver state
+
+GDCInfo = collections.namedtuple("GDCInfo", "N_PL N_L iterations rel_residual status")
+
+
+class GdcState(ctypes.Structure):
+    """Mirror of ``fd_gdc_state`` (the first bytes of the solver workspace)."""
+    _fields_ = [("rho", ctypes.c_double), ("rho_prev", ctypes.c_double), ("atol", ctypes.c_double), ("bnorm", ctypes.c_double),
+                ("rnorm", ctypes.c_double), ("iterations", ctypes.c_int), ("done", ctypes.c_int), ("converged", ctypes.c_int),
+                ("fail", ctypes.c_int), ("zero_rhs", ctypes.c_int)]
+
+
+_gmres_warned = [False]
+
+
+def _state(ws):
+    raw = ws[:ctypes.sizeof(GdcState)].cpu().numpy().tobytes()
+    return GdcState.from_buffer_copy(raw)
+
+
+def _camera(calib):
+    return tuple(float(getattr(calib, n)) for n in ("c_u", "c_v", "f_u", "f_v", "b_x", "b_y"))
+
+
+def _layout(N_PL, N_L, k):
+    """Byte offsets of the solver workspace's arrays (mirror of csrc/gdc.hip ``layout``; tests and scripts/time_gdc.py read the
+    intermediate results through it; its total is checked against fd_gdc_ws_bytes)."""
+    N, K1, nb = N_PL + N_L, k + 1, (max(N_PL, 1) + 255) // 256
+    sizes = [("state", ctypes.sizeof(GdcState)), ("px", 8 * N), ("py", 8 * N), ("pz", 8 * N), ("xinfo", 8 * N), ("gv", 8 * N_L),
+             ("nbr", 4 * N * k), ("w", 8 * N * k), ("b", 8 * N), ("acol", 4 * N * K1), ("aval", 8 * N * K1),
+             ("colcnt", 4 * (N_PL + 1)), ("colptr", 4 * (N_PL + 1)), ("cursor", 4 * (N_PL + 1)), ("trow", 4 * N * K1),
+             ("tval", 8 * N * K1), ("c", 8 * N_PL), ("x", 8 * N_PL), ("r", 8 * N_PL), ("p", 8 * N_PL), ("q", 8 * N_PL),
+             ("q1", 8 * N), ("part_cc", 8 * nb), ("part_rr", 8 * nb), ("part_pq", 8 * nb)]
+    out, o = {}, 0
+    for name, n in sizes:
+        out[name] = (o, n)
+        o += (max(n, 1) + 255) // 256 * 256
+    return out, o
+
+
+def ws_view(ws, N_PL, N_L, k, name):
+    """One array of the solver workspace as a typed view (int32: nbr, acol, colptr, trow; float64 otherwise)."""
+    lay, total = _layout(N_PL, N_L, k)
+    assert total == ws.numel(), "gdc workspace layout out of step with csrc/gdc.hip"
+    o, n = lay[name]
+    dt = torch.int32 if name in ("nbr", "acol", "colcnt", "colptr", "cursor", "trow") else torch.float64
+    return ws[o:o + n].view(dt)
+
+
+def prepare(pred, gt, calib, consider_range):
+    """fd_gdc_prepare: -> (pix [H*W] int32 device tensor: pred_mask pixels then gt_mask pixels, N_PL, N_L)."""
+    H, W = pred.shape
+    lo, hi = np.radians(consider_range[0]), np.radians(consider_range[1])
+    pix = torch.empty(H * W, dtype=torch.int32, device=pred.device)
+    counts = torch.empty(2, dtype=torch.int32, device=pred.device)
+    pws = torch.empty(query("fd_gdc_prepare_ws_bytes", H, W), dtype=torch.uint8, device=pred.device)
+    call("fd_gdc_prepare", pred.data_ptr(), gt.data_ptr(), H, W, *_camera(calib), float(lo), float(hi), pix.data_ptr(),
+         counts.data_ptr(), pws.data_ptr(), stream())
+    N_PL, N_L = (int(v) for v in counts.cpu())
+    return pix, N_PL, N_L
+
+
+def build(pred, gt, calib, pix, N_PL, N_L, k, recon_tol):
+    """fd_gdc_build -> the solver workspace (uint8 device tensor)."""
+    H, W = pred.shape
+    ws = torch.empty(query("fd_gdc_ws_bytes", N_PL, N_L, k), dtype=torch.uint8, device=pred.device)
+    call("fd_gdc_build", pred.data_ptr(), gt.data_ptr(), pix.data_ptr(), N_PL, N_L, k, H, W, *_camera(calib), float(recon_tol),
+         ws.data_ptr(), stream())
+    return ws
+
+
+def solve(ws, N_PL, N_L, k, maxiter):
+    """CG iterations in chunks of POLL until the state says done or ``maxiter`` iterations are enqueued -> the state."""
+    st = _state(ws)
+    done = 0
+    while not st.done and done < maxiter:
+        n = min(POLL, maxiter - done)
+        call("fd_gdc_cg_iters", ws.data_ptr(), N_PL, N_L, k, n, stream())
+        done += n
+        st = _state(ws)
+    return st
+
+
+def GDC(pred_depth, gt_depth, calib, k=10, W_tol=1e-5, recon_tol=1e-4, verbose=False, method='gmres', consider_range=(-0.1, 3.0),
+        subsample=False, idx=0, maxiter=None, return_info=False):
+    """gdc_old.py:74-250.  ``pred_depth`` [H,W] float32 and ``gt_depth`` [H,W] float32 / float64 (-1: no LiDAR point) device
+    tensors at ground-truth resolution; ``calib`` has ``c_u, c_v, f_u, f_v, b_x, b_y`` (``kitti_utils.Calibration``).
+    Returns the corrected [H,W] float32 device tensor, and with ``return_info`` a ``GDCInfo(N_PL, N_L, iterations,
+    rel_residual, status)`` (status: "converged", "maxiter" or "failed").  ``maxiter`` defaults to 10 * N_PL (scipy's);
+    ``W_tol`` does not enter the closed-form weights (module docstring); ``idx`` only named the reference's debug files."""
+    FD._need_cuda(pred_depth, gt_depth)
+    if subsample:
+        raise NotImplementedError("GDC: subsample=True (gdc_old.py's random grid subsampling) is not supported")
+    if verbose:
+        raise NotImplementedError("GDC: verbose=True (open3d point-cloud dumps) is not supported")
+    if method not in ("cg", "gmres"):
+        raise ValueError("GDC: method must be 'cg' or 'gmres', got %r" % (method,))
+    if method == "gmres" and not _gmres_warned[0]:
+        _gmres_warned[0] = True
+        warnings.warn("GDC: method='gmres' is solved by conjugate gradient on the same SPD normal equations", stacklevel=2)
+    if pred_depth.dim() != 2 or pred_depth.shape != gt_depth.shape:
+        raise ValueError("GDC: pred_depth %s and gt_depth %s must be matching [H, W] maps"
+                         % (tuple(pred_depth.shape), tuple(gt_depth.shape)))
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError("GDC: k = %d outside [1, 16]" % k)
+    pred = pred_depth.detach().to(torch.float32).contiguous()
+    gt = gt_depth.detach().to(torch.float64).contiguous()
+    H, W = pred.shape
+    pix, N_PL, N_L = prepare(pred, gt, calib, consider_range)
+    out = torch.empty_like(pred)
+
+    def failed():
+        call("fd_gdc_finish", pred.data_ptr(), gt.data_ptr(), None, N_PL, N_L, k, H, W, None, out.data_ptr(), stream())
+        return (out, GDCInfo(N_PL, N_L, 0, float("nan"), "failed")) if return_info else out
+
+    if N_PL + N_L < k + 1:
+        return failed()
+    ws = build(pred, gt, calib, pix, N_PL, N_L, k, recon_tol)
+    st = solve(ws, N_PL, N_L, k, 10 * N_PL if maxiter is None else int(maxiter))
+    if st.fail:
+        return failed()
+    call("fd_gdc_finish", pred.data_ptr(), gt.data_ptr(), pix.data_ptr(), N_PL, N_L, k, H, W, ws.data_ptr(), out.data_ptr(), stream())
+    if not return_info:
+        return out
+    st = _state(ws)
+    rel = st.rnorm / st.bnorm if st.bnorm > 0 else 0.0
+    status = "converged" if (st.converged or st.zero_rhs) else "maxiter"
+    return out, GDCInfo(N_PL, N_L, int(st.iterations), float(rel), status)

@@ -6,6 +6,7 @@ offline ``gen2channel.py`` script can call these instead:
   * ``load_velodyne_points`` / ``read_calib_file``            kitti_utils.py:8-30   (on-disk formats: Velodyne ``.bin`` =
     float32 x 4 per point; ``calib_*.txt`` = ``key: v0 v1 ...`` lines)
   * ``generate_depth_map(calib_dir, velo_filename, cam, vel_depth, shape)``   kitti_utils.py:40-102  -> float64 numpy image
+  * ``Calibration``                                           kitti_util_from_pse.py:47-102 (the camera of GDC, gdc.py)
   * ``get_4beam`` / ``get_4beam_2channel`` / ``gen2channel``  kitti_dataset.py:93-117, gen2channel.py:42-58,60-117,122-183
     (writes ``<idx>_<side>_<flip>.npy`` float32 [2,192,640], the files ``KITTIDataset.load_4beam_2channel`` reads).
 
@@ -64,6 +65,25 @@ def velo_to_image(calib_dir, cam=2):
     projection = intr["P_rect_0%d" % cam].reshape(3, 4)
     width, height = (int(v) for v in intr["S_rect_02"][:2])
     return (projection @ rectify) @ to_cam, (height, width)
+
+
+class Calibration:
+    """kitti_util_from_pse.py:47-102 ``Calibration`` (the camera GDC back-projects with, gdc_old.py:66-71): reads
+    ``calib_cam_to_cam.txt`` and exposes P = ``P_rect_0<cam>`` [3,4], P3 = ``P_rect_03``, R0 = ``R_rect_00`` and the float64
+    scalars c_u, c_v, f_u, f_v, b_x, b_y (x = ((u - c_u) z) / f_u + b_x, y = ((v - c_v) z) / f_v + b_y) and baseline."""
+
+    def __init__(self, calib_filepath, cam=2):
+        calibs = read_calib_file(calib_filepath)
+        self.P = np.reshape(calibs["P_rect_0{}".format(cam)], [3, 4])
+        self.R0 = np.reshape(calibs["R_rect_00"], [3, 3])
+        self.P3 = np.reshape(calibs["P_rect_03"], [3, 4])
+        self.c_u = self.P[0, 2]
+        self.c_v = self.P[1, 2]
+        self.f_u = self.P[0, 0]
+        self.f_v = self.P[1, 1]
+        self.b_x = self.P[0, 3] / (-self.f_u)
+        self.b_y = self.P[1, 3] / (-self.f_v)
+        self.baseline = self.P3[0, 3] / (-self.f_u) - self.P[0, 3] / (-self.f_u)
 
 
 def _device_scan(velo_filename, device):

@@ -33,8 +33,10 @@ extern "C" {
  * 4: additions only (round 6): fd_replay (+ fd_call_rec, fd_replay_function_count / _name / _signature); fd_tuning grew at its end (limb_1x1,
  *    limb_depth, limb_target, limb_split_max_out, limb_wgrad_target, limb_conv, wino_wgrad_limb, wino_fwd_limb); fd_relayout_job.mode 7 / 8 (1x1 weights pre-split into bf16
  *    limbs) and 9 / 10 (the same for a tap subset of a larger kernel); fd_refine_cfg accepts an empty crop window.  Nothing removed, no
- *    signature changed. */
-#define FD_ABI_VERSION 4
+ *    signature changed.
+ * 5: additions only: graph-based depth correction (fd_gdc_prepare_ws_bytes, fd_gdc_prepare, fd_gdc_ws_bytes, fd_gdc_build,
+ *    fd_gdc_cg_iters, fd_gdc_finish, struct fd_gdc_state).  Nothing removed, no signature changed. */
+#define FD_ABI_VERSION 5
 
 int fd_abi_version(void);
 const char* fd_supported_arch(void); /* "gfx950" */
@@ -571,6 +573,46 @@ int fd_replay_function_count(void);
 const char* fd_replay_function_name(int i);
 const char* fd_replay_function_signature(int i);
 int fd_replay(const fd_call_rec* recs, int n, void* arena, const void* const* inputs, int n_inputs, void* stream);
+
+/* ------------------------------------------------------------------ graph-based depth correction --
+ * gdc_old.py:74-250 GDC(pred_depth, gt_depth, calib, k, W_tol, recon_tol, consider_range, method='cg'): the stage-1 depth corrected
+ * against sparse LiDAR (the Refiner's `inf_gdc` target, inf_gdc.py; evaluate_depth.py:387-405 --eval_gdc).  Five stream-ordered
+ * calls; fusiondepth_amd/gdc.py drives them.  Unlike the rest of this header, the tensors here are float64 or int32 as stated per
+ * argument (the reference computes in float64).  All arithmetic is float64; results are bit-reproducible run to run.
+ *
+ *   fd_gdc_prepare   gdc_old.py:66-71,108-109,121-167 (depth2ptc, filter_mask, filter_theta_mask, the masks): pred [H][W] float32,
+ *                    gt [H][W] float64 (-1: no LiDAR), the rectified camera (c_u, c_v, f_u, f_v, b_x, b_y of
+ *                    kitti_util_from_pse.py:97-102) and the pitch range in radians [pitch_lo, pitch_hi)  ->  pix [H*W] int32: the
+ *                    pred_mask pixels (row-major), then the gt_mask pixels (row-major); counts [2] int32 = (N_PL, N_L).
+ *                    ws: fd_gdc_prepare_ws_bytes(H, W) bytes.  The caller reads `counts` to size the solver workspace.
+ *   fd_gdc_build     gdc_old.py:162-230 up to the solve: back-projected pred positions of the N = N_PL + N_L points, their exact
+ *                    k + 1 nearest neighbours (float64 squared distances, ties by index, the point itself dropped), the
+ *                    reconstruction weights in closed form (the (k+2)x(k+2) KKT system's solution does not depend on W_tol: it
+ *                    cancels analytically, so W_tol is not an argument), b, A = [I - W_PLPL ; W_PLL] and its transpose, and the
+ *                    start of scipy's cg on A^T A x = A^T b from x0 = x_info[:N_PL]: r = A^T b - A^T A x0, atol = recon_tol *
+ *                    ||A^T b||.  Needs 1 <= k <= 16 and N >= k + 1.  ws: fd_gdc_ws_bytes(N_PL, N_L, k) bytes, starting with an
+ *                    fd_gdc_state.  An exactly singular weight system (all k neighbours at one depth) sets state.fail.
+ *   fd_gdc_cg_iters  n_iters iterations of scipy 1.15's cg loop (convergence test ||r|| < atol at the top of each iteration), four
+ *                    launches each; once state.done is set every launch returns at once, so a caller enqueues iterations in
+ *                    chunks and reads the state between them.  The caller bounds the total (maxiter).
+ *   fd_gdc_finish    gdc_old.py:239-241: out [H][W] float32 = pred, the solution in the pred_mask pixels, gt wherever gt > 0; and
+ *                    state.rnorm = ||r||.  ws == NULL and pix == NULL: out = pred (the failure path - the reference's caller
+ *                    keeps the input depth when GDC raises). */
+typedef struct fd_gdc_state {
+    double rho, rho_prev;         /* r.r of the current / previous iteration */
+    double atol, bnorm, rnorm;    /* recon_tol * ||A^T b||, ||A^T b||, ||r|| (rnorm: written by fd_gdc_finish) */
+    int iterations;               /* completed CG iterations */
+    int done, converged, fail, zero_rhs;   /* done: converged, failed, or ||A^T b|| == 0 (the solution is then A^T b = 0) */
+} fd_gdc_state;
+long fd_gdc_prepare_ws_bytes(int H, int W);
+int fd_gdc_prepare(const float* pred, const double* gt, int H, int W, double c_u, double c_v, double f_u, double f_v, double b_x,
+                   double b_y, double pitch_lo, double pitch_hi, int* pix, int* counts, void* ws, void* stream);
+long fd_gdc_ws_bytes(int N_PL, int N_L, int k);
+int fd_gdc_build(const float* pred, const double* gt, const int* pix, int N_PL, int N_L, int k, int H, int W, double c_u, double c_v,
+                 double f_u, double f_v, double b_x, double b_y, double recon_tol, void* ws, void* stream);
+int fd_gdc_cg_iters(void* ws, int N_PL, int N_L, int k, int n_iters, void* stream);
+int fd_gdc_finish(const float* pred, const double* gt, const int* pix, int N_PL, int N_L, int k, int H, int W, void* ws, float* out,
+                  void* stream);
 
 #ifdef __cplusplus
 }
