@@ -17,7 +17,11 @@
 #include "conv_fast.h"
 #include "conv_limb.h"
 #include <stdio.h>
+#include <algorithm>
 #include "conv_narrow.h"
+
+extern "C" int fd_axpby(const float* a, const float* b, float* out, long n, float alpha, float beta, void* stream);   // pool.hip
+extern "C" int fd_act_bwd(const float* y, const float* gy, float* gpre, long n, int act, void* stream);   // pool.hip
 
 namespace {
 
@@ -825,25 +829,20 @@ inline int ew_blocks(long n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-}  // namespace
-
-namespace {
 inline long align4(long n) { return (n + 3) / 4 * 4; }
 inline bool fast_fwd_ok(const fd_conv_desc* d) { return d->Cin % 16 == 0 && !d->in_norm; }
 inline bool fast_dgrad_ok(const fd_conv_desc* d) { return d->Cout % 16 == 0; }
 // the stride-2 layers on the split-precision implicit GEMM (conv_limb.hip: k_conv_limb), forward and data gradient
 // (3x3 kernels always; the 1x1 stride-2 downsample layers only where the launch fills the chip without split-K - limb_conv_1x1_worth)
-inline bool limb_conv_fwd_ok(const fd_conv_desc* d) {
-    if (!(d->stride == 2 && !d->in_norm && limb_conv_problem_ok(d->Cout, d->Cin, d->pad_mode, d->act))) return false;
-    if (d->KH * d->KW > 1) return true;
+inline bool limb_conv_taps_ok(const fd_conv_desc* d, int M) {
     ConvShape s;
-    return d->pad == 0 && conv_out_shape(d, s) && limb_conv_1x1_worth(d->Cout, (long)d->N * s.Ho * s.Wo);
+    return d->KH * d->KW > 1 || (d->pad == 0 && conv_out_shape(d, s) && limb_conv_1x1_worth(M, (long)d->N * s.Ho * s.Wo));
+}
+inline bool limb_conv_fwd_ok(const fd_conv_desc* d) {
+    return d->stride == 2 && !d->in_norm && limb_conv_problem_ok(d->Cout, d->Cin, d->pad_mode, d->act) && limb_conv_taps_ok(d, d->Cout);
 }
 inline bool limb_conv_dgrad_ok(const fd_conv_desc* d) {
-    if (!(d->stride == 2 && d->pad_mode == 0 && limb_conv_problem_ok(d->Cin, d->Cout, 0, 0))) return false;
-    if (d->KH * d->KW > 1) return true;
-    ConvShape s;
-    return d->pad == 0 && conv_out_shape(d, s) && limb_conv_1x1_worth(d->Cin, (long)d->N * s.Ho * s.Wo);
+    return d->stride == 2 && d->pad_mode == 0 && limb_conv_problem_ok(d->Cin, d->Cout, 0, 0) && limb_conv_taps_ok(d, d->Cin);
 }
 inline bool limb_conv_wgrad_ok(const fd_conv_desc* d, const ConvShape& s) {
     if (!(d->stride == 2 && d->pad_mode == 0 && !d->in_norm && limb_wgrad_s2_shape_ok(d->Cout, d->Cin, d->H, d->W, s.Ho, s.Wo))) return false;
@@ -903,6 +902,7 @@ bool refl_wino_padded(const fd_conv_desc* d, fd_conv_desc& gp) {
     gp.H = d->H + 2; gp.W = d->W + 2;
     return wino_fwd_ok(&gp);
 }
+constexpr long REFLECT_RING_MIN_PIXELS = 16384;   // reflect_ring = 1 (smaller planes, measured up to 48 x 160: four thin launches + their fold cost more than the fold pass)
 
 void fill_fwd_args(const fd_conv_desc* d, const ConvShape& s, FastGemmArgs& f) {
     f = FastGemmArgs{};
@@ -915,124 +915,255 @@ void fill_fwd_args(const fd_conv_desc* d, const ConvShape& s, FastGemmArgs& f) {
     f.out_w = s.Wo; f.osy = 1; f.ooy = 0; f.osx = 1; f.oox = 0;
     f.act = d->act;
 }
-}  // namespace
 
-extern "C" long fd_conv2d_fwd_wt_floats(const fd_conv_desc* d) {
-    if (!d || c1_shape_ok(d) || !fast_fwd_ok(d)) return 0;
-    if (n16_shape_ok(d, d->Cout, d->Cin)) return 0;              // reads the weights as they are
-    if (limb_fwd_ok(d)) return align4(limb_wt_floats(d->Cout, d->Cin));
-    if (wino_use_fwd(d)) return align4(wino_wt_floats(d));
-    if (limb_conv_fwd_ok(d)) return align4(limb_wt_floats(d->Cout, (long)d->KH * d->KW * d->Cin));
-    return align4((long)d->Cout * d->Cin * d->KH * d->KW);
+int wgrad_splits(const fd_conv_desc* d, const ConvShape& s) {
+    const long Np = (long)d->N * s.Ho * s.Wo;
+    const long J = (long)d->Cin * d->KH * d->KW;
+    const long tiles = J <= 64 ? (long)fd_cdiv(d->Cout, 64) : (long)fd_cdiv(J, 128) * fd_cdiv(d->Cout, d->Cout <= 32 ? 32 : 64);
+    long want = (768 + tiles - 1) / tiles;            // ~3 workgroups per CU
+    long maxs = (Np + 511) / 512;                     // at least 512 pixels per split
+    long sp = want < maxs ? want : maxs;
+    if (sp < 1) sp = 1;
+    if (sp > 96) sp = 96;
+    return (int)sp;
 }
 
-extern "C" long fd_conv2d_fwd_ws_floats(const fd_conv_desc* d) {
-    if (!d) return 0;
+// re-layout mode of a Winograd layout: `g` = the convolution the kernel computes (for a data gradient: channels already swapped)
+inline int wino_layout_mode(const fd_conv_desc* g, bool dgrad) {
+    if (wino_fwd_limb(g)) return dgrad ? 12 : 11;
+    if (wino_fwd_2d(g)) return dgrad ? 6 : 5;
+    return dgrad ? 4 : 3;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Routing: the kernel family of a convolution, its weight layouts and its buffer sizes, decided ONCE per (descriptor, direction) by
+// route_fwd / route_dgrad / route_wgrad from the descriptor and fd_tuning alone.  The size queries, fd_conv2d_relayout_jobs and the
+// launchers all read the route; only pointer-dependent refinements stay at launch (stem7 without a bias, the 16-byte alignment of
+// the limb weight gradients, the alignment checks inside conv_wino.hip).
+//   C1 one-output-channel stencil (conv_c1.hip), N16 16 / 32-channel 3x3 blocks (conv_n16.hip), STEM7 / STEM_WGRAD 7x7 stems
+//   (conv_stem.hip / conv_narrow.hip), NARROW narrow weight gradients (conv_narrow.hip), LIMB_1X1 / LIMB_S2 1x1 stride-1 GEMM and
+//   stride-2 implicit GEMM on bf16 limbs (conv_limb.hip), WINO Winograd on `g` (conv_wino.hip), DIRECT implicit GEMM (conv_fast.hip),
+//   GENERIC gather GEMM (this file); reflect-padded data gradients: WINO_PADDED one Winograd convolution over the zero-bordered dY
+//   (`g`) + fold, RING_* the interior on the Winograd (`g`) / 16-channel / implicit-GEMM kernel + the ring, DIRECT / GENERIC the
+//   padded grid + fold.
+enum class Fam { C1, N16, STEM7, STEM_WGRAD, NARROW, LIMB_1X1, LIMB_S2, WINO, WINO_PADDED, RING_WINO, RING_N16, RING_DIRECT, DIRECT, GENERIC };
+struct Job { int mode, TA, TB, kh0, dkh, kw0, dkw, ph, pw; long off; };     // fd_relayout_job at wt + off; ph / pw: stride-2 parity class
+struct Route {
+    Fam fam = Fam::GENERIC, fallback = Fam::GENERIC;     // fallback: the weight gradient's family where a limb kernel's alignment fails
+    const char* name = "generic";                        // what fd_tuning.log prints
+    const char* fallback_name = "generic";
+    fd_conv_desc g = {};            // the Winograd problem: the forward itself, the swapped / flipped data gradient, or its zero-bordered grid
+    long wt = 0, ws = 0;            // weight-layout and workspace floats
+    int njobs = 0;
+    Job job[4];
+    bool need_zero = false;         // stride-2 data gradient: parity classes without taps leave pixels of gx unwritten
+    int stat_slots = 0;             // forward: BatchNorm statistics epilogue
+    bool bn = false;                // forward: fused BatchNorm (fd_conv2d_fwd_bn_ok adds the plane / group test)
+    void set(Fam f, const char* n) { fam = f; name = n; }
+    void add_job(int mode, int TA, int TB, int kh0, int dkh, int kw0, int dkw, long off = 0, int ph = 0, int pw = 0) {
+        job[njobs++] = Job{mode, TA, TB, kh0, dkh, kw0, dkw, ph, pw, off};
+    }
+};
+
+// Forward, in the order of DESIGN.md section 5.
+Route route_fwd(const fd_conv_desc* d) {
+    Route r;
     ConvShape s;
-    if (!conv_out_shape(d, s) || c1_shape_ok(d) || !fast_fwd_ok(d)) return 0;
-    if (n16_shape_ok(d, d->Cout, d->Cin)) return 0;
-    if (limb_fwd_ok(d)) return limb_gemm_ws_floats(d->Cout, d->Cin, d->N, d->H * d->W);
-    if (wino_use_fwd(d)) return wino_ws_floats(d);
-    FastGemmArgs f;
-    fill_fwd_args(d, s, f);
-    if (limb_conv_fwd_ok(d)) return limb_conv_ws_floats(f);
-    return fast_splitk_slab_floats(f, nullptr);
+    const bool shape_ok = conv_out_shape(d, s), fast = fast_fwd_ok(d);
+    const int KH = d->KH, KW = d->KW;
+    if (c1_shape_ok(d)) r.set(Fam::C1, "c1 stencil");
+    else if (fast && n16_shape_ok(d, d->Cout, d->Cin)) r.set(Fam::N16, "n16");            // reads the weights as they are
+    else if (stem7_fwd_ok(d)) r.set(Fam::STEM7, "stem7");
+    else if (!fast) r.set(Fam::GENERIC, "generic");                                     // likewise
+    else if (limb_fwd_ok(d)) {
+        r.set(Fam::LIMB_1X1, "limb 1x1");
+        r.wt = align4(limb_wt_floats(d->Cout, d->Cin));
+        r.ws = shape_ok ? limb_gemm_ws_floats(d->Cout, d->Cin, d->N, d->H * d->W) : 0;
+        r.add_job(7, 1, 1, 0, 1, 0, 1);
+    } else if (wino_use_fwd(d)) {
+        r.set(Fam::WINO, "wino");
+        r.g = *d;
+        r.wt = align4(wino_wt_floats(d));
+        r.ws = shape_ok ? wino_ws_floats(d) : 0;
+        r.add_job(wino_layout_mode(d, false), KH, KW, 0, 1, 0, 1);
+        r.stat_slots = wino_stat_slots(d);
+        r.bn = d->act == 0 && wino_fwd_slab_route(d);
+    } else {
+        const bool limb = limb_conv_fwd_ok(d);
+        if (limb) r.set(Fam::LIMB_S2, "limb direct");
+        else r.set(Fam::DIRECT, "direct");
+        r.wt = align4(limb ? limb_wt_floats(d->Cout, (long)KH * KW * d->Cin) : (long)d->Cout * d->Cin * KH * KW);
+        r.add_job(limb ? 9 : 0, KH, KW, 0, 1, 0, 1);
+        FastGemmArgs f;
+        fill_fwd_args(d, s, f);
+        r.ws = !shape_ok ? 0 : limb ? limb_conv_ws_floats(f) : fast_splitk_slab_floats(f, nullptr);
+    }
+    return r;
 }
 
-namespace {
-int conv2d_fwd_impl(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt, int wt_ready,
-                    float* ws, float* stat_part, void* stream);
+// Data gradient: a convolution over dY with the transposed, flipped kernel (stride 2: one per output-parity class).
+Route route_dgrad(const fd_conv_desc* d) {
+    Route r;
+    ConvShape s;
+    const bool shape_ok = conv_out_shape(d, s), fast = fast_dgrad_ok(d);
+    const int KH = d->KH, KW = d->KW;
+    const long wt_n = align4((long)d->Cin * d->Cout * KH * KW);
+    // reflect padding: the padded grid's gradient (or the ring's strips) at the front of the workspace
+    const long padded = d->pad_mode == 1 ? align4((long)d->N * d->Cin * (d->H + 2) * (d->W + 2)) : 0;
+    fd_conv_desc gz;
+    if (c1_shape_ok(d)) r.set(Fam::C1, "c1 stencil");   // the reflect adjoint folded into the stencil: no layouts, no workspace
+    else if (limb_dgrad_ok(d)) {                         // 1x1 stride 1: one GEMM with the transposed weights
+        r.set(Fam::LIMB_1X1, "limb 1x1");
+        r.wt = align4(limb_wt_floats(d->Cin, d->Cout));
+        r.ws = shape_ok ? limb_gemm_ws_floats(d->Cin, d->Cout, d->N, d->H * d->W) : 0;
+        r.add_job(8, 1, 1, 0, 1, 0, 1);
+    } else if (wino_dgrad_desc(d, r.g)) {
+        r.set(Fam::WINO, "wino");
+        r.wt = align4(wino_wt_floats(&r.g));
+        r.ws = shape_ok ? wino_ws_floats(&r.g) : 0;
+        r.add_job(wino_layout_mode(&r.g, true), KH, KW, 0, 1, 0, 1);
+    } else if (d->stride == 2) {
+        const bool limb = fast && limb_conv_dgrad_ok(d);
+        if (limb) r.set(Fam::LIMB_S2, "limb direct");
+        else r.set(fast ? Fam::DIRECT : Fam::GENERIC, "direct");        // (the log names the gather GEMM "direct" here too)
+        r.wt = 4 * wt_n;                                 // one slot per class: [Cin][(tap, Cout)], its limb image, or [Cin][Cout][tap]
+        r.ws = shape_ok ? padded : 0;
+        for (int ph = 0; ph < 2; ++ph)
+            for (int pw = 0; pw < 2; ++pw) {
+                const int kh0 = (ph + d->pad) & 1, kw0 = (pw + d->pad) & 1;
+                if (kh0 >= KH || kw0 >= KW) { r.need_zero = true; continue; }
+                if ((d->H - ph + 1) / 2 <= 0 || (d->W - pw + 1) / 2 <= 0) continue;
+                r.add_job(limb ? 10 : fast ? 1 : 2, (KH - kh0 + 1) / 2, (KW - kw0 + 1) / 2, kh0, 2, kw0, 2, (long)(ph * 2 + pw) * wt_n, ph, pw);
+            }
+    } else if (refl_wino_padded(d, r.g)) {               // [padded-grid gradient | slabs | dY in its border of zeros]
+        r.set(Fam::WINO_PADDED, "wino on the padded grid + fold");
+        r.wt = align4(wino_wt_floats(&r.g));
+        r.ws = shape_ok ? padded + wino_ws_floats(&r.g) + align4((long)d->N * d->Cout * (d->H + 2) * (d->W + 2)) : 0;
+        r.add_job(wino_layout_mode(&r.g, true), KH, KW, 0, 1, 0, 1);
+    } else {
+        r.set(fast ? Fam::DIRECT : Fam::GENERIC, "direct");
+        r.wt = wt_n;
+        r.add_job(fast ? 1 : 2, KH, KW, KH - 1, -1, KW - 1, -1);
+        long slabs = 0;
+        if (fast && shape_ok) {                          // split-K: the workspace covers every reflect candidate below
+            FastGemmArgs f = {};
+            f.M = d->Cin; f.C = d->Cout; f.T = KH * KW; f.Nb = d->N;
+            f.osy = 1; f.osx = 1;
+            auto slab_floats = [&](int NY, int NX) {
+                f.NY = NY; f.NX = NX;
+                f.out_total = (long)d->N * d->Cin * NY * NX;
+                return fast_splitk_slab_floats(f, nullptr);
+            };
+            slabs = slab_floats(d->pad_mode == 1 ? d->H + 2 : d->H, d->pad_mode == 1 ? d->W + 2 : d->W);
+            if (d->pad_mode == 1) slabs = std::max(slabs, slab_floats(d->H, d->W));   // the interior-plus-ring path: the H x W problem
+        }
+        const int ring_on = fd_tun().reflect_ring;
+        const bool wino_interior = refl_wino_interior(d, gz);
+        if (d->pad_mode == 1 && fast && ring_on && KH == 3 && KW == 3 && d->pad == 1 && d->H >= 2 && d->W >= 2 &&
+            (wino_interior || (long)d->H * d->W >= (ring_on > 1 ? ring_on : REFLECT_RING_MIN_PIXELS))) {
+            if (wino_interior) {                         // [layout of the ring's implicit GEMM | U of the interior's Winograd kernel]
+                r.set(Fam::RING_WINO, "wino + ring");
+                r.g = gz;
+                r.wt += align4(wino_wt_floats(&gz));
+                r.add_job(wino_layout_mode(&gz, true), KH, KW, 0, 1, 0, 1, wt_n);
+                slabs = std::max(slabs, wino_ws_floats(&gz));
+            } else if (n16_shape_ok(d, d->Cin, d->Cout)) r.set(Fam::RING_N16, "n16 + ring");
+            else r.set(Fam::RING_DIRECT, "direct");
+        }
+        r.ws = shape_ok ? padded + slabs : 0;
+    }
+    return r;
 }
-extern "C" int fd_conv2d_fwd(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt,
-                             int wt_ready, float* ws, void* stream) {
-    return conv2d_fwd_impl(d, x, w, bias, y, wt, wt_ready, ws, nullptr, stream);
+
+// Weight gradient.  The limb kernels need 16-byte aligned tensors: the family they fall back to is part of the route, and the
+// workspace covers both.
+Route route_wgrad(const fd_conv_desc* d) {
+    Route r;
+    ConvShape s;
+    if (!conv_out_shape(d, s)) return r;
+    const long wsz = (long)d->Cout * d->Cin * d->KH * d->KW;
+    long slabs;
+    if (narrow_wgrad_ok(d)) { r.set(Fam::NARROW, "narrow"); slabs = narrow_wgrad_ws_floats(d); }
+    else if (stem_wgrad_ok(d)) { r.set(Fam::STEM_WGRAD, "stem"); slabs = stem_wgrad_ws_floats(d); }
+    else if (wino_use_wgrad(d)) { r.set(Fam::WINO, "wino"); slabs = wino_wgrad_ws_floats(d); }
+    else if (fast_wgrad_ok(d)) {
+        r.set(Fam::DIRECT, "direct");
+        slabs = (long)fast_wgrad_splits(d->Cout, d->Cin, d->KH * d->KW, (long)d->N * s.Ho * s.Wo) * wsz;
+    } else {
+        r.set(Fam::GENERIC, "generic");
+        const int sp = wgrad_splits(d, s);
+        slabs = sp > 1 ? (long)sp * wsz : 0;
+    }
+    r.fallback = r.fam; r.fallback_name = r.name;
+    if (limb_wgrad_ok(d)) {
+        r.set(Fam::LIMB_1X1, "limb 1x1");
+        slabs = std::max(slabs, limb_wgrad_ws_floats(d->Cout, d->Cin, d->N, d->H * d->W));
+    } else if (limb_conv_wgrad_ok(d, s)) {
+        r.set(Fam::LIMB_S2, "limb direct");
+        slabs = std::max(slabs, limb_wgrad_s2_ws_floats(d->Cout, d->Cin, d->N, s.Ho * s.Wo, d->KH * d->KW));
+    }
+    if (slabs < wsz) slabs = wsz;                        // accumulate mode stages a single slab
+    r.ws = std::max(slabs, (long)d->Cout * CS_SPLITS);   // the bias gradient's partials: the two uses are sequential on the stream
+    return r;
 }
-extern "C" int fd_conv2d_fwd_bn_ok(const fd_conv_desc* d, int groups) {
-    if (!d || check_desc(d, "fd_conv2d_fwd_bn_ok")) return 0;
-    if (!(fast_fwd_ok(d) && wino_use_fwd(d) && wino_fwd_slab_route(d)) || d->act != 0 || c1_shape_ok(d) || n16_shape_ok(d, d->Cout, d->Cin)) return 0;
-    return bn_small_slabs_ok(d->N, d->Cout, d->H, d->W, groups) ? 1 : 0;
+
+// The stand-alone weight re-layout launches of the route's jobs [first, first + n) (wt_ready == 0).
+int relayout_launch(const Route& r, const fd_conv_desc* d, const float* w, float* wt, hipStream_t st, int first = 0, int n = -1) {
+    for (int i = first; i < (n < 0 ? r.njobs : first + n); ++i) {
+        const Job& j = r.job[i];
+        float* dst = wt + j.off;
+        int rc = 0;
+        if (j.mode <= 1) rc = fast_weight_relayout(w, dst, d->Cout, d->Cin, d->KH, d->KW, j.TA, j.TB, j.kh0, j.dkh, j.kw0, j.dkw, j.mode, st);
+        else if (j.mode == 7 || j.mode == 8)
+            rc = limb_weight_split_launch(w, dst, j.mode == 7 ? d->Cout : d->Cin, j.mode == 7 ? d->Cin : d->Cout, j.mode - 7, st);
+        else if (j.mode == 9 || j.mode == 10)
+            rc = limb_conv_weight_split_launch(w, dst, d->Cout, d->Cin, d->KH, d->KW, j.TA, j.TB, j.kh0, j.dkh, j.kw0, j.dkw, j.mode - 9, st);
+        else if (j.mode != 2) rc = wino_weight_launch(&r.g, w, dst, j.mode % 2 == 0, st);   // U of r.g: 3 / 5 / 11, flipped 4 / 6 / 12
+        else {
+            hipLaunchKernelGGL(k_weight_relayout, dim3(ew_blocks((long)d->Cin * d->Cout * j.TA * j.TB)), dim3(256), 0, st, w, dst,
+                               d->Cout, d->Cin, d->KH, d->KW, j.TA, j.TB, j.kh0, j.dkh, j.kw0, j.dkw);
+            FD_LAUNCH_CHECK("fd_conv2d_bwd_data(relayout)");
+        }
+        if (rc) return rc;
+    }
+    return 0;
 }
-extern "C" int fd_conv2d_fwd_bn(const fd_conv_desc* d, const float* x, const float* w, float* y, float* wt, int wt_ready, float* ws,
-                                const float* bn_weight, const float* bn_bias, const float* residual, float* out, float* running_mean,
-                                float* running_var, float* save_mean, float* save_invstd, int groups, float eps, float momentum, int relu,
-                                void* stream) {
-    FD_REQUIRE(fd_conv2d_fwd_bn_ok(d, groups), "fd_conv2d_fwd_bn: not a slab-route 3x3 convolution followed by a small-plane BatchNorm (fd_conv2d_fwd_bn_ok == 0)");
-    FD_REQUIRE(x && w && y && wt && ws && out && save_mean && save_invstd, "fd_conv2d_fwd_bn: NULL argument");
-    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "fd_conv2d_fwd_bn: running stats must come in pairs");
-    hipStream_t st = (hipStream_t)stream;
-    conv_log("fwd", "wino + bn", d);
-    if (!wt_ready)
-        if (int rc = wino_weight_launch(d, w, wt, 0, st)) return rc;
-    BnAfterConv bn = {bn_weight, bn_bias, residual, out, running_mean, running_var, save_mean, save_invstd, groups, eps, momentum, relu};
-    return wino_conv_launch(d, x, wt, nullptr, y, ws, st, nullptr, nullptr, &bn);
+
+void reflect_fold_launch(const float* gpad, float* gx, const fd_conv_desc* d, hipStream_t st) {
+    const long planes = (long)d->N * d->Cin, bx = ((long)d->H * d->W + 255) / 256;
+    hipLaunchKernelGGL(k_reflect_fold, dim3((unsigned)(bx > 64 ? 64 : bx), (unsigned)(planes > 32768 ? 32768 : planes)), dim3(256), 0, st,
+                       gpad, gx, planes, d->H, d->W);
 }
-extern "C" long fd_conv2d_fwd_stat_slots(const fd_conv_desc* d) {
-    if (!d || check_desc(d, "fd_conv2d_fwd_stat_slots")) return 0;
-    return (fast_fwd_ok(d) && wino_use_fwd(d)) ? wino_stat_slots(d) : 0;
-}
-extern "C" int fd_conv2d_fwd_stats(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt,
-                                   int wt_ready, float* ws, float* stat_part, void* stream) {
-    FD_REQUIRE(stat_part, "fd_conv2d_fwd_stats: stat_part is NULL");
-    FD_REQUIRE(fd_conv2d_fwd_stat_slots(d) > 0, "fd_conv2d_fwd_stats: this convolution has no statistics epilogue (fd_conv2d_fwd_stat_slots == 0)");
-    return conv2d_fwd_impl(d, x, w, bias, y, wt, wt_ready, ws, stat_part, stream);
-}
-namespace {
-int conv2d_fwd_impl(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt, int wt_ready,
-                    float* ws, float* stat_part, void* stream) {
-    if (int rc = check_desc(d, "fd_conv2d_fwd")) return rc;
+
+int conv2d_fwd_impl(const fd_conv_desc* d, const Route& r, const float* x, const float* w, const float* bias, float* y, float* wt,
+                    int wt_ready, float* ws, float* stat_part, hipStream_t st) {
     FD_REQUIRE(x && w && y, "fd_conv2d_fwd: NULL tensor");
     ConvShape s;
     FD_REQUIRE(conv_out_shape(d, s), "fd_conv2d_fwd: empty output");
     FD_REQUIRE((long)d->N * d->Cin * d->H * d->W < (1L << 29) && (long)d->N * d->Cout * s.Ho * s.Wo < (1L << 29),
                "fd_conv2d_fwd: tensor too large for 32-bit byte offsets (2 GiB per tensor)");
-    hipStream_t st = (hipStream_t)stream;
-    if (c1_shape_ok(d)) {
-        FD_REQUIRE(!stat_part, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
-        conv_log("fwd", "c1 stencil", d);
-        return c1_fwd_launch(d, x, w, bias, y, st);
-    }
-    if (fast_fwd_ok(d) && n16_shape_ok(d, d->Cout, d->Cin)) {
-        FD_REQUIRE(!stat_part, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
-        conv_log("fwd", "n16", d);
-        return n16_launch(d, d->Cout, d->Cin, x, w, bias, y, 0, d->pad_mode, d->act, st);
-    }
-    if (!bias && stem7_fwd_ok(d)) {
-        FD_REQUIRE(!stat_part, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
-        conv_log("fwd", "stem7", d);
-        return stem7_fwd_launch(d, x, w, bias, y, st);
-    }
-    if (fast_fwd_ok(d)) {
+    FD_REQUIRE(!stat_part || r.stat_slots > 0, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
+    const Fam fam = (r.fam == Fam::STEM7 && bias) ? Fam::GENERIC : r.fam;     // the stem kernels have no bias
+    conv_log("fwd", fam == r.fam ? r.name : "generic", d);
+    if (r.njobs) {
         FD_REQUIRE(wt, "fd_conv2d_fwd: weight-layout buffer required (fd_conv2d_fwd_wt_floats)");
-        if (limb_fwd_ok(d)) {
-            FD_REQUIRE(!stat_part, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
-            conv_log("fwd", "limb 1x1", d);
-            if (!wt_ready)
-                if (int rc = limb_weight_split_launch(w, wt, d->Cout, d->Cin, 0, st)) return rc;
-            return limb_gemm_launch(wt, x, y, bias, nullptr, ws, d->Cout, d->Cin, d->N, d->H * d->W, d->act, st);
-        }
-        if (wino_use_fwd(d)) {
-            conv_log("fwd", "wino", d);
-            if (!wt_ready)
-                if (int rc = wino_weight_launch(d, w, wt, 0, st)) return rc;
-            return wino_conv_launch(d, x, wt, bias, y, ws, st, nullptr, stat_part);
-        }
+        if (!wt_ready)
+            if (int rc = relayout_launch(r, d, w, wt, st)) return rc;
+    }
+    switch (fam) {
+    case Fam::C1: return c1_fwd_launch(d, x, w, bias, y, st);
+    case Fam::N16: return n16_launch(d, d->Cout, d->Cin, x, w, bias, y, 0, d->pad_mode, d->act, st);
+    case Fam::STEM7: return stem7_fwd_launch(d, x, w, bias, y, st);
+    case Fam::LIMB_1X1: return limb_gemm_launch(wt, x, y, bias, nullptr, ws, d->Cout, d->Cin, d->N, d->H * d->W, d->act, st);
+    case Fam::WINO: return wino_conv_launch(d, x, wt, bias, y, ws, st, nullptr, stat_part);
+    case Fam::LIMB_S2: case Fam::DIRECT: {
         FastGemmArgs f;
         fill_fwd_args(d, s, f);
-        if (limb_conv_fwd_ok(d)) {
-            FD_REQUIRE(!stat_part, "fd_conv2d_fwd_stats: no statistics epilogue for this shape");
-            conv_log("fwd", "limb direct", d);
-            if (!wt_ready)
-                if (int rc = limb_conv_weight_split_launch(w, wt, d->Cout, d->Cin, d->KH, d->KW, d->KH, d->KW, 0, 1, 0, 1, 0, st)) return rc;
-            f.A = wt; f.X = x; f.Y = y; f.bias = bias;
-            f.slabs = ws;
-            return limb_conv_launch(f, st);
-        }
-        conv_log("fwd", "direct", d);
-        if (!wt_ready)
-            if (int rc = fast_weight_relayout(w, wt, d->Cout, d->Cin, d->KH, d->KW, d->KH, d->KW, 0, 1, 0, 1, 0, st)) return rc;
         f.A = wt; f.X = x; f.Y = y; f.bias = bias;
         f.slabs = ws;
-        return fast_gemm_launch(f, st);
+        return fam == Fam::LIMB_S2 ? limb_conv_launch(f, st) : fast_gemm_launch(f, st);
+    }
+    default: break;
     }
     GemmArgs g = {};
     g.A = w; g.X = x; g.Y = y; g.bias = bias;
@@ -1048,91 +1179,18 @@ int conv2d_fwd_impl(const fd_conv_desc* d, const float* x, const float* w, const
     FD_LAUNCH_CHECK("fd_conv2d_fwd");
     return 0;
 }
-}  // namespace
 
-extern "C" long fd_conv2d_bwd_data_wt_floats(const fd_conv_desc* d) {
-    if (!d || c1_shape_ok(d)) return 0;
-    if (limb_dgrad_ok(d)) return align4(limb_wt_floats(d->Cin, d->Cout));
-    fd_conv_desc g;
-    if (wino_dgrad_desc(d, g)) return align4(wino_wt_floats(&g));
-    if (refl_wino_padded(d, g)) return align4(wino_wt_floats(&g));
-    if (refl_wino_interior(d, g))                            // [layout of the ring's implicit GEMM | U of the interior's Winograd kernel]
-        return align4((long)d->Cin * d->Cout * d->KH * d->KW) + align4(wino_wt_floats(&g));
-    return (d->stride == 1 ? 1 : 4) * align4((long)d->Cin * d->Cout * d->KH * d->KW);
-}
-
-extern "C" long fd_conv2d_bwd_data_ws_floats(const fd_conv_desc* d) {
-    if (!d) return 0;
-    ConvShape s;
-    if (!conv_out_shape(d, s) || c1_shape_ok(d)) return 0;
-    if (limb_dgrad_ok(d)) return limb_gemm_ws_floats(d->Cin, d->Cout, d->N, d->H * d->W);
-    {
-        fd_conv_desc g;
-        if (wino_dgrad_desc(d, g)) return wino_ws_floats(&g);
-    }
-    const long wt = 0;
-    const long padded = d->pad_mode == 1 ? align4((long)d->N * d->Cin * (d->H + 2) * (d->W + 2)) : 0;
-    long slabs = 0;
-    if (fast_dgrad_ok(d) && d->stride == 1) {          // split-K only on the stride-1 path
-        FastGemmArgs f = {};
-        f.M = d->Cin; f.C = d->Cout; f.T = d->KH * d->KW; f.Nb = d->N;
-        f.NY = d->pad_mode == 1 ? d->H + 2 : d->H; f.NX = d->pad_mode == 1 ? d->W + 2 : d->W;
-        f.osy = 1; f.osx = 1;
-        f.out_total = (long)d->N * d->Cin * f.NY * f.NX;
-        slabs = fast_splitk_slab_floats(f, nullptr);
-        if (d->pad_mode == 1) {                        // the interior-plus-ring path runs the H x W problem: its own split count
-            f.NY = d->H; f.NX = d->W;
-            f.out_total = (long)d->N * d->Cin * f.NY * f.NX;
-            const long s2 = fast_splitk_slab_floats(f, nullptr);
-            slabs = s2 > slabs ? s2 : slabs;
-            fd_conv_desc gz;
-            if (refl_wino_padded(d, gz))                     // [padded-grid gradient | slabs | dY in its border of zeros]
-                return padded + wino_ws_floats(&gz) + align4((long)d->N * d->Cout * (d->H + 2) * (d->W + 2));
-            if (refl_wino_interior(d, gz)) { const long s3 = wino_ws_floats(&gz); slabs = s3 > slabs ? s3 : slabs; }
-        }
-    }
-    return wt + padded + slabs;
-}
-
-namespace {
-int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float* gx, float* wt_base, int wt_ready, float* ws,
-                  void* stream, const float* gx_add = nullptr);
-}
-extern "C" int fd_axpby(const float* a, const float* b, float* out, long n, float alpha, float beta, void* stream);   // pool.hip
-extern "C" int fd_conv2d_bwd_data(const fd_conv_desc* d, const float* gy, const float* w, float* gx, float* wt_base,
-                                  int wt_ready, float* ws, void* stream) {
-    return bwd_data_impl(d, gy, w, gx, wt_base, wt_ready, ws, stream);
-}
-extern "C" int fd_conv2d_bwd_data_add(const fd_conv_desc* d, const float* gy, const float* w, const float* gx_add, float* gx,
-                                      float* wt_base, int wt_ready, float* ws, void* stream) {
-    FD_REQUIRE(gx_add != gx, "fd_conv2d_bwd_data_add: gx_add must not alias gx");
-    return bwd_data_impl(d, gy, w, gx, wt_base, wt_ready, ws, stream, gx_add);
-}
-extern "C" int fd_act_bwd(const float* y, const float* gy, float* gpre, long n, int act, void* stream);   // pool.hip
-extern "C" int fd_conv2d_bwd_data_inact(const fd_conv_desc* d, const float* gy, const float* w, const float* x_in, int in_act, float* gx,
-                                        float* wt_base, int wt_ready, float* ws, void* stream) {
-    if (int rc = check_desc(d, "fd_conv2d_bwd_data_inact")) return rc;
-    FD_REQUIRE(x_in && in_act >= 1 && in_act <= 4, "fd_conv2d_bwd_data_inact: needs the layer's input and an activation id 1..4");
-    if (c1_shape_ok(d)) {                                // dispconv: the factor act'(x_in) rides in the stencil's store
-        FD_REQUIRE(gy && w && gx, "fd_conv2d_bwd_data_inact: NULL tensor");
-        conv_log("dgrad", "c1 stencil * act'(input)", d);
-        return c1_dgrad_launch(d, gy, w, gx, (hipStream_t)stream, x_in, in_act);
-    }
-    if (int rc = bwd_data_impl(d, gy, w, gx, wt_base, wt_ready, ws, stream, nullptr)) return rc;
-    return fd_act_bwd(x_in, gx, gx, (long)d->N * d->Cin * d->H * d->W, in_act, stream);       // every other kernel family: one element-wise pass
-}
-namespace {
-int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float* gx, float* wt_base, int wt_ready, float* ws,
-                  void* stream, const float* gx_add) {
-    if (int rc = check_desc(d, "fd_conv2d_bwd_data")) return rc;
+int bwd_data_impl(const fd_conv_desc* d, const Route& r, const float* gy, const float* w, float* gx, float* wt_base, int wt_ready,
+                  float* ws, void* stream, const float* gx_add = nullptr) {
     // gx_add joins in the epilogue of the MFMA kernels (and of their split-K reduction); the remaining paths (generic gather
     // GEMM, reflect padding with its fold pass, parity classes without taps) add it with one element-wise launch afterwards
     const long gx_n = (long)d->N * d->Cin * d->H * d->W;
     auto add_after = [&]() -> int { return gx_add ? fd_axpby(gx, gx_add, gx, gx_n, 1.0f, 1.0f, stream) : 0; };
-    if (c1_shape_ok(d)) {                                // dispconv: a stencil with the reflect adjoint folded in (conv_c1.hip)
+    hipStream_t st = (hipStream_t)stream;
+    conv_log("dgrad", r.name, d);
+    if (r.fam == Fam::C1) {                              // dispconv: a stencil with the reflect adjoint folded in (conv_c1.hip)
         FD_REQUIRE(gy && w && gx, "fd_conv2d_bwd_data: NULL tensor");
-        conv_log("dgrad", "c1 stencil", d);
-        if (int rc = c1_dgrad_launch(d, gy, w, gx, (hipStream_t)stream)) return rc;
+        if (int rc = c1_dgrad_launch(d, gy, w, gx, st)) return rc;
         return add_after();
     }
     FD_REQUIRE(gy && w && gx && wt_base, "fd_conv2d_bwd_data: NULL tensor");
@@ -1140,42 +1198,42 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
     FD_REQUIRE(conv_out_shape(d, s), "fd_conv2d_bwd_data: empty output");
     FD_REQUIRE((long)d->N * d->Cin * (d->H + 2) * (d->W + 2) < (1L << 29) && (long)d->N * d->Cout * s.Ho * s.Wo < (1L << 29),
                "fd_conv2d_bwd_data: tensor too large for 32-bit byte offsets (2 GiB per tensor)");
-    hipStream_t st = (hipStream_t)stream;
     const int KH = d->KH, KW = d->KW;
-    if (limb_dgrad_ok(d)) {                              // 1x1 stride 1: gx[n][ci][p] = sum_co W[co][ci] gy[n][co][p], one GEMM with the transposed weights
-        conv_log("dgrad", "limb 1x1", d);
-        if (!wt_ready)
-            if (int rc = limb_weight_split_launch(w, wt_base, d->Cin, d->Cout, 1, st)) return rc;
-        return limb_gemm_launch(wt_base, gy, gx, nullptr, gx_add, ws, d->Cin, d->Cout, d->N, d->H * d->W, 0, st);
-    }
-    {
-        fd_conv_desc gd;
-        conv_log("dgrad", wino_dgrad_desc(d, gd) ? "wino" : (d->stride == 2 && fast_dgrad_ok(d) && limb_conv_dgrad_ok(d)) ? "limb direct" : "direct", d);
-        if (wino_dgrad_desc(d, gd)) {
-            if (!wt_ready)
-                if (int rc = wino_weight_launch(&gd, w, wt_base, 1, st)) return rc;
-            return wino_conv_launch(&gd, gy, wt_base, nullptr, gx, ws, st, gx_add);
-        }
-    }
-    const bool fast = fast_dgrad_ok(d);
-    bool add_in_kernel = false;
-    const long wt_n = align4((long)d->Cin * d->Cout * KH * KW);
-    float* wt = wt_base;                       // per parity class: wt_base + class * wt_n
-    float* gpad = ws;
     const long pad_n = d->pad_mode == 1 ? align4((long)d->N * d->Cin * (d->H + 2) * (d->W + 2)) : 0;
-    float* slabs = ws ? ws + pad_n : nullptr;
     FD_REQUIRE(ws || (pad_n == 0), "fd_conv2d_bwd_data: workspace required for reflect padding");
+    float* gpad = ws;
+    float* slabs = ws ? ws + pad_n : nullptr;
+    if (!wt_ready && d->stride == 1)                     // (stride 2: each parity class's re-layout just before its launch, below)
+        if (int rc = relayout_launch(r, d, w, wt_base, st)) return rc;
+
+    switch (r.fam) {
+    case Fam::LIMB_1X1:                                  // gx[n][ci][p] = sum_co W[co][ci] gy[n][co][p]
+        return limb_gemm_launch(wt_base, gy, gx, nullptr, gx_add, ws, d->Cin, d->Cout, d->N, d->H * d->W, 0, st);
+    case Fam::WINO:
+        return wino_conv_launch(&r.g, gy, wt_base, nullptr, gx, ws, st, gx_add);
+    case Fam::WINO_PADDED: {
+        const long planes_in = (long)d->N * d->Cout, bx = ((long)(d->H + 2) * (d->W + 2) + 255) / 256;
+        float* gyp = slabs + wino_ws_floats(&r.g);
+        hipLaunchKernelGGL(k_zero_border_copy, dim3((unsigned)(bx > 64 ? 64 : bx), (unsigned)(planes_in > 32768 ? 32768 : planes_in)), dim3(256), 0, st,
+                           gy, gyp, planes_in, d->H, d->W);
+        FD_LAUNCH_CHECK("fd_conv2d_bwd_data(zero border)");
+        if (int rc = wino_conv_launch(&r.g, gyp, wt_base, nullptr, gpad, slabs, st, nullptr)) return rc;
+        reflect_fold_launch(gpad, gx, d, st);
+        FD_LAUNCH_CHECK("fd_conv2d_bwd_data(fold)");
+        return add_after();
+    }
+    default: break;
+    }
+    const bool fast = r.fam != Fam::GENERIC;
 
     // common geometry of "a conv over gy": channels = Cout, spatial = Ho x Wo
     GemmArgs g = {};
     g.X = gy; g.bias = nullptr; g.act = 0; g.in_norm = 0; g.pad_mode = 0;
     g.M = d->Cin; g.Nb = d->N; g.C = d->Cout; g.Hi = s.Ho; g.Wi = s.Wo;
-    auto run = [&](int TA, int TB, int kh0, int dkh, int kw0, int dkw, bool allow_split) -> int {
+    auto run = [&](const float* A, int TA, int TB, const float* add) -> int {
         if (fast) {
-            if (!wt_ready)
-                if (int rc = fast_weight_relayout(w, wt, d->Cout, d->Cin, KH, KW, TA, TB, kh0, dkh, kw0, dkw, 1, st)) return rc;
             FastGemmArgs f = {};
-            f.A = wt; f.X = gy; f.Y = g.Y; f.bias = nullptr;
+            f.A = A; f.X = gy; f.Y = g.Y; f.bias = nullptr;
             f.M = d->Cin; f.C = d->Cout; f.T = TA * TB; f.TB = TB; f.K = f.T * f.C;
             f.Nb = d->N; f.Hi = s.Ho; f.Wi = s.Wo; f.NY = g.NY; f.NX = g.NX;
             f.sy = g.sy; f.oy = g.oy; f.da = g.da; f.sx = g.sx; f.ox = g.ox; f.db = g.db;
@@ -1184,16 +1242,10 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
             f.osy = g.osy; f.ooy = g.ooy; f.osx = g.osx; f.oox = g.oox;
             f.out_total = (long)d->N * g.out_ns; f.slab_stride = f.out_total;
             f.slabs = slabs;       // split-K is only chosen for unit-stride outputs (fast_splitk_slab_floats)
-            f.add = add_in_kernel ? gx_add : nullptr;
-            (void)allow_split;
+            f.add = add;
             return fast_gemm_launch(f, st);
         }
-        if (!wt_ready) {
-            hipLaunchKernelGGL(k_weight_relayout, dim3(ew_blocks((long)d->Cin * d->Cout * TA * TB)), dim3(256), 0, st, w, wt,
-                               d->Cout, d->Cin, KH, KW, TA, TB, kh0, dkh, kw0, dkw);
-            FD_LAUNCH_CHECK("fd_conv2d_bwd_data(relayout)");
-        }
-        g.A = wt; g.K = d->Cout * TA * TB;
+        g.A = A; g.K = d->Cout * TA * TB;
         if (int rc = dispatch_gemm(TA, TB, g, st)) return rc;
         FD_LAUNCH_CHECK("fd_conv2d_bwd_data(gemm)");
         return 0;
@@ -1202,58 +1254,26 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
     if (d->stride == 1) {
         g.sy = 1; g.da = 1; g.sx = 1; g.db = 1;
         g.osy = 1; g.ooy = 0; g.osx = 1; g.oox = 0;
-        const int ring_on = fd_tun().reflect_ring;
-        fd_conv_desc gz;
-        if (d->pad_mode == 1 && refl_wino_padded(d, gz)) {
-            conv_log("dgrad", "wino on the padded grid + fold", d);
-            const long planes_in = (long)d->N * d->Cout, planes_out = (long)d->N * d->Cin;
-            const long np = (long)(d->H + 2) * (d->W + 2);
-            float* wslabs = ws + pad_n;
-            float* gyp = wslabs + wino_ws_floats(&gz);
-            if (!wt_ready)
-                if (int rc = wino_weight_launch(&gz, w, wt, 1, st)) return rc;
-            const long bx = (np + 255) / 256;
-            hipLaunchKernelGGL(k_zero_border_copy, dim3((unsigned)(bx > 64 ? 64 : bx), (unsigned)(planes_in > 32768 ? 32768 : planes_in)), dim3(256), 0, st,
-                               gy, gyp, planes_in, d->H, d->W);
-            FD_LAUNCH_CHECK("fd_conv2d_bwd_data(zero border)");
-            if (int rc = wino_conv_launch(&gz, gyp, wt, nullptr, gpad, wslabs, st, nullptr)) return rc;
-            const long fold_bx = ((long)d->H * d->W + 255) / 256;
-            hipLaunchKernelGGL(k_reflect_fold, dim3((unsigned)(fold_bx > 64 ? 64 : fold_bx), (unsigned)(planes_out > 32768 ? 32768 : planes_out)),
-                               dim3(256), 0, st, gpad, gx, planes_out, d->H, d->W);
-            FD_LAUNCH_CHECK("fd_conv2d_bwd_data(fold)");
-            return add_after();
-        }
-        const bool wino_interior = refl_wino_interior(d, gz);
-        if (d->pad_mode == 1 && fast && ring_on && KH == 3 && KW == 3 && d->pad == 1 && d->H >= 2 && d->W >= 2 &&
-            (wino_interior || (long)d->H * d->W >= (ring_on > 1 ? ring_on : 16384))) {      // smaller planes (measured up to 48 x 160): four thin launches + their fold cost more than the fold pass
+        if (r.fam == Fam::RING_WINO || r.fam == Fam::RING_N16 || r.fam == Fam::RING_DIRECT) {
             // Reflect padding, 3x3: (1) the interior of the padded grid = the zero-padded data gradient, straight into gx (with the
             // second gradient of the tensor, if any, in the epilogue); (2) the ring's four strips as ONE grouped launch of thin
             // problems into a small buffer; (3) k_reflect_ring_fold.  The padded-grid gradient + k_reflect_fold of rounds 1-2 wrote
             // and re-read the whole (H+2) x (W+2) tensor on the decoder's serial chain (0.65 ms per training step).
             g.NY = d->H; g.NX = d->W; g.oy = -1; g.ox = -1;
             g.Y = gx; g.out_w = d->W; g.out_cs = (long)d->H * d->W; g.out_ns = g.out_cs * d->Cin;
-            add_in_kernel = false;       // a second gradient of the tensor (not used by the decoder) is added after the fold, so
-                                         // that the sum keeps the order (interior + ring) + other of the fold path, bit for bit
-            if (wino_interior) {                         // the decoder's wide blocks: the interior on the Winograd kernels
-                conv_log("dgrad", "wino + ring", d);
-                float* wt_wino = wt + wt_n;
-                if (!wt_ready) {
-                    if (int rc = fast_weight_relayout(w, wt, d->Cout, d->Cin, KH, KW, KH, KW, KH - 1, -1, KW - 1, -1, 1, st)) return rc;
-                    if (int rc = wino_weight_launch(&gz, w, wt_wino, 1, st)) return rc;
-                }
-                if (int rc = wino_conv_launch(&gz, gy, wt_wino, nullptr, gx, slabs, st, nullptr)) return rc;
-            } else if (n16_shape_ok(d, d->Cin, d->Cout)) {      // the zero-padded data gradient of a 16 / 32-channel block: conv_n16.hip on dY
-                conv_log("dgrad", "n16 + ring", d);
-                if (!wt_ready)                           // the ring below still runs on the implicit-GEMM kernel and its layout
-                    if (int rc = fast_weight_relayout(w, wt, d->Cout, d->Cin, KH, KW, KH, KW, KH - 1, -1, KW - 1, -1, 1, st)) return rc;
+            // a second gradient of the tensor (not used by the decoder) is added after the fold, so that the sum keeps the order
+            // (interior + ring) + other of the fold path, bit for bit
+            if (r.fam == Fam::RING_WINO) {               // the decoder's wide blocks: the interior on the Winograd kernels
+                if (int rc = wino_conv_launch(&r.g, gy, wt_base + r.job[1].off, nullptr, gx, slabs, st, nullptr)) return rc;
+            } else if (r.fam == Fam::RING_N16) {         // the zero-padded data gradient of a 16 / 32-channel block: conv_n16.hip on dY
                 if (int rc = n16_launch(d, d->Cin, d->Cout, gy, w, nullptr, gx, 1, 0, 0, st)) return rc;
-            } else if (int rc = run(KH, KW, KH - 1, -1, KW - 1, -1, true)) return rc;
+            } else if (int rc = run(wt_base, KH, KW, nullptr)) return rc;
             const int Hp = d->H, Wp2 = d->W + 2;
             const long ring_plane = 2L * Wp2 + 2L * Hp;
             float* ring = gpad;                                   // [N][Cin][top W+2 | bottom W+2 | left H | right H]
             FastGemmArgs f = {};
             FastGemmGroup q = {};
-            f.A = wt; f.X = gy; f.Y = ring; f.bias = nullptr;
+            f.A = wt_base; f.X = gy; f.Y = ring; f.bias = nullptr;
             f.M = d->Cin; f.C = d->Cout; f.T = 9; f.TB = 3; f.K = 9 * d->Cout;
             f.Nb = d->N; f.Hi = s.Ho; f.Wi = s.Wo;
             f.sy = 1; f.da = 1; f.sx = 1; f.db = 1; f.pad_mode = 0;       // the flip is in the weight layout (kh0 = 2, dkh = -1)
@@ -1264,7 +1284,7 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
             const int oy4[4] = {-2, -2 + d->H + 1, -1, -1}, ox4[4] = {-2, -2, -2, -2 + d->W + 1};
             const long yoff[4] = {0, Wp2, 2L * Wp2, 2L * Wp2 + Hp};
             for (int j = 0; j < 4; ++j) {
-                q.A[j] = wt; q.NY[j] = ny[j]; q.NX[j] = nx[j]; q.oy[j] = oy4[j]; q.ox[j] = ox4[j]; q.ooy[j] = 0; q.oox[j] = 0;
+                q.A[j] = wt_base; q.NY[j] = ny[j]; q.NX[j] = nx[j]; q.oy[j] = oy4[j]; q.ox[j] = ox4[j]; q.ooy[j] = 0; q.oox[j] = 0;
                 q.T[j] = 9; q.TB[j] = 3; q.K[j] = 9 * d->Cout;
                 q.y_off[j] = yoff[j]; q.out_w[j] = nx[j]; q.out_cs[j] = ring_plane; q.out_ns[j] = ring_plane * d->Cin;
             }
@@ -1282,33 +1302,21 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
             g.NY = d->H + 2; g.NX = d->W + 2; g.oy = -(KH - 1); g.ox = -(KW - 1);
             g.Y = gpad; g.out_w = d->W + 2;
             g.out_cs = (long)(d->H + 2) * (d->W + 2); g.out_ns = g.out_cs * d->Cin;
-            if (int rc = run(KH, KW, KH - 1, -1, KW - 1, -1, true)) return rc;
-            const long n = (long)d->N * d->Cin * d->H * d->W;
-            const long fold_planes = (long)d->N * d->Cin, fold_bx = ((long)d->H * d->W + 255) / 256;
-            hipLaunchKernelGGL(k_reflect_fold, dim3((unsigned)(fold_bx > 64 ? 64 : fold_bx), (unsigned)(fold_planes > 32768 ? 32768 : fold_planes)),
-                               dim3(256), 0, st, gpad, gx, fold_planes, d->H, d->W);
+            if (int rc = run(wt_base, KH, KW, nullptr)) return rc;
+            reflect_fold_launch(gpad, gx, d, st);
             FD_LAUNCH_CHECK("fd_conv2d_bwd_data(fold)");
             return add_after();
         }
         g.NY = d->H; g.NX = d->W; g.oy = -(KH - 1 - d->pad); g.ox = -(KW - 1 - d->pad);
         g.Y = gx; g.out_w = d->W; g.out_cs = (long)d->H * d->W; g.out_ns = g.out_cs * d->Cin;
-        add_in_kernel = fast && gx_add;
-        if (int rc = run(KH, KW, KH - 1, -1, KW - 1, -1, true)) return rc;
-        return add_in_kernel ? 0 : add_after();
+        const float* add = fast ? gx_add : nullptr;
+        if (int rc = run(wt_base, KH, KW, add)) return rc;
+        return add ? 0 : add_after();
     }
-    // stride 2: four output-parity classes, each a dense conv over its own tap subset
+    // stride 2: the route's output-parity classes, each a dense conv over its own tap subset
     g.out_w = d->W; g.out_cs = (long)d->H * d->W; g.out_ns = g.out_cs * d->Cin; g.Y = gx;
-    bool need_zero = false;
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw)
-            if (((ph + d->pad) & 1) >= KH || ((pw + d->pad) & 1) >= KW) need_zero = true;
-    if (need_zero) {
-        if (hipMemsetAsync(gx, 0, sizeof(float) * (size_t)d->N * d->Cin * d->H * d->W, st) != hipSuccess) {
-            fd_set_error("fd_conv2d_bwd_data: memset failed");
-            return -1;
-        }
-    }
-    add_in_kernel = fast && gx_add && !need_zero;       // every element of gx is written by exactly one parity class
+    FD_REQUIRE(!r.need_zero || hipMemsetAsync(gx, 0, sizeof(float) * (size_t)gx_n, st) == hipSuccess, "fd_conv2d_bwd_data: memset failed");
+    const float* add = fast && !r.need_zero ? gx_add : nullptr;     // every element of gx is written by exactly one parity class
     if (fast) {
         // the (up to) four classes in ONE launch: alone, a class has a quarter of the pixels and no split-K (its output is strided) -
         // 92 workgroups for layer4.0 at batch 24; four launches in a row measured 253 us there (27 TFLOP/s)
@@ -1322,105 +1330,120 @@ int bwd_data_impl(const fd_conv_desc* d, const float* gy, const float* w, float*
         f.out_ns = g.out_ns; f.out_cs = g.out_cs; f.out_w = g.out_w;
         f.osy = 2; f.osx = 2;
         f.out_total = (long)d->N * g.out_ns; f.slab_stride = f.out_total; f.slabs = nullptr;
-        f.add = add_in_kernel ? gx_add : nullptr;
+        f.add = add;
         // the classes' weights: [Cin][(tap, Cout)] fp32 for k_conv_fast_grp, or its pre-split image for k_conv_limb_grp (in the same slots:
         // 1.5 x (<= 4 of 9 taps) of a slot; a 1x1 kernel has one class and four slots)
-        const bool limb_s2 = limb_conv_dgrad_ok(d);
         // (classes with the most taps first: their workgroups are the launch's longest - 4, 2, 2, 1 taps for a 3x3 kernel with pad 1)
-        for (int ph = 1; ph >= 0; --ph)
-            for (int pw = 1; pw >= 0; --pw) {
-                const int kh0 = (ph + d->pad) & 1, kw0 = (pw + d->pad) & 1;
-                if (kh0 >= KH || kw0 >= KW) continue;
-                const int TA = (KH - kh0 + 1) / 2, TB = (KW - kw0 + 1) / 2;
-                const int NY = (d->H - ph + 1) / 2, NX = (d->W - pw + 1) / 2;
-                if (NY <= 0 || NX <= 0) continue;
-                float* wc = wt_base + (long)(ph * 2 + pw) * wt_n;
-                if (!wt_ready) {
-                    if (limb_s2) { if (int rc = limb_conv_weight_split_launch(w, wc, d->Cout, d->Cin, KH, KW, TA, TB, kh0, 2, kw0, 2, 1, st)) return rc; }
-                    else if (int rc = fast_weight_relayout(w, wc, d->Cout, d->Cin, KH, KW, TA, TB, kh0, 2, kw0, 2, 1, st)) return rc;
-                }
-                const int j = q.n++;
-                q.A[j] = wc; q.NY[j] = NY; q.NX[j] = NX;
-                q.oy[j] = (ph + d->pad - kh0) / 2; q.ox[j] = (pw + d->pad - kw0) / 2;
-                q.ooy[j] = ph; q.oox[j] = pw;
-                q.T[j] = TA * TB; q.TB[j] = TB; q.K[j] = TA * TB * d->Cout;
-            }
+        for (int i = r.njobs - 1; i >= 0; --i) {
+            const Job& c = r.job[i];
+            if (!wt_ready)
+                if (int rc = relayout_launch(r, d, w, wt_base, st, i, 1)) return rc;
+            const int j = q.n++;
+            q.A[j] = wt_base + c.off; q.NY[j] = (d->H - c.ph + 1) / 2; q.NX[j] = (d->W - c.pw + 1) / 2;
+            q.oy[j] = (c.ph + d->pad - c.kh0) / 2; q.ox[j] = (c.pw + d->pad - c.kw0) / 2;
+            q.ooy[j] = c.ph; q.oox[j] = c.pw;
+            q.T[j] = c.TA * c.TB; q.TB[j] = c.TB; q.K[j] = c.TA * c.TB * d->Cout;
+        }
         if (q.n > 0) {
             f.A = q.A[0]; f.NY = q.NY[0]; f.NX = q.NX[0]; f.T = q.T[0]; f.TB = q.TB[0]; f.K = q.K[0];
-            if (limb_s2) { if (int rc = limb_conv_group_launch(f, q, st)) return rc; }
+            if (r.fam == Fam::LIMB_S2) { if (int rc = limb_conv_group_launch(f, q, st)) return rc; }
             else if (int rc = fast_gemm_group_launch(f, q, st)) return rc;
         }
-        return add_in_kernel ? 0 : add_after();
+        return add ? 0 : add_after();
     }
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-            const int kh0 = (ph + d->pad) & 1, kw0 = (pw + d->pad) & 1;
-            if (kh0 >= KH || kw0 >= KW) continue;
-            const int TA = (KH - kh0 + 1) / 2, TB = (KW - kw0 + 1) / 2;
-            const int NY = (d->H - ph + 1) / 2, NX = (d->W - pw + 1) / 2;
-            if (NY <= 0 || NX <= 0) continue;
-            g.NY = NY; g.NX = NX;
-            g.sy = 1; g.oy = (ph + d->pad - kh0) / 2; g.da = -1;
-            g.sx = 1; g.ox = (pw + d->pad - kw0) / 2; g.db = -1;
-            g.osy = 2; g.ooy = ph; g.osx = 2; g.oox = pw;
-            wt = wt_base + (long)(ph * 2 + pw) * wt_n;
-            if (int rc = run(TA, TB, kh0, 2, kw0, 2, false)) return rc;
-        }
-    return add_in_kernel ? 0 : add_after();
+    for (int i = 0; i < r.njobs; ++i) {
+        const Job& c = r.job[i];
+        if (!wt_ready)
+            if (int rc = relayout_launch(r, d, w, wt_base, st, i, 1)) return rc;
+        g.NY = (d->H - c.ph + 1) / 2; g.NX = (d->W - c.pw + 1) / 2;
+        g.sy = 1; g.oy = (c.ph + d->pad - c.kh0) / 2; g.da = -1;
+        g.sx = 1; g.ox = (c.pw + d->pad - c.kw0) / 2; g.db = -1;
+        g.osy = 2; g.ooy = c.ph; g.osx = 2; g.oox = c.pw;
+        if (int rc = run(wt_base + c.off, c.TA, c.TB, nullptr)) return rc;
+    }
+    return add_after();
 }
 }  // namespace
 
-namespace {
-// re-layout mode of a Winograd layout: `g` = the convolution the kernel computes (for a data gradient: channels already swapped)
-inline int wino_layout_mode(const fd_conv_desc* g, bool dgrad) {
-    if (wino_fwd_limb(g)) return dgrad ? 12 : 11;
-    if (wino_fwd_2d(g)) return dgrad ? 6 : 5;
-    return dgrad ? 4 : 3;
+extern "C" long fd_conv2d_fwd_wt_floats(const fd_conv_desc* d) { return d ? route_fwd(d).wt : 0; }
+extern "C" long fd_conv2d_fwd_ws_floats(const fd_conv_desc* d) { return d ? route_fwd(d).ws : 0; }
+
+extern "C" int fd_conv2d_fwd(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt,
+                             int wt_ready, float* ws, void* stream) {
+    if (int rc = check_desc(d, "fd_conv2d_fwd")) return rc;
+    return conv2d_fwd_impl(d, route_fwd(d), x, w, bias, y, wt, wt_ready, ws, nullptr, (hipStream_t)stream);
 }
-}  // namespace
+extern "C" int fd_conv2d_fwd_bn_ok(const fd_conv_desc* d, int groups) {
+    if (!d || check_desc(d, "fd_conv2d_fwd_bn_ok")) return 0;
+    return route_fwd(d).bn && bn_small_slabs_ok(d->N, d->Cout, d->H, d->W, groups) ? 1 : 0;
+}
+extern "C" int fd_conv2d_fwd_bn(const fd_conv_desc* d, const float* x, const float* w, float* y, float* wt, int wt_ready, float* ws,
+                                const float* bn_weight, const float* bn_bias, const float* residual, float* out, float* running_mean,
+                                float* running_var, float* save_mean, float* save_invstd, int groups, float eps, float momentum, int relu,
+                                void* stream) {
+    FD_REQUIRE(fd_conv2d_fwd_bn_ok(d, groups), "fd_conv2d_fwd_bn: not a slab-route 3x3 convolution followed by a small-plane BatchNorm (fd_conv2d_fwd_bn_ok == 0)");
+    FD_REQUIRE(x && w && y && wt && ws && out && save_mean && save_invstd, "fd_conv2d_fwd_bn: NULL argument");
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "fd_conv2d_fwd_bn: running stats must come in pairs");
+    hipStream_t st = (hipStream_t)stream;
+    conv_log("fwd", "wino + bn", d);
+    if (!wt_ready)
+        if (int rc = relayout_launch(route_fwd(d), d, w, wt, st)) return rc;
+    BnAfterConv bn = {bn_weight, bn_bias, residual, out, running_mean, running_var, save_mean, save_invstd, groups, eps, momentum, relu};
+    return wino_conv_launch(d, x, wt, nullptr, y, ws, st, nullptr, nullptr, &bn);
+}
+extern "C" long fd_conv2d_fwd_stat_slots(const fd_conv_desc* d) {
+    if (!d || check_desc(d, "fd_conv2d_fwd_stat_slots")) return 0;
+    return route_fwd(d).stat_slots;
+}
+extern "C" int fd_conv2d_fwd_stats(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, float* wt,
+                                   int wt_ready, float* ws, float* stat_part, void* stream) {
+    FD_REQUIRE(stat_part, "fd_conv2d_fwd_stats: stat_part is NULL");
+    if (int rc = check_desc(d, "fd_conv2d_fwd_stats")) return rc;
+    const Route r = route_fwd(d);
+    FD_REQUIRE(r.stat_slots > 0, "fd_conv2d_fwd_stats: this convolution has no statistics epilogue (fd_conv2d_fwd_stat_slots == 0)");
+    return conv2d_fwd_impl(d, r, x, w, bias, y, wt, wt_ready, ws, stat_part, (hipStream_t)stream);
+}
+
+extern "C" long fd_conv2d_bwd_data_wt_floats(const fd_conv_desc* d) { return d ? route_dgrad(d).wt : 0; }
+extern "C" long fd_conv2d_bwd_data_ws_floats(const fd_conv_desc* d) { return d ? route_dgrad(d).ws : 0; }
+
+extern "C" int fd_conv2d_bwd_data(const fd_conv_desc* d, const float* gy, const float* w, float* gx, float* wt_base,
+                                  int wt_ready, float* ws, void* stream) {
+    if (int rc = check_desc(d, "fd_conv2d_bwd_data")) return rc;
+    return bwd_data_impl(d, route_dgrad(d), gy, w, gx, wt_base, wt_ready, ws, stream);
+}
+extern "C" int fd_conv2d_bwd_data_add(const fd_conv_desc* d, const float* gy, const float* w, const float* gx_add, float* gx,
+                                      float* wt_base, int wt_ready, float* ws, void* stream) {
+    FD_REQUIRE(gx_add != gx, "fd_conv2d_bwd_data_add: gx_add must not alias gx");
+    if (int rc = check_desc(d, "fd_conv2d_bwd_data")) return rc;
+    return bwd_data_impl(d, route_dgrad(d), gy, w, gx, wt_base, wt_ready, ws, stream, gx_add);
+}
+extern "C" int fd_conv2d_bwd_data_inact(const fd_conv_desc* d, const float* gy, const float* w, const float* x_in, int in_act, float* gx,
+                                        float* wt_base, int wt_ready, float* ws, void* stream) {
+    if (int rc = check_desc(d, "fd_conv2d_bwd_data_inact")) return rc;
+    FD_REQUIRE(x_in && in_act >= 1 && in_act <= 4, "fd_conv2d_bwd_data_inact: needs the layer's input and an activation id 1..4");
+    const Route r = route_dgrad(d);
+    if (r.fam == Fam::C1) {                              // dispconv: the factor act'(x_in) rides in the stencil's store
+        FD_REQUIRE(gy && w && gx, "fd_conv2d_bwd_data_inact: NULL tensor");
+        conv_log("dgrad", "c1 stencil * act'(input)", d);
+        return c1_dgrad_launch(d, gy, w, gx, (hipStream_t)stream, x_in, in_act);
+    }
+    if (int rc = bwd_data_impl(d, r, gy, w, gx, wt_base, wt_ready, ws, stream, nullptr)) return rc;
+    return fd_act_bwd(x_in, gx, gx, (long)d->N * d->Cin * d->H * d->W, in_act, stream);       // every other kernel family: one element-wise pass
+}
+
 extern "C" int fd_conv2d_relayout_jobs(const fd_conv_desc* d, int kind, const float* w, float* wt, fd_relayout_job* jobs) {
     if (check_desc(d, "fd_conv2d_relayout_jobs") || !w || !wt || !jobs) return 0;
-    auto fill = [&](fd_relayout_job& j, float* dst, int TA, int TB, int kh0, int dkh, int kw0, int dkw, int mode) {
+    const Route r = kind == 0 ? route_fwd(d) : route_dgrad(d);
+    for (int i = 0; i < r.njobs; ++i) {
+        const Job& c = r.job[i];
+        fd_relayout_job& j = jobs[i];
         j = fd_relayout_job{};
-        j.w = w; j.dst = dst; j.Co = d->Cout; j.Ci = d->Cin; j.KH = d->KH; j.KW = d->KW;
-        j.TA = TA; j.TB = TB; j.kh0 = kh0; j.dkh = dkh; j.kw0 = kw0; j.dkw = dkw; j.mode = mode;
-        j.n = (long)d->Cout * d->Cin * TA * TB;
-    };
-    if (c1_shape_ok(d)) return 0;                        // stencil kernels: no layouts
-    if (kind == 0) {
-        if (!fast_fwd_ok(d) || n16_shape_ok(d, d->Cout, d->Cin)) return 0;
-        if (limb_fwd_ok(d)) { fill(jobs[0], wt, 1, 1, 0, 1, 0, 1, 7); return 1; }
-        fill(jobs[0], wt, d->KH, d->KW, 0, 1, 0, 1, wino_use_fwd(d) ? wino_layout_mode(d, false) : (limb_conv_fwd_ok(d) ? 9 : 0));
-        return 1;
+        j.w = w; j.dst = wt + c.off; j.Co = d->Cout; j.Ci = d->Cin; j.KH = d->KH; j.KW = d->KW;
+        j.TA = c.TA; j.TB = c.TB; j.kh0 = c.kh0; j.dkh = c.dkh; j.kw0 = c.kw0; j.dkw = c.dkw; j.mode = c.mode;
+        j.n = (long)d->Cout * d->Cin * c.TA * c.TB;
     }
-    const int KH = d->KH, KW = d->KW;
-    if (limb_dgrad_ok(d)) { fill(jobs[0], wt, 1, 1, 0, 1, 0, 1, 8); return 1; }
-    {
-        fd_conv_desc gd;
-        if (wino_dgrad_desc(d, gd)) { fill(jobs[0], wt, KH, KW, 0, 1, 0, 1, wino_layout_mode(&gd, true)); return 1; }
-    }
-    const int mode = fast_dgrad_ok(d) ? 1 : 2;
-    if (d->stride == 1) {
-        fd_conv_desc gz;
-        if (refl_wino_padded(d, gz)) { fill(jobs[0], wt, KH, KW, 0, 1, 0, 1, wino_layout_mode(&gz, true)); return 1; }
-        fill(jobs[0], wt, KH, KW, KH - 1, -1, KW - 1, -1, mode);
-        if (refl_wino_interior(d, gz)) {                 // second layout behind the first: U of the interior's Winograd kernel
-            fill(jobs[1], wt + align4((long)d->Cin * d->Cout * KH * KW), KH, KW, 0, 1, 0, 1, wino_layout_mode(&gz, true));
-            return 2;
-        }
-        return 1;
-    }
-    const long wt_n = align4((long)d->Cin * d->Cout * KH * KW);
-    int n = 0;
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {                 // same enumeration as fd_conv2d_bwd_data
-            const int kh0 = (ph + d->pad) & 1, kw0 = (pw + d->pad) & 1;
-            if (kh0 >= KH || kw0 >= KW) continue;
-            const int TA = (KH - kh0 + 1) / 2, TB = (KW - kw0 + 1) / 2;
-            if ((d->H - ph + 1) / 2 <= 0 || (d->W - pw + 1) / 2 <= 0) continue;
-            fill(jobs[n++], wt + (long)(ph * 2 + pw) * wt_n, TA, TB, kh0, 2, kw0, 2, (mode == 1 && limb_conv_dgrad_ok(d)) ? 10 : mode);
-        }
-    return n;
+    return r.njobs;
 }
 
 extern "C" long fd_relayout_plan(fd_relayout_job* jobs, int n) {
@@ -1436,37 +1459,7 @@ extern "C" int fd_relayout_batch(const fd_relayout_job* jobs_dev, int n, long to
     return 0;
 }
 
-namespace {
-int wgrad_splits(const fd_conv_desc* d, const ConvShape& s) {
-    const long Np = (long)d->N * s.Ho * s.Wo;
-    const long J = (long)d->Cin * d->KH * d->KW;
-    const long tiles = J <= 64 ? (long)fd_cdiv(d->Cout, 64) : (long)fd_cdiv(J, 128) * fd_cdiv(d->Cout, d->Cout <= 32 ? 32 : 64);
-    long want = (768 + tiles - 1) / tiles;            // ~3 workgroups per CU
-    long maxs = (Np + 511) / 512;                     // at least 512 pixels per split
-    long sp = want < maxs ? want : maxs;
-    if (sp < 1) sp = 1;
-    if (sp > 96) sp = 96;
-    return (int)sp;
-}
-}  // namespace
-
-extern "C" long fd_conv2d_bwd_weight_ws_floats(const fd_conv_desc* d) {
-    if (!d) return 0;
-    ConvShape s;
-    if (!conv_out_shape(d, s)) return 0;
-    const long wsz = (long)d->Cout * d->Cin * d->KH * d->KW;
-    long slabs;
-    if (narrow_wgrad_ok(d)) slabs = narrow_wgrad_ws_floats(d);
-    else if (stem_wgrad_ok(d)) slabs = stem_wgrad_ws_floats(d);
-    else if (wino_use_wgrad(d)) slabs = wino_wgrad_ws_floats(d);
-    else if (fast_wgrad_ok(d)) slabs = (long)fast_wgrad_splits(d->Cout, d->Cin, d->KH * d->KW, (long)d->N * s.Ho * s.Wo) * wsz;
-    else { const int sp = wgrad_splits(d, s); slabs = sp > 1 ? (long)sp * wsz : 0; }
-    if (limb_wgrad_ok(d)) { const long l = limb_wgrad_ws_floats(d->Cout, d->Cin, d->N, d->H * d->W); slabs = l > slabs ? l : slabs; }   // (the direct kernel stays the fallback for unaligned tensors)
-    if (limb_conv_wgrad_ok(d, s)) { const long l = limb_wgrad_s2_ws_floats(d->Cout, d->Cin, d->N, s.Ho * s.Wo, d->KH * d->KW); slabs = l > slabs ? l : slabs; }
-    const long bias_part = (long)d->Cout * CS_SPLITS;
-    if (slabs < wsz) slabs = wsz;                            // accumulate mode stages a single slab
-    return slabs > bias_part ? slabs : bias_part;          // the two uses are sequential on the stream
-}
+extern "C" long fd_conv2d_bwd_weight_ws_floats(const fd_conv_desc* d) { return d ? route_wgrad(d).ws : 0; }
 
 extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const float* gy, float* gw, float* gbias,
                                     float* ws, int accumulate, void* stream) {
@@ -1478,20 +1471,19 @@ extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const
                "fd_conv2d_bwd_weight: tensor too large for 32-bit byte offsets (2 GiB per tensor)");
     hipStream_t st = (hipStream_t)stream;
     const long Np = (long)d->N * s.Ho * s.Wo;
-    const bool limb_w = limb_wgrad_ok(d) && (((uintptr_t)x | (uintptr_t)gy) & 15) == 0;
-    const bool limb_w2 = !limb_w && limb_conv_wgrad_ok(d, s) && (((uintptr_t)x | (uintptr_t)gy) & 15) == 0;
-    conv_log("wgrad", limb_w ? "limb 1x1" : limb_w2 ? "limb direct" : narrow_wgrad_ok(d) ? "narrow" : stem_wgrad_ok(d) ? "stem" : wino_use_wgrad(d) ? "wino" : fast_wgrad_ok(d) ? "direct" : "generic", d);
-    if (limb_w) {
-        if (int rc = limb_wgrad_launch(x, gy, gw, ws, d->Cout, d->Cin, d->N, d->H * d->W, accumulate, st)) return rc;
-    } else if (limb_w2) {
-        if (int rc = limb_wgrad_s2_launch(x, gy, gw, ws, d->Cout, d->Cin, d->N, d->H, d->W, s.Ho, s.Wo, d->KH * d->KW, accumulate, st)) return rc;
-    } else if (narrow_wgrad_ok(d)) {
-        if (int rc = narrow_wgrad_launch(d, x, gy, gw, ws, accumulate, st)) return rc;
-    } else if (stem_wgrad_ok(d)) {
-        if (int rc = stem_wgrad_launch(d, x, gy, gw, ws, accumulate, st)) return rc;
-    } else if (wino_use_wgrad(d)) {
-        if (int rc = wino_wgrad_launch(d, x, gy, gw, ws, accumulate, st)) return rc;
-    } else if (fast_wgrad_ok(d)) {
+    const Route r = route_wgrad(d);
+    const bool aligned = (((uintptr_t)x | (uintptr_t)gy) & 15) == 0;
+    const bool limb = r.fam == Fam::LIMB_1X1 || r.fam == Fam::LIMB_S2;
+    const Fam fam = limb && !aligned ? r.fallback : r.fam;
+    conv_log("wgrad", limb && !aligned ? r.fallback_name : r.name, d);
+    int rc = 0;
+    switch (fam) {
+    case Fam::LIMB_1X1: rc = limb_wgrad_launch(x, gy, gw, ws, d->Cout, d->Cin, d->N, d->H * d->W, accumulate, st); break;
+    case Fam::LIMB_S2: rc = limb_wgrad_s2_launch(x, gy, gw, ws, d->Cout, d->Cin, d->N, d->H, d->W, s.Ho, s.Wo, d->KH * d->KW, accumulate, st); break;
+    case Fam::NARROW: rc = narrow_wgrad_launch(d, x, gy, gw, ws, accumulate, st); break;
+    case Fam::STEM_WGRAD: rc = stem_wgrad_launch(d, x, gy, gw, ws, accumulate, st); break;
+    case Fam::WINO: rc = wino_wgrad_launch(d, x, gy, gw, ws, accumulate, st); break;
+    case Fam::DIRECT: {
         FastWgradArgs f = {};
         f.dY = gy; f.X = x; f.slabs = ws;
         f.M = d->Cout; f.C = d->Cin; f.T = d->KH * d->KW; f.TB = d->KW;
@@ -1499,8 +1491,10 @@ extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const
         f.sy = d->stride; f.oy = -d->pad; f.da = 1; f.sx = d->stride; f.ox = -d->pad; f.db = 1;
         f.pad_mode = d->pad_mode;
         f.dy_cs = (long)s.Ho * s.Wo; f.dy_ns = f.dy_cs * d->Cout;
-        if (int rc = fast_wgrad_launch(f, gw, fast_wgrad_splits(f.M, f.C, f.T, Np), accumulate, st)) return rc;
-    } else {
+        rc = fast_wgrad_launch(f, gw, fast_wgrad_splits(f.M, f.C, f.T, Np), accumulate, st);
+        break;
+    }
+    default: {
         const int sp = wgrad_splits(d, s);
         const bool staged = sp > 1 || accumulate;
         WgradArgs g = {};
@@ -1514,7 +1508,7 @@ extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const
         long pps = (Np + sp - 1) / sp;
         pps = (pps + 31) / 32 * 32;
         g.pix_per_split = pps;
-        if (int rc = dispatch_wgrad(d->KH, d->KW, g, sp, st)) return rc;
+        if ((rc = dispatch_wgrad(d->KH, d->KW, g, sp, st))) return rc;
         FD_LAUNCH_CHECK("fd_conv2d_bwd_weight");
         if (staged) {
             const long n = (long)g.M * g.J;
@@ -1522,6 +1516,8 @@ extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const
             FD_LAUNCH_CHECK("fd_conv2d_bwd_weight(reduce)");
         }
     }
+    }
+    if (rc) return rc;
     if (gbias) {
         const long plane = (long)s.Ho * s.Wo;
         const bool vec = (plane & 3) == 0 && ((uintptr_t)gy & 15) == 0;
