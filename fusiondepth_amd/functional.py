@@ -1014,7 +1014,8 @@ def _conv_forward(ctx, x, w, bias, stride, pad, pad_mode, act, in_norm, want_sta
     ws = _empty((nws,), x) if nws > 0 else None
     wt, ready = _weight_layout(w, cache_id, "f", nwt, d) if nwt > 0 else (None, 0)
     part = None
-    if want_stats and plan.stat_slots > 0:
+    # a view off a 16-byte boundary: some statistics epilogues need an aligned input, so BatchNorm makes its own pass instead
+    if want_stats and plan.stat_slots > 0 and x.data_ptr() % 16 == 0:
         part = _empty((d.N, d.Cout, plan.stat_slots, 2), x)
         call("fd_conv2d_fwd_stats", plan.dp, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(wt), ready, ptr(ws), ptr(part), stream())
     else:
