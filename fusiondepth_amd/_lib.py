@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FD_LIBFDHIP") or os.path.join(_HERE, "libfdhip.so")   # FD_LIBFDHIP: ablation builds (scripts/)
-ABI_VERSION = 5
+ABI_VERSION = 6
 PHOTO_OUT_FLOATS = 96        # FD_PHOTO_OUT_FLOATS
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -43,6 +43,12 @@ class RefineCfg(ctypes.Structure):
 class ConvDesc(ctypes.Structure):
     """Mirror of ``fd_conv_desc``."""
     _fields_ = [(n, _I) for n in ("N", "Cin", "H", "W", "Cout", "KH", "KW", "stride", "pad", "pad_mode", "act", "in_norm")]
+
+
+class JitterDesc(ctypes.Structure):
+    """Mirror of ``fd_jitter_desc``."""
+    _fields_ = [("src_off", _L), ("u8_off", _L), ("planes_off", _L), ("plain_off", _L), ("H", _I), ("W", _I), ("factor", _F * 4),
+                ("order", _I * 4), ("n_ops", _I), ("hue_shift", _I)]
 
 
 class RelayoutJob(ctypes.Structure):
@@ -157,6 +163,12 @@ SIGNATURES = {
     "fd_gdc_build": ("ppp" "iiiii" "ddddddd" "pp", "i"),
     "fd_gdc_cg_iters": ("piiiip", "i"),
     "fd_gdc_finish": ("ppp" "iiiii" "ppp", "i"),
+    "fd_resize_lanczos_u8_ws_bytes": ("iiiii", "l"),
+    "fd_resize_lanczos_u8": ("pp" "iiiii" "pipi" "ppp", "i"),
+    "fd_color_jitter_u8_ws_bytes": ("i", "l"),
+    "fd_color_jitter_u8_means_offset": ("i", "l"),
+    "fd_color_jitter_u8": ("plplpl" "pil" "pp", "i"),
+    "fd_u8_to_planes": ("pp" "iii" "l" "p", "i"),
 }
 
 _lock = threading.Lock()

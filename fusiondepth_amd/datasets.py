@@ -1,0 +1,334 @@
+"""KITTI raw training batches, built on the GPU: the reference's ``KITTIRAWDataset`` (datasets/mono_dataset.py:33-228,
+datasets/kitti_dataset.py:28-117) plus the ``DataLoader`` around it (trainer.py:155-171), as one iterable that yields
+collated batches on the device in the reference's schema.
+
+    loader = KITTIRAWBatches(data_path, filenames, 192, 640, [0, -1, 1], 4, is_train=True, img_ext=".jpg", opt=opts,
+                             batch_size=12, shuffle=True, seed=0)
+    Trainer(opts).train(loader)
+
+What runs where
+  * host, on a thread pool of at most 16 workers: ``PIL.Image.open(path).convert("RGB")`` per frame and ``np.fromfile`` per
+    LiDAR scan (PIL is imported here, lazily, and nowhere else in the package);
+  * device: the frames are uploaded as uint8 and everything after the decoder runs in HIP kernels - the four-level Lanczos
+    pyramid, colour jitter and ``ToTensor`` (``FD.image_pyramid``), the ``4beam`` rasterisation, the ``2channel`` scatter
+    (computed online from the beam map: no ``.npy`` files are read) and ``depth_gt``.
+  * the builder issues batch i + 1 on its own stream before it hands batch i to the consumer; the hand-over is an event the
+    consumer's stream waits on (the pattern of ``refiner.prefetch_frozen``).  All device work is issued from the calling thread.
+
+Colour jitter policy.  The reference's docstring (mono_dataset.py:88-90) promises that "the same augmentation" reaches all
+images of an item.  That was true of its monodepth2 ancestor, which called ``ColorJitter.get_params(...)`` once per item and got
+back one fixed transform (torchvision < 0.9; from 0.9 on ``get_params`` returns the raw draw instead).  The reference itself
+builds a ``ColorJitter`` OBJECT per item (mono_dataset.py:178) and calls it on every frame and scale, and in the torchvision
+sources known to us (0.9 and later) ``ColorJitter.forward`` draws the order and the four factors afresh on every call - so
+there every image gets its own draw.  Default here: what the docstring promises, ONE draw per item shared by all of its frames
+and scales; ``jitter_per_image=True`` gives one draw per (frame, scale), the behaviour of the object under torchvision >= 0.9.
+torchvision is not installed where this package is built, so both statements are second-hand (read from its published source),
+like the ResNet trunk's layout.
+
+Deviation from the reference, on purpose: it rasterises ``4beam`` at the fixed ``[384, 1280]`` (a ``[192, 640]`` map) whatever
+``height`` / ``width`` are, and its ``2channel`` files are made for that size.  Here the map is rasterised at ``[2 height, 2 width]``
+and scattered with the ROI scaled to match - identical at the reference's 192x640, and usable by the trainer at other sizes, where
+the reference's fixed-size map does not fit the network's input.  As in the reference, ``("2channel", f, 0)`` exists whenever
+``need_2_channel`` is set; ``"4beam"`` and ``"2channel"`` only with ``need_4beam``.
+
+Not covered (each raises): the stereo frame ``"s"``, ``need_full_res_4beam`` (needs cv2), ``need_inf_gdc`` / ``clone_gdc``.
+"""
+import concurrent.futures
+import os
+
+import numpy as np
+import torch
+
+from . import functional as FD
+from . import kitti_utils
+from . import synthetic
+
+SIDE_MAP = {"2": 2, "3": 3, "l": 2, "r": 3}                  # kitti_dataset.py:42
+JITTER_RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))     # mono_dataset.py:65-68
+
+
+def pil_loader(path):
+    """mono_dataset.py:14-17 -> [H,W,3] uint8."""
+    from PIL import Image
+    with open(path, "rb") as f:
+        with Image.open(f) as img:
+            return np.asarray(img.convert("RGB"))
+
+
+def parse_line(line):
+    """One split-file line ``"<folder> <frame> <side>"`` -> (folder, frame_index, side); a bare folder gives (folder, 0, None)
+    (mono_dataset.py:138-154)."""
+    parts = line.split()
+    if len(parts) == 3:
+        return parts[0], int(parts[1]), parts[2]
+    return parts[0], 0, None
+
+
+class KITTIRAWBatches:
+    """See the module docstring.  The first nine arguments are ``KITTIRAWDataset``'s; ``batch_size`` / ``shuffle`` are the
+    ``DataLoader``'s (``drop_last=True``).  ``seed`` seeds the epoch order and the per-item draws, ``workers`` sizes the decode pool
+    (at most 16), ``draws`` = callable ``(epoch, index) -> dict`` that replaces ``item_draws`` (tests inject flags and jitter
+    parameters through it), ``loader`` = callable ``path -> [H,W,3] uint8`` instead of the PIL decoder (pre-decoded frames),
+    ``prefetch`` = issue the next batch on a side stream before handing out the current one."""
+
+    def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
+                 batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
+                 prefetch=True):
+        self.data_path, self.filenames = data_path, list(filenames)
+        self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
+        self.frame_idxs = list(frame_idxs)
+        self.is_train, self.img_ext, self.opt = bool(is_train), img_ext, opt
+        self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
+        self.device = torch.device(device)
+        self.workers = max(1, min(int(workers), 16))
+        self.jitter_per_image = bool(jitter_per_image)
+        self.draws, self.loader, self.prefetch = draws, loader or pil_loader, bool(prefetch)
+        if self.batch_size < 1:
+            raise ValueError("KITTIRAWBatches: batch_size must be positive")
+        if "s" in self.frame_idxs:
+            raise NotImplementedError("KITTIRAWBatches: the stereo frame 's' is not covered (temporal frames only)")
+        if self._opt("need_full_res_4beam"):
+            raise NotImplementedError("KITTIRAWBatches: need_full_res_4beam is not covered (the reference resizes with cv2)")
+        if self._opt("need_inf_gdc") or self._opt("clone_gdc"):
+            raise NotImplementedError("KITTIRAWBatches: need_inf_gdc / clone_gdc are not covered (no inf_gdc maps are loaded)")
+        if 0 not in self.frame_idxs:
+            raise ValueError("KITTIRAWBatches: frame_idxs must contain 0 (the frame every network and the LiDAR keys refer to)")
+        self.need_4beam = bool(self._opt("need_4beam"))
+        self.need_2_channel = bool(self._opt("need_2_channel"))
+        self.load_depth = self.check_depth()
+        self._epoch = 0
+        self._pool = None
+        self._stream = None
+        self._K = None
+        self._calib = {}
+
+    def _opt(self, name, default=False):
+        return getattr(self.opt, name, default) if self.opt is not None else default
+
+    # ---- paths (kitti_dataset.py:44-54, 72-76, 93-103) --------------------------------------------------------------------------
+    def get_image_path(self, folder, frame_index, side):
+        return os.path.join(self.data_path, folder, "image_0{}/data".format(SIDE_MAP[side]), "{:010d}{}".format(frame_index, self.img_ext))
+
+    def get_velo_path(self, folder, frame_index):
+        return os.path.join(self.data_path, folder, "velodyne_points/data/{:010d}.bin".format(int(frame_index)))
+
+    def beam_folder(self):
+        random_sample = self._opt("random_sample", -1)
+        return "random{}".format(random_sample) if random_sample > 0 else "{}beam".format(self._opt("nbeams", 4))
+
+    def get_beam_path(self, folder, frame_index):
+        return os.path.join(self.data_path, folder, "{}/{:010d}.bin".format(self.beam_folder(), int(frame_index)))
+
+    def check_depth(self):
+        if not self.filenames:
+            return False
+        folder, frame_index, _ = parse_line(self.filenames[0])
+        return os.path.isfile(self.get_velo_path(folder, frame_index))
+
+    def close(self):
+        """Stop the decode pool (idle threads otherwise live as long as the object)."""
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- order and draws --------------------------------------------------------------------------------------------------------
+    def __len__(self):
+        return len(self.filenames) // self.batch_size            # drop_last=True
+
+    def epoch_order(self, epoch):
+        """Item indices of one epoch, in batch order (the trailing partial batch is dropped)."""
+        n = len(self.filenames)
+        order = np.random.default_rng([self.seed, int(epoch)]).permutation(n) if self.shuffle else np.arange(n)
+        return [int(i) for i in order[:len(self) * self.batch_size]]
+
+    def item_draws(self, epoch, index):
+        """The random part of one item, a function of (seed, epoch, index) alone: ``do_color_aug`` and ``do_flip`` (``random() > 0.5``
+        each, training only) and ``jitter``: one ``((brightness, contrast, saturation, hue), order)`` draw, or with
+        ``jitter_per_image`` a list ``[frame][scale]`` of them; None without colour augmentation."""
+        if self.draws is not None:
+            return self.draws(epoch, index)
+        rng = np.random.default_rng([self.seed, int(epoch), int(index), 1])
+        do_color_aug = self.is_train and rng.random() > 0.5
+        do_flip = self.is_train and rng.random() > 0.5
+
+        def one():
+            order = [int(o) for o in rng.permutation(4)]
+            return tuple(float(rng.uniform(lo, hi)) for lo, hi in JITTER_RANGES), order
+
+        jitter = None
+        if do_color_aug:
+            jitter = [[one() for _ in range(self.num_scales)] for _ in self.frame_idxs] if self.jitter_per_image else one()
+        return {"do_color_aug": bool(do_color_aug), "do_flip": bool(do_flip), "jitter": jitter}
+
+    # ---- host side of a batch ---------------------------------------------------------------------------------------------------
+    def _workers(self):
+        if self._pool is None:
+            self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers)
+        return self._pool
+
+    def plan_batch(self, epoch, indices):
+        """Everything about a batch that needs no device: per item (folder, frame, side, draws) and the files to read."""
+        items = []
+        for index in indices:
+            folder, frame_index, side = parse_line(self.filenames[index])
+            d = self.item_draws(epoch, index)
+            item = {"index": index, "folder": folder, "frame_index": frame_index, "side": side, "date": folder.split("/")[0],
+                    "do_flip": bool(d["do_flip"]), "jitter": d["jitter"] if d["do_color_aug"] else None,
+                    "images": [self.get_image_path(folder, frame_index + f, side) for f in self.frame_idxs],
+                    "beams": [], "velo": None}
+            if self.need_4beam or self.need_2_channel:
+                frames = self.frame_idxs if self.need_2_channel else [0]
+                item["beams"] = [self.get_beam_path(folder, frame_index + f) for f in frames]
+            if self.load_depth:
+                item["velo"] = self.get_velo_path(folder, frame_index)
+            items.append(item)
+        return items
+
+    def _start_host(self, epoch, indices):
+        """Submit the file work of a batch to the pool."""
+        items = self.plan_batch(epoch, indices)
+        pool = self._workers()
+        for it in items:
+            it["image_futures"] = [pool.submit(self.loader, p) for p in it["images"]]
+            it["beam_futures"] = [pool.submit(kitti_utils.load_velodyne_points, p) for p in it["beams"]]
+            it["velo_future"] = pool.submit(kitti_utils.load_velodyne_points, it["velo"]) if it["velo"] else None
+        return items
+
+    def _projection(self, date, cam):
+        key = (date, cam)
+        if key not in self._calib:
+            self._calib[key] = kitti_utils.velo_to_image(os.path.join(self.data_path, date), cam)
+        return self._calib[key]
+
+    # ---- device side of a batch -------------------------------------------------------------------------------------------------
+    def _colour_keys(self, items, batch):
+        B, F = len(items), len(self.frame_idxs)
+        frames = [[f.result() for f in it["image_futures"]] for it in items]
+        groups = {}                                              # native size -> [(frame slot, item)]: drives differ in size
+        for fi in range(F):                                      # frame-major: with one native size every key is a contiguous slice
+            for b in range(B):
+                groups.setdefault(frames[b][fi].shape, []).append((fi, b))
+        sizes = [(self.height // 2 ** s, self.width // 2 ** s) for s in range(self.num_scales)]
+        whole = {}
+        for shape, members in groups.items():
+            if len(shape) != 3 or shape[2] != 3:
+                raise RuntimeError("KITTIRAWBatches: a decoded frame has shape %s, expected [H,W,3]" % (shape,))
+            stack = torch.from_numpy(np.stack([frames[b][fi] for fi, b in members])).to(self.device, non_blocking=True)
+            flip = [items[b]["do_flip"] for _, b in members]
+            jitter = None
+            if any(it["jitter"] is not None for it in items):
+                jitter = []
+                for fi, b in members:
+                    j = items[b]["jitter"]
+                    jitter.append(j[fi] if isinstance(j, list) else j)
+            pyr = FD.image_pyramid(stack, self.height, self.width, self.num_scales, flip, jitter)
+            if len(groups) == 1:
+                whole = pyr
+                break
+            slots = torch.tensor([fi * B + b for fi, b in members], device=self.device)
+            for s, (h, w) in enumerate(sizes):
+                for name in ("color", "color_aug"):
+                    if (name, s) not in whole:
+                        whole[(name, s)] = torch.empty((F * B, 3, h, w), device=self.device)
+                    whole[(name, s)][slots] = pyr[(name, s)]
+        for fi, f in enumerate(self.frame_idxs):
+            for s in range(self.num_scales):
+                for name in ("color", "color_aug"):
+                    batch[(name, f, s)] = whole[(name, s)][fi * B:(fi + 1) * B]
+
+    def _lidar_keys(self, items, batch):
+        if self.need_4beam or self.need_2_channel:
+            per_item = len(items[0]["beams"])
+            beams = []
+            for k in range(per_item):                            # frame-major, like the colour keys
+                for it in items:
+                    P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
+                    pts = torch.from_numpy(it["beam_futures"][k].result()).to(self.device, non_blocking=True)
+                    beam = FD.velo_rasterize(pts, P, im_h, im_w, (2 * self.height, 2 * self.width))     # [384, 1280] at 192x640
+                    beams.append(torch.flip(beam, dims=[1]) if it["do_flip"] else beam)
+            beams = torch.stack(beams).unsqueeze(1).contiguous()
+            B = len(items)
+            zero = self.frame_idxs.index(0) if self.need_2_channel else 0
+            if self.need_2_channel:                              # mono_dataset.py:162-163: one per frame, with or without need_4beam
+                two = FD.scatter_2channel(beams, FD.scaled_roi(self.height, self.width))
+                for fi, f in enumerate(self.frame_idxs):
+                    batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
+            if self.need_4beam:                                  # mono_dataset.py:193-206
+                batch["4beam"] = beams[zero * B:(zero + 1) * B]
+                if self.need_2_channel:
+                    batch["2channel"] = two[zero * B:(zero + 1) * B]
+        if self.load_depth:
+            maps = []
+            for it in items:
+                P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
+                pts = torch.from_numpy(it["velo_future"].result()).to(self.device, non_blocking=True)
+                full = FD.velo_rasterize(pts, P, im_h, im_w, (375, 1242), return_full=True, beam=False)
+                maps.append((torch.flip(full, dims=[1]) if it["do_flip"] else full).float())
+            batch["depth_gt"] = torch.stack(maps).unsqueeze(1).contiguous()
+
+    def _finish_batch(self, items):
+        """The device work of one batch, on the current stream."""
+        batch = {}
+        if self.opt is not None:
+            batch["date"] = [it["date"] for it in items]
+            if self._opt("need_path"):
+                batch["path"] = [self.filenames[it["index"]] for it in items]
+        self._colour_keys(items, batch)
+        if self._K is None:
+            self._K = synthetic.intrinsics(len(items), self.height, self.width, self.num_scales, self.device)
+        batch.update(self._K)
+        self._lidar_keys(items, batch)
+        return batch
+
+    def build_batch(self, epoch, indices):
+        """One batch, start to finish, on the current stream (no prefetch)."""
+        return self._finish_batch(self._start_host(epoch, indices))
+
+    def _issue(self, items):
+        """Device work of a batch on the builder's stream -> (batch, event)."""
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        with torch.cuda.stream(self._stream):
+            batch = self._finish_batch(items)
+            done = torch.cuda.Event()
+            done.record(self._stream)
+        return batch, done
+
+    @staticmethod
+    def _tensors(batch):
+        return [v for v in batch.values() if torch.is_tensor(v)]
+
+    def __iter__(self):
+        epoch = self._epoch
+        self._epoch += 1
+        order = self.epoch_order(epoch)
+        B = self.batch_size
+        chunks = [order[i * B:(i + 1) * B] for i in range(len(self))]
+        if not chunks:
+            return
+        if not (self.prefetch and self.device.type == "cuda"):
+            host = self._start_host(epoch, chunks[0])
+            for i in range(len(chunks)):
+                nxt = self._start_host(epoch, chunks[i + 1]) if i + 1 < len(chunks) else None    # files of the next batch meanwhile
+                yield self._finish_batch(host)
+                host = nxt
+            return
+        with torch.cuda.device(self.device):
+            host = [self._start_host(epoch, c) for c in chunks[:2]]                # file work runs up to two batches ahead
+            pending = self._issue(host.pop(0))
+            for i in range(len(chunks)):
+                if i + 2 < len(chunks):
+                    host.append(self._start_host(epoch, chunks[i + 2]))
+                batch, done = pending
+                pending = self._issue(host.pop(0)) if i + 1 < len(chunks) else None    # batch i + 1 goes out before batch i is consumed
+                cur = torch.cuda.current_stream()
+                cur.wait_event(done)
+                for t in self._tensors(batch):
+                    t.record_stream(cur)
+                yield batch

@@ -1834,3 +1834,217 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, betas=(0.9, 0.999), e
     call("fd_adam_step_dev", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(state), betas[0],
          betas[1], float(eps), float(grad_scale), stream())
     refresh_weight_layouts()
+
+
+# ------------------------------------------------------------------------------------ training images (uint8) ---
+# datasets/mono_dataset.py:85-104 on the device: Pillow's antialiased Lanczos resample, ColorJitter and ToTensor, bit for bit
+# (csrc/augment.hip; the arithmetic is restated in tests/augment_ref.py).  uint8 images are [N,H,W,3].
+_LANCZOS_TABLES = {}
+_LANCZOS_DEVICE_TABLES = {}
+JITTER_OPS = ("brightness", "contrast", "saturation", "hue")
+
+
+def lanczos_table(in_size, out_size):
+    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for the Lanczos filter, in float64 on the host: int32
+    [out_size, 2 + k] rows of (first tap, tap count, k coefficients) and k = 2 * ceil(3 * max(in, out) / out) + 1.  Cached."""
+    import math
+    import numpy as np
+    key = (int(in_size), int(out_size))
+    if key in _LANCZOS_TABLES:
+        return _LANCZOS_TABLES[key]
+    n_in, n_out = key
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError("lanczos_table: sizes must be positive, got %r" % (key,))
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 3.0 * filterscale
+    k = 2 * ((3 * max(n_in, n_out) + n_out - 1) // n_out) + 1
+    inv = 1.0 / filterscale
+    tab = np.zeros((n_out, 2 + k), np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        first = max(int(center - support + 0.5), 0)
+        count = min(int(center + support + 0.5), n_in) - first
+        ws, total = [], 0.0
+        for x in range(count):
+            t = (x + first - center + 0.5) * inv
+            if -3.0 <= t < 3.0:
+                a, b = t * math.pi, t / 3.0 * math.pi
+                w = (1.0 if t == 0.0 else math.sin(a) / a) * (1.0 if t == 0.0 else math.sin(b) / b)
+            else:
+                w = 0.0
+            ws.append(w)
+            total += w
+        tab[xx, 0], tab[xx, 1] = first, count
+        for x, w in enumerate(ws):
+            if total != 0.0:
+                w = w / total
+            tab[xx, 2 + x] = int(w * (1 << 22) - 0.5) if w < 0 else int(w * (1 << 22) + 0.5)
+    _LANCZOS_TABLES[key] = (tab, k)
+    return tab, k
+
+
+def _lanczos_table_on(in_size, out_size, device):
+    key = (int(in_size), int(out_size), str(device))
+    if key not in _LANCZOS_DEVICE_TABLES:
+        tab, k = lanczos_table(in_size, out_size)
+        _LANCZOS_DEVICE_TABLES[key] = (torch.from_numpy(tab).to(device), k)
+    return _LANCZOS_DEVICE_TABLES[key]
+
+
+def _need_u8_images(x, what):
+    _need_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
+        raise RuntimeError("%s: images must be uint8 [N,H,W,3], got %s %s" % (what, x.dtype, tuple(x.shape)))
+    return x.contiguous()
+
+
+def _mirror_table(mirror, n, device):
+    if mirror is None or mirror is False:
+        return None
+    if torch.is_tensor(mirror):
+        if mirror.dtype != torch.int32 or mirror.numel() != n:
+            raise RuntimeError("mirror: expected %d int32 flags" % n)
+        _need_cuda(mirror)
+        return mirror.contiguous()
+    flags = [bool(mirror)] * n if isinstance(mirror, bool) else [bool(m) for m in mirror]
+    if len(flags) != n:
+        raise RuntimeError("mirror: %d flags for %d images" % (len(flags), n))
+    return torch.tensor(flags, dtype=torch.int32).to(device) if any(flags) else None
+
+
+def resize_lanczos_u8(x, size, mirror=None, out=None):
+    """``Image.resize((size[1], size[0]), LANCZOS)`` of every image of ``x`` [N,H,W,3] uint8 -> [N,size[0],size[1],3].
+    ``mirror``: bool, N bools or an int32 device tensor - those frames are flipped left-right first (kitti_dataset.py:59-60)."""
+    x = _need_u8_images(x, "resize_lanczos_u8")
+    N, Hin, Win, _ = x.shape
+    Hout, Wout = int(size[0]), int(size[1])
+    xtab, kx = _lanczos_table_on(Win, Wout, x.device)
+    ytab, ky = _lanczos_table_on(Hin, Hout, x.device)
+    mir = _mirror_table(mirror, N, x.device)
+    if out is None:
+        out = torch.empty((N, Hout, Wout, 3), device=x.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, Hout, Wout, 3) or not out.is_contiguous() or out.device != x.device:
+        raise RuntimeError("resize_lanczos_u8: out must be a contiguous uint8 [%d,%d,%d,3] tensor on %s" % (N, Hout, Wout, x.device))
+    ws = torch.empty((max(query("fd_resize_lanczos_u8_ws_bytes", N, Hin, Win, Hout, Wout), 16),), device=x.device, dtype=torch.uint8)
+    call("fd_resize_lanczos_u8", ptr(x), ptr(out), N, Hin, Win, Hout, Wout, xtab.data_ptr(), kx, ytab.data_ptr(), ky,
+         mir.data_ptr() if mir is not None else None, ptr(ws), stream())
+    return out
+
+
+def u8_to_planes(x, out=None):
+    """``ToTensor``: [N,H,W,3] uint8 -> [N,3,H,W] float32 = v / 255.  ``out``: a batch slot, i.e. a float32 tensor [N,3,H,W] whose
+    images are dense (it may be a slice of a larger batch along dim 0, or strided along dim 0)."""
+    x = _need_u8_images(x, "u8_to_planes")
+    N, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((N, 3, H, W), device=x.device, dtype=torch.float32)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (N, 3, H, W) or out.device != x.device or
+          tuple(out.stride()[1:]) != (H * W, W, 1) or (N > 1 and out.stride(0) < 3 * H * W)):
+        raise RuntimeError("u8_to_planes: out must be float32 [%d,3,%d,%d] with dense images on %s" % (N, H, W, x.device))
+    call("fd_u8_to_planes", ptr(x), out.data_ptr(), N, H, W, out.stride(0) if N > 1 else 3 * H * W, stream())
+    return out
+
+
+def _jitter_ops(entry):
+    """(factors, order) -> (4 floats, list of distinct op ids); None -> no operation."""
+    if entry is None:
+        return (1.0, 1.0, 1.0, 0.0), []
+    factors, order = entry
+    factors, order = [float(f) for f in factors], [int(o) for o in order]
+    if len(factors) != 4 or any(o not in (0, 1, 2, 3) for o in order) or len(set(order)) != len(order):
+        raise ValueError("jitter: expected ((brightness, contrast, saturation, hue), order of distinct op ids 0..3), got %r" % (entry,))
+    return factors, order
+
+
+def _run_jitter(src, descs, dst_u8, dst_planes, max_pixels):
+    """descs: list of (src_off, u8_off, planes_off, plain_off, H, W, factors, order).  The hue offset is formed here, from the Python
+    double: trunc(h * 255) mod 256 (the kernel's float32 copy of h could land on the other side of an integer)."""
+    n = len(descs)
+    table = (_lib.JitterDesc * n)()
+    for d, (src_off, u8_off, planes_off, plain_off, H, W, factors, order) in zip(table, descs):
+        d.src_off, d.u8_off, d.planes_off, d.plain_off, d.H, d.W, d.n_ops = src_off, u8_off, planes_off, plain_off, H, W, len(order)
+        d.factor[:] = list(factors[:3]) + [0.0]
+        d.order[:] = list(order) + [0] * (4 - len(order))
+        d.hue_shift = int(factors[3] * 255.0) % 256
+    dev_table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(src.device)
+    ws = torch.empty((query("fd_color_jitter_u8_ws_bytes", n),), device=src.device, dtype=torch.uint8)
+    call("fd_color_jitter_u8", ptr(src), src.numel(), ptr(dst_u8), dst_u8.numel() if dst_u8 is not None else 0,
+         ptr(dst_planes), dst_planes.numel() if dst_planes is not None else 0, dev_table.data_ptr(), n, int(max_pixels), ptr(ws),
+         stream())
+    off = query("fd_color_jitter_u8_means_offset", n)
+    return ws[off:off + 4 * n].view(torch.int32)
+
+
+def color_jitter_u8(x, params, planes=False, return_means=False):
+    """torchvision ``ColorJitter`` on PIL images, for every image of ``x`` [N,H,W,3] uint8 in one launch sequence.  ``params``: one
+    entry per image, ``((brightness, contrast, saturation, hue), order)`` with ``order`` the op ids (0 brightness, 1 contrast,
+    2 saturation, 3 hue) in application order, or None to copy the image.  Returns uint8 [N,H,W,3], or with ``planes`` the float32
+    [N,3,H,W] ``ToTensor`` of it; with ``return_means`` also the int32 grey level each contrast operation blended towards (-1: none)."""
+    x = _need_u8_images(x, "color_jitter_u8")
+    N, H, W, _ = x.shape
+    if len(params) != N:
+        raise ValueError("color_jitter_u8: %d parameter sets for %d images" % (len(params), N))
+    out = torch.empty((N, 3, H, W), device=x.device, dtype=torch.float32) if planes else torch.empty_like(x)
+    per = 3 * H * W
+    descs = []
+    for i, entry in enumerate(params):
+        factors, order = _jitter_ops(entry)
+        descs.append((i * per, -1 if planes else i * per, i * per if planes else -1, -1, H, W, factors, order))
+    means = _run_jitter(x.view(-1), descs, None if planes else out.view(-1), out.view(-1) if planes else None, H * W)
+    return (out, means) if return_means else out
+
+
+def image_pyramid(frames_u8, height, width, num_scales, flip=None, jitter=None):
+    """The colour keys of a batch (mono_dataset.py:85-104): ``frames_u8`` [N,H,W,3] uint8 decoded frames ->
+    ``{("color", s): [N,3,height >> s,width >> s], ("color_aug", s): ...}`` float32.  Scale s is resampled from scale s - 1 (Lanczos,
+    chained as the reference does); ``flip``: per-frame left-right mirror of the source.  ``jitter``: None (``color_aug`` is
+    ``color``), or one entry per frame: None, a ``(factors, order)`` pair applied at every scale, or a list of ``num_scales`` such
+    pairs (a fresh draw per image).  Ten launches whatever N: two resample passes per scale, then the contrast statistics, their
+    final pass and one apply pass that reads every level once and writes every plane of ``color`` and ``color_aug`` once."""
+    frames_u8 = _need_u8_images(frames_u8, "image_pyramid")
+    N = frames_u8.shape[0]
+    dev = frames_u8.device
+    if jitter is not None and len(jitter) != N:
+        raise ValueError("image_pyramid: %d jitter entries for %d frames" % (len(jitter), N))
+    sizes = [(int(height) // 2 ** s, int(width) // 2 ** s) for s in range(int(num_scales))]
+    if not sizes or min(min(hw) for hw in sizes) < 1:
+        raise ValueError("image_pyramid: %dx%d has no %d-level pyramid" % (height, width, num_scales))
+    r16 = lambda v: (v + 15) // 16 * 16
+    u8_off, pl_off, u8_total, pl_total = [], [], 0, 0
+    variants = 2 if jitter is not None else 1
+    for h, w in sizes:
+        u8_off.append(u8_total)
+        pl_off.append(pl_total)
+        u8_total += r16(N * h * w * 3)
+        pl_total += r16(variants * N * h * w * 3)
+    arena = torch.empty((u8_total,), device=dev, dtype=torch.uint8)
+    planes = torch.empty((pl_total,), device=dev, dtype=torch.float32)
+    levels, cur = [], frames_u8
+    for s, (h, w) in enumerate(sizes):
+        lvl = arena[u8_off[s]:u8_off[s] + N * h * w * 3].view(N, h, w, 3)
+        resize_lanczos_u8(cur, (h, w), mirror=flip if s == 0 else None, out=lvl)
+        levels.append(lvl)
+        cur = lvl
+    descs, out = [], {}
+    for s, (h, w) in enumerate(sizes):
+        per = 3 * h * w
+        out[("color", s)] = planes[pl_off[s]:pl_off[s] + N * per].view(N, 3, h, w)
+        if jitter is not None:
+            out[("color_aug", s)] = planes[pl_off[s] + N * per:pl_off[s] + 2 * N * per].view(N, 3, h, w)
+        else:
+            out[("color_aug", s)] = out[("color", s)]
+        for n in range(N):
+            if jitter is None:
+                descs.append((u8_off[s] + n * per, -1, pl_off[s] + n * per, -1, h, w, (1.0, 1.0, 1.0, 0.0), []))
+                continue
+            entry = jitter[n]
+            if isinstance(entry, list):
+                if len(entry) != len(sizes):
+                    raise ValueError("image_pyramid: a per-image jitter list needs one entry per scale")
+                entry = entry[s]
+            factors, order = _jitter_ops(entry)
+            # one table entry per image: the level is read once, `color` is written from it as read and `color_aug` after the operations
+            descs.append((u8_off[s] + n * per, -1, pl_off[s] + (N + n) * per, pl_off[s] + n * per, h, w, factors, order))
+    _run_jitter(arena, descs, None, planes, sizes[0][0] * sizes[0][1])
+    return out

@@ -347,8 +347,8 @@ class Trainer:
         if val_loader is not None:
             self.val_loader = val_loader
         if getattr(self, "train_loader", None) is None:
-            raise RuntimeError("Trainer.train: no train_loader (pass one, or set self.train_loader; this package ships no KITTI "
-                               "DataLoader - any iterable of reference-schema batches works)")
+            raise RuntimeError("Trainer.train: no train_loader (pass one, or set self.train_loader: datasets.KITTIRAWBatches for "
+                               "KITTI raw, or any iterable of reference-schema batches)")
         self.epoch, self.step = 0, 0
         self.scheduler_epochs = 0              # a second train() on the same object starts its StepLR count afresh
         self.start_time = time.time()

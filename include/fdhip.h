@@ -35,8 +35,10 @@ extern "C" {
  *    limbs) and 9 / 10 (the same for a tap subset of a larger kernel); fd_refine_cfg accepts an empty crop window.  Nothing removed, no
  *    signature changed.
  * 5: additions only: graph-based depth correction (fd_gdc_prepare_ws_bytes, fd_gdc_prepare, fd_gdc_ws_bytes, fd_gdc_build,
- *    fd_gdc_cg_iters, fd_gdc_finish, struct fd_gdc_state).  Nothing removed, no signature changed. */
-#define FD_ABI_VERSION 5
+ *    fd_gdc_cg_iters, fd_gdc_finish, struct fd_gdc_state).  Nothing removed, no signature changed.
+ * 6: additions only: the image half of the KITTI loader (fd_resize_lanczos_u8_ws_bytes, fd_resize_lanczos_u8, fd_color_jitter_u8_ws_bytes,
+ *    fd_color_jitter_u8_means_offset, fd_color_jitter_u8, fd_u8_to_planes, struct fd_jitter_desc).  Nothing removed, no signature changed. */
+#define FD_ABI_VERSION 6
 
 int fd_abi_version(void);
 const char* fd_supported_arch(void); /* "gfx950" */
@@ -613,6 +615,49 @@ int fd_gdc_build(const float* pred, const double* gt, const int* pix, int N_PL, 
 int fd_gdc_cg_iters(void* ws, int N_PL, int N_L, int k, int n_iters, void* stream);
 int fd_gdc_finish(const float* pred, const double* gt, const int* pix, int N_PL, int N_L, int k, int H, int W, void* ws, float* out,
                   void* stream);
+
+/* ------------------------------------------------------------------ training images (uint8) ---- */
+
+/* The image half of a training item, datasets/mono_dataset.py:85-104: `Resize(..., ANTIALIAS)`, `ColorJitter` and `ToTensor` on
+ * PIL images.  uint8 images are [H][W][3] (what a decoder produces), outputs for the networks are float32 [3][H][W] planes.
+ * Pinned bit for bit to PIL 12 (tests/augment_ref.py restates the rules; torchvision's PIL branch is a thin mapping onto them).
+ *
+ * fd_resize_lanczos_u8: Pillow's 8-bit antialiased Lanczos resample, src [N][Hin][Win][3] -> dst [N][Hout][Wout][3]: a horizontal
+ *   pass into ws (uint8), then a vertical pass.  xtab / ytab (device, int32): per output column / row the record
+ *   (first tap, tap count, k coefficients), k = kx / ky = 2 * ceil(3 * max(in, out) / out) + 1; coefficient = int(w * 2^22 +- 0.5) of
+ *   the float64 weight, built by the caller on the host (functional.lanczos_table).  pixel = clip((2^21 + sum) >> 22).
+ *   mirror (device, int32 [N], may be NULL): frames with a non-zero entry are read flipped left-right (kitti_dataset.py:59-60 flips
+ *   before resizing).  src and ws 16-byte aligned; ws: fd_resize_lanczos_u8_ws_bytes bytes.
+ * fd_color_jitter_u8: n_images images described by a device table, one launch sequence for all of them whatever their sizes.
+ *   Image i is read at src + src_off, has order[0 .. n_ops) of the operations 0 brightness, 1 contrast, 2 saturation, 3 hue applied
+ *   with factor[op] (every intermediate is uint8, as between PIL calls; n_ops = 0 copies), and is written as uint8 to
+ *   dst_u8 + u8_off and / or as v / 255 planes to dst_planes + planes_off + c * H * W (an offset < 0: not written); plain_off
+ *   receives the planes of the image as read, so one pass over a level writes `color` and `color_aug`.  An operation may appear
+ *   at most once in order (an entry that repeats one is skipped).  Contrast
+ *   blends towards int(mean(L) + 0.5) of the image as it stands at that point: an exact integer sum, reduced by wave shuffle, LDS
+ *   and a fixed-order final pass.  An image whose extent leaves src_bytes / dst_bytes / planes_floats is skipped as a whole.
+ *   max_pixels: the largest H * W of the table (sizes the grid).  ws: fd_color_jitter_u8_ws_bytes(n_images) bytes, 8-byte
+ *   aligned; after the call int32 mean[n_images] (-1: no contrast) stands at byte fd_color_jitter_u8_means_offset(n_images) of it.
+ * fd_u8_to_planes: ToTensor.  src [N][H][W][3] -> dst + n * dst_image_stride + c * H * W, float32(v) / 255 correctly rounded. */
+typedef struct fd_jitter_desc {
+    long src_off;                 /* bytes */
+    long u8_off;                  /* bytes, < 0: no uint8 output */
+    long planes_off;              /* floats, < 0: no plane output of the jittered image */
+    long plain_off;               /* floats, < 0: none; planes of the image BEFORE the operations (`color` beside `color_aug`) */
+    int H, W;
+    float factor[4];              /* brightness, contrast, saturation as float32 (PIL casts them to C float itself); [3] unused */
+    int order[4];                 /* operation ids in application order, each at most once */
+    int n_ops;                    /* 0 .. 4 */
+    int hue_shift;                /* uint8 added to H: trunc(h * 255) mod 256 of the DOUBLE h, computed by the caller */
+} fd_jitter_desc;
+long fd_resize_lanczos_u8_ws_bytes(int N, int Hin, int Win, int Hout, int Wout);
+int fd_resize_lanczos_u8(const uint8_t* src, uint8_t* dst, int N, int Hin, int Win, int Hout, int Wout, const int* xtab, int kx,
+                         const int* ytab, int ky, const int* mirror, void* ws, void* stream);
+long fd_color_jitter_u8_ws_bytes(int n_images);
+long fd_color_jitter_u8_means_offset(int n_images);
+int fd_color_jitter_u8(const uint8_t* src, long src_bytes, uint8_t* dst_u8, long dst_bytes, float* dst_planes, long planes_floats,
+                       const fd_jitter_desc* desc, int n_images, long max_pixels, void* ws, void* stream);
+int fd_u8_to_planes(const uint8_t* src, float* dst, int N, int H, int W, long dst_image_stride, void* stream);
 
 #ifdef __cplusplus
 }
