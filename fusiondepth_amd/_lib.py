@@ -51,6 +51,18 @@ class JitterDesc(ctypes.Structure):
                 ("order", _I * 4), ("n_ops", _I), ("hue_shift", _I)]
 
 
+class SparsifyCfg(ctypes.Structure):
+    """Mirror of ``fd_sparsify_cfg``."""
+    _fields_ = [("S", _I), ("H", _I), ("W", _I), ("n_rows", _I), ("rows", _I * 64),
+                ("x_lo", _F), ("x_hi", _F), ("y_lo", _F), ("y_hi", _F), ("z_lo", _F), ("z_hi", _F),
+                ("random_sample", _I), ("reserved", _I), ("seed", ctypes.c_ulonglong)]
+
+
+class RasterDesc(ctypes.Structure):
+    """Mirror of ``fd_raster_desc``."""
+    _fields_ = [("P", _D * 12), ("im_h", _I), ("im_w", _I), ("flip", _I), ("reserved", _I)]
+
+
 class RelayoutJob(ctypes.Structure):
     """Mirror of ``fd_relayout_job``."""
     _fields_ = ([("w", ctypes.c_void_p), ("dst", ctypes.c_void_p)] +
@@ -169,6 +181,10 @@ SIGNATURES = {
     "fd_color_jitter_u8_means_offset": ("i", "l"),
     "fd_color_jitter_u8": ("plplpl" "pil" "pp", "i"),
     "fd_u8_to_planes": ("pp" "iii" "l" "p", "i"),
+    "fd_sparsify_ws_bytes": ("p", "l"),
+    "fd_sparsify_scans": ("pp" "l" "ppppppp" "p", "i"),
+    "fd_velo_rasterize_batch_ws_bytes": ("iii", "l"),
+    "fd_velo_rasterize_batch": ("pp" "ii" "p" "iiiiii" "ppp" "p", "i"),
 }
 
 _lock = threading.Lock()

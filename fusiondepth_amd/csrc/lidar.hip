@@ -227,3 +227,197 @@ extern "C" int fd_velo_rasterize(const float* points, int n_points, const double
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same rasterisation for S scans in one call: the kernels above with a scan index (blockIdx.y), the per-scan camera, image
+// size and flip flag read from a device table, and the scans either packed behind an offsets table or equal-capacity slabs whose
+// unused rows are (-1, 0, 0, 0) - dropped by the x >= 0 test like any point behind the car.  The arithmetic is spelled exactly as
+// above, so every scan's result is bit-identical to fd_velo_rasterize on it; the depth of a pixel's last point is recomputed
+// from the point instead of being kept in a per-point array.
+namespace {
+
+struct RasterBatch {
+    const float4* pts; const int* off; int n_max, S;
+    const fd_raster_desc* desc; int max_h, max_w; long npix_max;
+    int vel_depth, tgt_h, tgt_w, padded_h;
+    unsigned long long* zmin; unsigned* first; unsigned* last; double* depth;       // [S][npix_max] each
+};
+
+struct ScanGeom { int im_h, im_w, ypad, crop, flip; };
+
+// false: the scan does not fit the batch (see include/fdhip.h) and gets an all-zero output
+__device__ __forceinline__ bool scan_geom(const RasterBatch& a, int s, ScanGeom& g) {
+    g.im_h = a.desc[s].im_h; g.im_w = a.desc[s].im_w; g.flip = a.desc[s].flip;
+    if (g.im_h <= 0 || g.im_w <= 0 || g.im_h > a.max_h || g.im_w > a.max_w || g.im_w > a.tgt_w) return false;
+    g.ypad = a.tgt_h > g.im_h ? a.tgt_h - g.im_h : g.im_h - a.tgt_h;
+    g.crop = a.tgt_h < g.im_h ? 2 : 0;
+    return g.im_h + g.ypad - g.crop == a.padded_h;
+}
+
+// kitti_utils.py:65-74 for one point: pixel (u, v) before the bounds test and the depth it carries
+__device__ __forceinline__ void project_point(const double* __restrict__ P, float4 p, int vel_depth, double& u, double& v, double& depth) {
+    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+    const double c0 = fma(P[3], 1.0, fma(P[2], z, fma(P[1], y, P[0] * x)));
+    const double c1 = fma(P[7], 1.0, fma(P[6], z, fma(P[5], y, P[4] * x)));
+    const double c2 = fma(P[11], 1.0, fma(P[10], z, fma(P[9], y, P[8] * x)));
+    u = rint(c0 / c2) - 1.0; v = rint(c1 / c2) - 1.0;
+    depth = vel_depth ? x : c2;
+}
+
+__device__ __forceinline__ void scan_points(const RasterBatch& a, int s, long& base, int& n) {
+    if (a.off) {
+        base = a.off[s];
+        n = a.off[s + 1] - a.off[s];
+        n = n < 0 ? 0 : (n > a.n_max ? a.n_max : n);
+    } else {
+        base = (long)s * a.n_max;
+        n = a.n_max;
+    }
+}
+
+__global__ void k_rasterb_init(RasterBatch a) {
+    const long n = (long)a.S * a.npix_max;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        a.zmin[i] = ~0ull; a.first[i] = 0xFFFFFFFFu; a.last[i] = 0u;
+    }
+}
+
+__global__ void k_rasterb_points(RasterBatch a) {
+    const int s = blockIdx.y;
+    ScanGeom g;
+    if (!scan_geom(a, s, g)) return;
+    long base; int n;
+    scan_points(a, s, base, n);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = a.pts[base + i];
+    if (!((double)p.x >= 0.0)) return;
+    double u, v, depth;
+    project_point(a.desc[s].P, p, a.vel_depth, u, v, depth);
+    if (!(u >= 0.0 && v >= 0.0 && u < (double)g.im_w && v < (double)g.im_h)) return;
+    const long pix = (long)s * a.npix_max + (long)v * g.im_w + (long)u;
+    atomicMin(&a.zmin[pix], zkey(depth));
+    atomicMin(&a.first[pix], (unsigned)i);
+    atomicMax(&a.last[pix], (unsigned)i);
+}
+
+__global__ void k_rasterb_resolve(RasterBatch a) {
+    const int s = blockIdx.y;
+    ScanGeom g;
+    if (!scan_geom(a, s, g)) return;
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (long)g.im_h * g.im_w) return;
+    const long o = (long)s * a.npix_max;
+    const int im_h = g.im_h, im_w = g.im_w;
+    const int r = (int)(p / im_w), c = (int)(p - (long)r * im_w);
+    double d = 0.0;
+    if (a.first[o + p] != 0xFFFFFFFFu) {
+        d = zunkey(a.zmin[o + p]);
+        long q = -1;                                                       // the partner pixel of k_raster_resolve
+        if (im_w > 1 && c == 0 && r >= 1) q = (long)(r - 1) * im_w + (im_w - 1);
+        else if (im_w > 1 && c == im_w - 1 && r + 1 < im_h) q = (long)(r + 1) * im_w;
+        if (q >= 0 && a.first[o + q] != 0xFFFFFFFFu) {
+            if (a.first[o + p] < a.first[o + q]) {
+                const double dq = zunkey(a.zmin[o + q]);
+                d = dq < d ? dq : d;
+            } else {
+                long base; int n;
+                scan_points(a, s, base, n);
+                double u, v;
+                project_point(a.desc[s].P, a.pts[base + a.last[o + p]], a.vel_depth, u, v, d);
+            }
+        }
+        if (d < 0.0) d = 0.0;
+    }
+    a.depth[o + p] = d;
+}
+
+__global__ void k_rasterb_pad(RasterBatch a, double* __restrict__ out) {
+    const int s = blockIdx.y;
+    ScanGeom g;
+    const bool ok = scan_geom(a, s, g);
+    const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= (long)a.padded_h * a.tgt_w) return;
+    const int ty = (int)(o / a.tgt_w), tx = (int)(o - (long)ty * a.tgt_w);
+    double v = 0.0;
+    if (ok) {
+        const int sy = ty + g.crop - g.ypad, sx = tx - (a.tgt_w - g.im_w) / 2;
+        if (sy >= 0 && sy < g.im_h && sx >= 0 && sx < g.im_w) v = a.depth[(long)s * a.npix_max + (long)sy * g.im_w + sx];
+    }
+    const int ox = ok && g.flip ? a.tgt_w - 1 - tx : tx;
+    out[(long)s * a.padded_h * a.tgt_w + (long)ty * a.tgt_w + ox] = v;
+}
+
+__global__ void k_rasterb_pool(RasterBatch a, float* __restrict__ out, int out_h, int out_w) {
+    const int s = blockIdx.y;
+    ScanGeom g;
+    const bool ok = scan_geom(a, s, g);
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= out_h * out_w) return;
+    const int oy = o / out_w, ox = o - oy * out_w;
+    float res = 0.f;
+    if (ok) {
+        const int pad_left = (a.tgt_w - g.im_w) / 2;
+        const double* depth = a.depth + (long)s * a.npix_max;
+        double m = -1.0 / 0.0;
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ty = 2 * oy + dy, tx = 2 * ox + dx;
+                if (ty >= a.padded_h || tx >= a.tgt_w) continue;
+                const int sy = ty + g.crop - g.ypad, sx = tx - pad_left;
+                const double v = (sy >= 0 && sy < g.im_h && sx >= 0 && sx < g.im_w) ? depth[(long)sy * g.im_w + sx] : 0.0;
+                m = v > m ? v : m;
+            }
+        res = (float)m / 100.0f;
+    }
+    const int dx = ok && g.flip ? out_w - 1 - ox : ox;
+    out[(long)s * out_h * out_w + (long)oy * out_w + dx] = res;
+}
+
+}  // namespace
+
+extern "C" long fd_velo_rasterize_batch_ws_bytes(int S, int max_im_h, int max_im_w) {
+    if (S <= 0 || max_im_h <= 0 || max_im_w <= 0) return 0;
+    const size_t n = (size_t)S * max_im_h * max_im_w;
+    return (long)(2 * align256(n * 8) + 2 * align256(n * 4));
+}
+
+extern "C" int fd_velo_rasterize_batch(const float* points, const int* offsets, int n_max, int S, const fd_raster_desc* desc,
+                                       int max_im_h, int max_im_w, int vel_depth, int target_h, int target_w, int padded_h,
+                                       float* beam_out, double* depth_out, void* ws, void* stream) {
+    FD_REQUIRE((points || n_max == 0) && desc && (beam_out || depth_out) && ws && n_max >= 0 && S > 0 && S <= 65535 && max_im_h > 0 &&
+                   max_im_w > 0 && target_h > 0 && target_w > 0 && padded_h > 0,
+               "fd_velo_rasterize_batch: bad args");
+    FD_REQUIRE(((uintptr_t)points & 15) == 0, "fd_velo_rasterize_batch: points must be 16-byte aligned");
+    FD_REQUIRE(target_w >= max_im_w, "fd_velo_rasterize_batch: target width %d < image width %d (the reference pads, never crops, columns)",
+               target_w, max_im_w);
+    hipStream_t st = (hipStream_t)stream;
+    RasterBatch a;
+    a.pts = (const float4*)points; a.off = offsets; a.n_max = n_max; a.S = S; a.desc = desc; a.max_h = max_im_h; a.max_w = max_im_w;
+    a.npix_max = (long)max_im_h * max_im_w;
+    a.vel_depth = vel_depth; a.tgt_h = target_h; a.tgt_w = target_w; a.padded_h = padded_h;
+    const size_t n = (size_t)S * a.npix_max;
+    char* b = (char*)ws;
+    a.zmin = (unsigned long long*)b; b += align256(n * 8);
+    a.depth = (double*)b; b += align256(n * 8);
+    a.first = (unsigned*)b; b += align256(n * 4);
+    a.last = (unsigned*)b;
+    hipLaunchKernelGGL(k_rasterb_init, dim3(fd_cdiv((long)n, 256)), dim3(256), 0, st, a);
+    FD_LAUNCH_CHECK("fd_velo_rasterize_batch(init)");
+    if (n_max > 0) {
+        hipLaunchKernelGGL(k_rasterb_points, dim3(fd_cdiv(n_max, 256), S), dim3(256), 0, st, a);
+        FD_LAUNCH_CHECK("fd_velo_rasterize_batch(points)");
+    }
+    hipLaunchKernelGGL(k_rasterb_resolve, dim3(fd_cdiv(a.npix_max, 256), S), dim3(256), 0, st, a);
+    FD_LAUNCH_CHECK("fd_velo_rasterize_batch(resolve)");
+    if (depth_out) {
+        hipLaunchKernelGGL(k_rasterb_pad, dim3(fd_cdiv((long)padded_h * target_w, 256), S), dim3(256), 0, st, a, depth_out);
+        FD_LAUNCH_CHECK("fd_velo_rasterize_batch(pad)");
+    }
+    if (beam_out) {
+        const int out_h = (padded_h + 1) / 2, out_w = (target_w + 1) / 2;
+        hipLaunchKernelGGL(k_rasterb_pool, dim3(fd_cdiv((long)out_h * out_w, 256), S), dim3(256), 0, st, a, beam_out, out_h, out_w);
+        FD_LAUNCH_CHECK("fd_velo_rasterize_batch(pool)");
+    }
+    return 0;
+}

@@ -31,16 +31,29 @@ and scattered with the ROI scaled to match - identical at the reference's 192x64
 the reference's fixed-size map does not fit the network's input.  As in the reference, ``("2channel", f, 0)`` exists whenever
 ``need_2_channel`` is set; ``"4beam"`` and ``"2channel"`` only with ``need_4beam``.
 
+LiDAR source.  ``lidar_source="files"`` (the default) reads the ``{n}beam/`` / ``random{N}/`` scans an offline sparsifier wrote
+(the reference's ``sparsify/sparsify.py`` or ``python -m fusiondepth_amd.sparsify``).  ``lidar_source="raw"`` needs none of them: it reads
+``velodyne_points/data/*.bin`` and sparsifies on the device.  That path is batched from the start - whatever the batch size, the LiDAR
+keys of a batch cost ONE host-to-device copy (the worker threads read the files straight into one pinned staging buffer that also
+carries the offsets, the random keys and the cameras) and four library calls: ``fd_sparsify_scans``, ``fd_velo_rasterize_batch`` for
+the beam maps, ``fd_velo_rasterize_batch`` for ``depth_gt`` (frame 0's scan serves both, read and uploaded once) and
+``fd_scatter_2channel``.  Rows: ``line_spec``, default the reference's list for ``opt.nbeams``; ``opt.random_sample > 0`` samples
+instead, with the generator keyed by (``seed``, folder, frame index) - a frame's sparse scan is the same in every epoch, batch and
+worker order, and the same as the offline tool writes with ``--seed``.  The two sources give bit-identical batches.
+
 Not covered (each raises): the stereo frame ``"s"``, ``need_full_res_4beam`` (needs cv2), ``need_inf_gdc`` / ``clone_gdc``.
 """
 import concurrent.futures
+import ctypes
 import os
 
 import numpy as np
 import torch
 
+from . import _lib
 from . import functional as FD
 from . import kitti_utils
+from . import sparsify as SP
 from . import synthetic
 
 SIDE_MAP = {"2": 2, "3": 3, "l": 2, "r": 3}                  # kitti_dataset.py:42
@@ -53,6 +66,23 @@ def pil_loader(path):
     with open(path, "rb") as f:
         with Image.open(f) as img:
             return np.asarray(img.convert("RGB"))
+
+
+def _round16(n):
+    return (n + 15) // 16 * 16
+
+
+def _read_into(path, dst):
+    """Fill the uint8 array ``dst`` (a slice of the staging buffer) from the start of a file."""
+    with open(path, "rb") as f:
+        got = f.readinto(memoryview(dst))
+    if got != dst.size:
+        raise RuntimeError("KITTIRAWBatches: %s changed size while it was read (%d of %d bytes)" % (path, got, dst.size))
+
+
+def _upload(staging, device):
+    """The one host-to-device copy of a raw-mode batch's LiDAR data."""
+    return staging.to(device, non_blocking=True)
 
 
 def parse_line(line):
@@ -69,11 +99,13 @@ class KITTIRAWBatches:
     ``DataLoader``'s (``drop_last=True``).  ``seed`` seeds the epoch order and the per-item draws, ``workers`` sizes the decode pool
     (at most 16), ``draws`` = callable ``(epoch, index) -> dict`` that replaces ``item_draws`` (tests inject flags and jitter
     parameters through it), ``loader`` = callable ``path -> [H,W,3] uint8`` instead of the PIL decoder (pre-decoded frames),
-    ``prefetch`` = issue the next batch on a side stream before handing out the current one."""
+    ``prefetch`` = issue the next batch on a side stream before handing out the current one, ``lidar_source`` = ``"files"`` (sparse
+    scans written offline) or ``"raw"`` (sparsified here from ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default:
+    the reference's list for ``opt.nbeams``), ``sparsify_grid`` = (H, W) of its angular grid."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
                  batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
-                 prefetch=True):
+                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024)):
         self.data_path, self.filenames = data_path, list(filenames)
         self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
         self.frame_idxs = list(frame_idxs)
@@ -96,6 +128,17 @@ class KITTIRAWBatches:
         self.need_4beam = bool(self._opt("need_4beam"))
         self.need_2_channel = bool(self._opt("need_2_channel"))
         self.load_depth = self.check_depth()
+        if lidar_source not in ("files", "raw"):
+            raise ValueError("KITTIRAWBatches: lidar_source must be 'files' or 'raw', got %r" % (lidar_source,))
+        self.lidar_source = lidar_source
+        self.sparsify_grid = (int(sparsify_grid[0]), int(sparsify_grid[1]))
+        self.random_sample = max(int(self._opt("random_sample", -1)), 0)
+        if line_spec is None and not self.random_sample:
+            nbeams = int(self._opt("nbeams", 4))
+            if lidar_source == "raw" and nbeams not in FD.SPARSIFY_LINE_SPEC:
+                raise ValueError("KITTIRAWBatches: no default row list for nbeams = %d; pass line_spec" % nbeams)
+            line_spec = FD.SPARSIFY_LINE_SPEC.get(nbeams)
+        self.line_spec = None if line_spec is None else [int(r) for r in line_spec]
         self._epoch = 0
         self._pool = None
         self._stream = None
@@ -187,8 +230,55 @@ class KITTIRAWBatches:
                 item["beams"] = [self.get_beam_path(folder, frame_index + f) for f in frames]
             if self.load_depth:
                 item["velo"] = self.get_velo_path(folder, frame_index)
+            if self.lidar_source == "raw":                       # the raw scans of the frames whose beam maps are needed
+                item["frames"] = [frame_index + f for f in frames] if item["beams"] else []
+                item["beams"] = [self.get_velo_path(folder, i) for i in item["frames"]]
             items.append(item)
         return items
+
+    def _plan_staging(self, items):
+        """Raw mode: the layout of the batch's staging buffer.  Scans are frame-major like every other key; with ``depth_gt`` alone
+        (no beam keys) the scans are the items' own frames.  Frame 0's scan serves ``depth_gt`` too, so it appears once."""
+        per_item = len(items[0]["beams"])
+        if per_item:
+            scans = [(it, it["beams"][k], it["frames"][k]) for k in range(per_item) for it in items]
+        else:
+            scans = [(it, it["velo"], it["frame_index"]) for it in items if it["velo"]]
+        S = len(scans)
+        lengths = [os.path.getsize(path) // 16 for _, path, _ in scans]
+        plan = {"S": S, "lengths": lengths, "sparse": bool(per_item), "scans": scans}
+        at = 0
+        for name, nbytes in (("offsets", 4 * (S + 1)), ("keys", 8 * S), ("descs", ctypes.sizeof(_lib.RasterDesc) * S)):
+            plan[name] = (at, at + nbytes)
+            at = _round16(at + nbytes)
+        plan["points"] = (at, at + 16 * sum(lengths))
+        plan["bytes"] = max(plan["points"][1], 16)
+        return plan
+
+    def _start_raw(self, items, pool):
+        """Raw mode: one pinned staging buffer per batch, filled by the pool - the files are read straight into it."""
+        plan = self._plan_staging(items)
+        if not plan["S"]:
+            return None
+        staging = torch.empty((plan["bytes"],), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        ends = np.cumsum([0] + plan["lengths"])
+        if ends[-1] >= 2 ** 31:
+            raise RuntimeError("KITTIRAWBatches: %d points in one batch" % ends[-1])
+        host[plan["offsets"][0]:plan["offsets"][1]].view(np.int32)[:] = ends
+        host[plan["keys"][0]:plan["keys"][1]].view(np.uint64)[:] = np.array([SP.scan_key(it["folder"], frame) for it, _, frame in plan["scans"]],
+                                                                              dtype=np.uint64)
+        descs = []
+        for it, _, _ in plan["scans"]:
+            P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
+            descs.append((P, im_h, im_w, it["do_flip"]))
+        table = FD.raster_desc_table(descs)
+        host[plan["descs"][0]:plan["descs"][1]] = np.frombuffer(table, dtype=np.uint8)
+        base = plan["points"][0]
+        plan["futures"] = [pool.submit(_read_into, path, host[base + 16 * int(ends[k]):base + 16 * int(ends[k + 1])])
+                           for k, (_, path, _) in enumerate(plan["scans"])]
+        plan["staging"], plan["desc_list"] = staging, descs
+        return plan
 
     def _start_host(self, epoch, indices):
         """Submit the file work of a batch to the pool."""
@@ -196,8 +286,12 @@ class KITTIRAWBatches:
         pool = self._workers()
         for it in items:
             it["image_futures"] = [pool.submit(self.loader, p) for p in it["images"]]
+            if self.lidar_source == "raw":
+                continue
             it["beam_futures"] = [pool.submit(kitti_utils.load_velodyne_points, p) for p in it["beams"]]
             it["velo_future"] = pool.submit(kitti_utils.load_velodyne_points, it["velo"]) if it["velo"] else None
+        if self.lidar_source == "raw":
+            items[0]["raw_plan"] = self._start_raw(items, pool)
         return items
 
     def _projection(self, date, cam):
@@ -242,7 +336,43 @@ class KITTIRAWBatches:
                 for name in ("color", "color_aug"):
                     batch[(name, f, s)] = whole[(name, s)][fi * B:(fi + 1) * B]
 
+    def _lidar_keys_raw(self, items, batch):
+        """The LiDAR keys from raw scans: one upload and four library calls whatever the batch size (module docstring)."""
+        plan = items[0]["raw_plan"]
+        if plan is None:
+            return
+        for f in plan["futures"]:
+            f.result()
+        dev = _upload(plan["staging"], self.device)
+        S, B, descs = plan["S"], len(items), plan["desc_list"]
+        part = lambda name: dev[plan[name][0]:plan[name][1]]
+        offsets, keys, table = part("offsets").view(torch.int32), part("keys").view(torch.int64), part("descs")
+        points = part("points").view(torch.float32).view(-1, 4)
+        zero = 0
+        if plan["sparse"]:
+            H, W = self.sparsify_grid
+            slab, _ = FD.sparsify_scans(points, H, W, None if self.random_sample else self.line_spec, 1, self.random_sample, None,
+                                        self.seed, keys, offsets=offsets)
+            beams = FD.velo_rasterize_batch(slab, descs, (2 * self.height, 2 * self.width), desc_table=table).unsqueeze(1)
+            zero = self.frame_idxs.index(0) if self.need_2_channel else 0
+            if self.need_2_channel:
+                two = FD.scatter_2channel(beams, FD.scaled_roi(self.height, self.width))
+                for fi, f in enumerate(self.frame_idxs):
+                    batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
+            if self.need_4beam:
+                batch["4beam"] = beams[zero * B:(zero + 1) * B]
+                if self.need_2_channel:
+                    batch["2channel"] = two[zero * B:(zero + 1) * B]
+        if self.load_depth:                                      # frame 0's scans are B consecutive entries of the same tables
+            size = ctypes.sizeof(_lib.RasterDesc)
+            full = FD.velo_rasterize_batch(points, descs[zero * B:(zero + 1) * B], (375, 1242), return_full=True, beam=False,
+                                           offsets=offsets[zero * B:(zero + 1) * B + 1], n_max=max(plan["lengths"][zero * B:(zero + 1) * B]),
+                                           desc_table=table[zero * B * size:(zero + 1) * B * size])
+            batch["depth_gt"] = full.float().unsqueeze(1)
+
     def _lidar_keys(self, items, batch):
+        if self.lidar_source == "raw":
+            return self._lidar_keys_raw(items, batch)
         if self.need_4beam or self.need_2_channel:
             per_item = len(items[0]["beams"])
             beams = []

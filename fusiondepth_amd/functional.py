@@ -372,6 +372,154 @@ def scaled_roi(H, W):
     return (max(int(round(76 * H / 192)), 2), min(int(round(190 * H / 192)), H - 2), 2, W - 2)
 
 
+# sparsify/sparsify.py on the GPU ------------------------------------------------------------------
+SPARSIFY_BOX = (0.0, 120.0, -50.0, 50.0, -2.5, 1.5)          # sparsify.py:98-103: x, y, z half-open ranges
+SPARSIFY_LINE_SPEC = {1: (9,), 2: (9, 11), 3: (7, 9, 11), 4: (2, 7, 12, 16)}     # prepare_{n}beam_data_for_prediction.sh --line_spec
+
+
+def sparsify_rows(H=64, line_spec=None, slice=1):
+    """The rows ``pto_ang_map`` keeps, in output order: ``line_spec`` as given, else ``0::slice``."""
+    return [int(r) for r in line_spec] if line_spec is not None else list(range(0, int(H), int(slice)))
+
+
+def as_int64(v):
+    """The 64 bits of an integer as a signed value (how a uint64 key travels in an int64 tensor)."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def _device_table(values, dtype, device):
+    return torch.tensor(values, dtype=dtype).to(device)
+
+
+def sparsify_scans(points, H=64, W=1024, line_spec=None, slice=1, random_sample=0, uniforms=None, seed=0, keys=None, offsets=None,
+                   box=SPARSIFY_BOX, return_cells=False):
+    """``gen_sparse_points`` (sparsify/sparsify.py:32-136) for S raw Velodyne scans in one call (fd_sparsify_scans).
+    ``points``: a list of [n,4] float32 CUDA tensors, or one packed [sum n,4] tensor with ``offsets`` (int32 CUDA, [S+1]).
+    ``random_sample`` = N > 0 keeps about N * 1.8 of the points: with ``uniforms`` (a float64 CUDA [S, cap] tensor, or a list of 1-D
+    arrays, one draw per compacted point - ``np.random.uniform(0, 1, m)`` of the reference) or, without, with the library's
+    generator keyed by (``seed``, ``keys[s]``, slot); ``keys``: S integers or an int64 CUDA tensor (default 0 .. S-1).
+    Returns ``(slab, counts)``: slab [S, cap, 4] with cap = rows * W, scan s's points in ``slab[s, :counts[s]]`` in the reference's
+    order and ``(-1, 0, 0, 0)`` after them; counts int32 CUDA [S].  ``return_cells`` adds int32 [sum n]: row * W + column per point
+    (-1: filtered out).  numpy 2 semantics (the angle arithmetic after arcsin is float64)."""
+    if isinstance(points, (list, tuple)):
+        scans = [f32(p).reshape(-1, 4) for p in points]
+        if not scans:
+            raise ValueError("sparsify_scans: no scans")
+        _need_cuda(*scans)
+        ends, total = [0], 0
+        for p in scans:
+            total += p.shape[0]
+            ends.append(total)
+        packed = torch.cat(scans) if len(scans) > 1 else scans[0]
+        offsets = _device_table(ends, torch.int32, packed.device)
+    else:
+        packed = f32(points).reshape(-1, 4)
+        _need_cuda(packed)
+        if offsets is None or offsets.dtype != torch.int32 or not offsets.is_cuda or not offsets.is_contiguous():
+            raise ValueError("sparsify_scans: a packed tensor needs offsets: a contiguous int32 CUDA tensor [S + 1]")
+    if not packed.is_contiguous():
+        packed = packed.contiguous()
+    S = offsets.numel() - 1
+    rows = sparsify_rows(H, line_spec, slice)
+    if not 1 <= len(rows) <= 64:
+        raise ValueError("sparsify_scans: %d rows selected; the kernel takes 1 .. 64" % len(rows))
+    cfg = _lib.SparsifyCfg()
+    cfg.S, cfg.H, cfg.W, cfg.n_rows = S, int(H), int(W), len(rows)
+    for k, r in enumerate(rows):
+        cfg.rows[k] = r
+    cfg.x_lo, cfg.x_hi, cfg.y_lo, cfg.y_hi, cfg.z_lo, cfg.z_hi = [float(v) for v in box]
+    cfg.random_sample, cfg.seed = int(random_sample), int(seed) & 0xFFFFFFFFFFFFFFFF
+    cap = len(rows) * int(W)
+    dev = packed.device
+    if cfg.random_sample > 0:
+        if uniforms is not None:
+            if not torch.is_tensor(uniforms):
+                import numpy as np
+                host = np.ones((S, cap), dtype=np.float64)
+                for s_, u in enumerate(uniforms):
+                    u = np.asarray(u, dtype=np.float64).reshape(-1)
+                    host[s_, :u.size] = u
+                uniforms = torch.from_numpy(host).to(dev)
+            if uniforms.dtype != torch.float64 or tuple(uniforms.shape) != (S, cap) or not uniforms.is_cuda or not uniforms.is_contiguous():
+                raise ValueError("sparsify_scans: uniforms must be a contiguous float64 CUDA tensor [%d, %d]" % (S, cap))
+        elif keys is None:
+            keys = list(range(S))
+        if keys is not None and not torch.is_tensor(keys):
+            keys = _device_table([as_int64(k) for k in keys], torch.int64, dev)
+        if keys is not None and (keys.dtype != torch.int64 or keys.numel() != S or not keys.is_cuda or not keys.is_contiguous()):
+            raise ValueError("sparsify_scans: keys must be %d integers or a contiguous int64 CUDA tensor" % S)
+    else:
+        uniforms = keys = None
+    nbytes = query("fd_sparsify_ws_bytes", ctypes.byref(cfg))
+    if nbytes <= 0:
+        raise RuntimeError("fd_sparsify_ws_bytes: %s" % _lib.last_error())
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    slab = torch.empty((S, cap, 4), device=dev, dtype=torch.float32)
+    counts = torch.empty((S,), device=dev, dtype=torch.int32)
+    cells = torch.empty((packed.shape[0],), device=dev, dtype=torch.int32) if return_cells else None
+    call("fd_sparsify_scans", packed.data_ptr() if packed.shape[0] else None, offsets.data_ptr(), packed.shape[0], ctypes.byref(cfg),
+         uniforms.data_ptr() if uniforms is not None else None, keys.data_ptr() if keys is not None else None, slab.data_ptr(),
+         counts.data_ptr(), cells.data_ptr() if cells is not None and cells.numel() else None, ws.data_ptr(), stream())
+    return (slab, counts, cells) if return_cells else (slab, counts)
+
+
+def raster_desc_table(descs):
+    """Host image of the ``fd_raster_desc`` table for ``descs`` = [(P_velo2im 3x4, im_h, im_w, flip)]: a ctypes array."""
+    import numpy as np
+    table = (_lib.RasterDesc * len(descs))()
+    for d, (P, im_h, im_w, flip) in zip(table, descs):
+        P = np.asarray(P.cpu() if torch.is_tensor(P) else P, dtype=np.float64).reshape(12)
+        for k in range(12):
+            d.P[k] = P[k]
+        d.im_h, d.im_w, d.flip = int(im_h), int(im_w), 1 if flip else 0
+    return table
+
+
+def velo_rasterize_batch(points, descs, shape=(384, 1280), return_full=False, vel_depth=False, beam=True, offsets=None, n_max=None,
+                         desc_table=None):
+    """``velo_rasterize`` for S scans in one call (fd_velo_rasterize_batch), each already flipped left-right where asked.
+    ``points``: a slab [S, cap, 4] (rows with x < 0, such as ``sparsify_scans``' padding, are dropped), or a packed [N, 4] tensor
+    with ``offsets`` (int32 CUDA [S+1]) and ``n_max`` >= the longest scan.  ``descs``: [(P_velo2im, im_h, im_w, flip)] per scan (sizes
+    may differ; all must pad to the same number of rows for ``shape``); ``desc_table``: the same table already on the device (a uint8
+    CUDA tensor holding ``raster_desc_table(descs)``), else it is uploaded here.  Returns [S, h, w] float32 and / or, with
+    ``return_full``, [S, H, W] float64."""
+    points = f32(points)
+    _need_cuda(points)
+    if not points.is_contiguous():
+        points = points.contiguous()
+    S = len(descs)
+    if offsets is None:
+        if points.dim() != 3 or points.shape[0] != S or points.shape[2] != 4:
+            raise ValueError("velo_rasterize_batch: expected a slab [%d, cap, 4], got %s" % (S, tuple(points.shape)))
+        n_max = points.shape[1]
+    else:
+        if offsets.dtype != torch.int32 or not offsets.is_cuda or offsets.numel() != S + 1 or not offsets.is_contiguous() or n_max is None:
+            raise ValueError("velo_rasterize_batch: packed points need int32 CUDA offsets [S + 1] and n_max")
+    th, tw = int(shape[0]), int(shape[1])
+    rows = {padded_rows(int(d[1]), th) for d in descs}
+    if len(rows) != 1:
+        raise ValueError("velo_rasterize_batch: the scans pad to different heights %s for target %d rows" % (sorted(rows), th))
+    ph = rows.pop()
+    max_h, max_w = max(int(d[1]) for d in descs), max(int(d[2]) for d in descs)
+    if desc_table is None:
+        table = raster_desc_table(descs)
+        desc_table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(points.device)
+    elif desc_table.dtype != torch.uint8 or not desc_table.is_cuda or desc_table.numel() != S * ctypes.sizeof(_lib.RasterDesc):
+        raise ValueError("velo_rasterize_batch: desc_table must be a uint8 CUDA tensor of %d bytes" % (S * ctypes.sizeof(_lib.RasterDesc)))
+    out = torch.empty((S, (ph + 1) // 2, (tw + 1) // 2), device=points.device, dtype=torch.float32) if beam else None
+    full = torch.empty((S, ph, tw), device=points.device, dtype=torch.float64) if return_full else None
+    if out is None and full is None:
+        raise ValueError("velo_rasterize_batch: nothing to return")
+    ws = torch.empty((query("fd_velo_rasterize_batch_ws_bytes", S, max_h, max_w),), device=points.device, dtype=torch.uint8)
+    call("fd_velo_rasterize_batch", points.data_ptr() if points.numel() else None, offsets.data_ptr() if offsets is not None else None,
+         int(n_max), S, desc_table.data_ptr(), max_h, max_w, 1 if vel_depth else 0, th, tw, ph,
+         out.data_ptr() if out is not None else None, full.data_ptr() if full is not None else None, ws.data_ptr(), stream())
+    if out is not None and full is not None:
+        return out, full
+    return out if out is not None else full
+
+
 # ------------------------------------------------------------------------------------ fused loss --
 class PhotoOptions:
     """The option subset the fused loss reads (options.py:64-71,111-125,242-330)."""

@@ -659,6 +659,63 @@ int fd_color_jitter_u8(const uint8_t* src, long src_bytes, uint8_t* dst_u8, long
                        const fd_jitter_desc* desc, int n_images, long max_pixels, void* ws, void* stream);
 int fd_u8_to_planes(const uint8_t* src, float* dst, int N, int H, int W, long dst_image_stride, void* stream);
 
+/* ------------------------------------------------------------------ raw Velodyne scans -> sparse LiDAR ----
+ * sparsify/sparsify.py:32-136 (gen_sparse_points + pto_ang_map), batched: S scans in one call, a constant number of launches
+ * whatever S is.  A scan is [n][4] float32 (x, y, z, intensity); the scans are concatenated in `points` and `offsets` (device,
+ * int32 [S + 1], offsets[0] = 0, offsets[S] = total_points) says where each starts.
+ *   filter   x_lo <= x < x_hi, y_lo <= y < y_hi, z_lo <= z < z_hi (the reference: [0,120) x [-50,50) x [-2.5,1.5)).
+ *   cell     d = sqrt(x*x + y*y + z*z), r = sqrt(x*x + y*y) in float32, summed left to right, no fused multiply-add; an exact 0
+ *            becomes float32(1e-6); asin(y / r) and asin(z / d) as float32; from there float64, as numpy 2 promotes the
+ *            reference's expression: column = int((radians(45) - asin(y/r)) / radians(90 / W)), row = int((radians(2) -
+ *            asin(z/d)) / radians(0.4 * 64 / H)), truncated towards zero and clamped to [0, W-1] / [0, H-1].  asin is the one
+ *            step numpy does not round correctly; here it is evaluated in double on the float32 quotient and rounded once.
+ *   winner   the LAST point of a cell in scan order (the reference's fancy-index assignment) = the highest index: an integer
+ *            atomic max, order independent.
+ *   output   the winners of the occupied cells of rows[0 .. n_rows) (in the order given; no row twice), columns ascending, as
+ *            their original 16 bytes: slab [S][cap][4] float32 with cap = n_rows * W, kept points first, the remainder filled
+ *            with (-1, 0, 0, 0) - generate_depth_map drops x < 0 first, so a padded slab rasterises like the compacted scan -
+ *            and counts (device, int32 [S]).  Nothing is read back.
+ *   random_sample = N > 0 (sparsify.py:15-29,81-87): of those points, keep the ones with a non-zero float64 norm of (x,y,z,i)
+ *            and u < N * 1.8 / n_keep, one u per compacted point in output order, n_keep = the number with a non-zero norm.
+ *            u comes from `uniforms` (device, float64 [S][cap]: reproduces np.random.uniform draws injected by the caller) or,
+ *            when that is NULL, from the library's counter-based generator keyed by (seed, keys[s], output slot): a scan's
+ *            selection depends on nothing else.  keys: device, uint64 [S], needed only then.
+ *   cells    optional (device, int32 [total_points]): row * W + column of every point that passed the filter, -1 otherwise.
+ *   ws: fd_sparsify_ws_bytes(cfg) bytes, 16-byte aligned.  Run-to-run identical: integer atomics and fixed-order sums only. */
+#define FD_SPARSIFY_MAX_ROWS 64
+typedef struct fd_sparsify_cfg {
+    int S;                        /* scans */
+    int H, W;                     /* angular grid: 1 <= H <= 1024 rows, W columns */
+    int n_rows;                   /* 1 .. FD_SPARSIFY_MAX_ROWS */
+    int rows[FD_SPARSIFY_MAX_ROWS];
+    float x_lo, x_hi, y_lo, y_hi, z_lo, z_hi;
+    int random_sample;            /* N; 0: off */
+    int reserved;
+    unsigned long long seed;      /* the library's own generator (uniforms == NULL) */
+} fd_sparsify_cfg;
+long fd_sparsify_ws_bytes(const fd_sparsify_cfg* cfg);
+int fd_sparsify_scans(const float* points, const int* offsets, long total_points, const fd_sparsify_cfg* cfg,
+                      const double* uniforms, const unsigned long long* keys, float* slab, int* counts, int* cells, void* ws,
+                      void* stream);
+
+/* fd_velo_rasterize for S scans in one call (four launches whatever S is).  Scan s is points[offsets[s] .. offsets[s + 1]) when
+ * `offsets` (device, int32 [S + 1]) is given, else points[s * n_max .. (s + 1) * n_max) - a padded slab of fd_sparsify_scans;
+ * n_max bounds every scan's length.  desc (device, [S]): the scan's P_velo2im, image size and flip flag; max_im_h / max_im_w
+ * bound the image sizes (they size ws).  target_h / target_w and vel_depth are common.  Every scan must pad to the same
+ * padded_h rows (im_h + |target_h - im_h|, minus 2 when target_h < im_h) and have im_w <= target_w: one that does not, or that
+ * leaves max_im_h / max_im_w, gets an all-zero output.  beam_out [S][(padded_h + 1) / 2][(target_w + 1) / 2] float32 and / or
+ * depth_out [S][padded_h][target_w] float64, each scan bit-identical to fd_velo_rasterize on it, mirrored left-right where
+ * desc[s].flip is set.  ws: fd_velo_rasterize_batch_ws_bytes(S, max_im_h, max_im_w) bytes. */
+typedef struct fd_raster_desc {
+    double P[12];                 /* P_velo2im, row-major 3x4 */
+    int im_h, im_w;
+    int flip, reserved;
+} fd_raster_desc;
+long fd_velo_rasterize_batch_ws_bytes(int S, int max_im_h, int max_im_w);
+int fd_velo_rasterize_batch(const float* points, const int* offsets, int n_max, int S, const fd_raster_desc* desc, int max_im_h,
+                            int max_im_w, int vel_depth, int target_h, int target_w, int padded_h, float* beam_out,
+                            double* depth_out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,16 @@ runs, each GPU step as a child process under its own ``timeout -k 10`` and chain
   4. ``trainer``  Trainer images/s fed by the builder (pre-decoded frames) beside the same trainer fed make_scene_batch batches,
                   alternating windows; and the condition: (1) <= 10 % of the synthetic-fed step time.
 
+``--step raw [--out profiles/sparsify_time.log]`` measures the raw-scan LiDAR path (``lidar_source="raw"``, fd_sparsify_scans +
+fd_velo_rasterize_batch) the same way, as a run of its own:
+
+  5. ``sparsify``     device time per batch (36 scans of about 128 k points) of the new kernels against their compulsory traffic at
+                      8 TB/s, and the upload time of the batch's pinned staging buffer.
+  6. ``raw_builder``  items/s of KITTIRAWBatches in raw mode beside file mode (pre-decoded frames, the same tree, alternating).
+  7. ``raw_trainer``  Trainer images/s fed by raw mode, by file mode and by make_scene_batch batches, alternating windows.
+  8. ``offline``      scans/s of ``python -m fusiondepth_amd.sparsify`` beside the numpy restatement (tests/sparsify_ref.py) on 16
+                      worker processes.
+
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
 import argparse
@@ -314,6 +324,262 @@ def step_trainer(args):
                 % (args.colour_ms * per_step / BATCH, per_step, 100 * share, 1e3 * syn, "within" if share <= 0.10 else "ABOVE"))
 
 
+# ---------------------------------------------------------------------------------------------------- 5-8. raw Velodyne scans
+PEAK_BPS = 8.0e12
+LINE_SPEC = [2, 7, 12, 16]
+
+
+def _ref():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sparsify_ref
+    return sparsify_ref
+
+
+def write_raw_tree(root, n_frames):
+    """write_tree plus 64-ring raw scans (about 128 k points, 2 MB each); ``4beam/`` is then rewritten from them by the offline tool, so
+    that file mode and raw mode build the same batches."""
+    from fusiondepth_amd import sparsify as SP
+    SR = _ref()
+    lines, _ = write_tree(root, n_frames, (".png",))
+    folder = lines[0].split()[0]
+    os.makedirs(os.path.join(root, folder, "velodyne_points/data"), exist_ok=True)
+    for i in range(n_frames):
+        SR.synthetic_scan(500 + i).tofile(os.path.join(root, folder, "velodyne_points/data/%010d.bin" % i))
+    split = os.path.join(root, "scans.txt")
+    with open(split, "w") as f:
+        f.write("".join("%s %d l\n" % (folder, i) for i in range(n_frames)))
+    SP.main(["--W", "1024", "--H", "64", "--line_spec"] + [str(r) for r in LINE_SPEC] + ["--ptc_path", root + "/", "--output_path", root + "/",
+                                                                                        "--split_file", split])
+    return lines, split
+
+
+def step_sparsify(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import functional as FD
+    SR = _ref()
+    S = BATCH * FRAMES
+    scans = [SR.synthetic_scan(700 + i % 6) for i in range(S)]
+    ends = np.cumsum([0] + [len(p) for p in scans])
+    packed = torch.from_numpy(np.concatenate(scans)).cuda()
+    offsets = torch.tensor(ends, dtype=torch.int32).cuda()
+    K = np.array([[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]])
+    V = np.array([[7.533745e-03, -9.999714e-01, -6.166020e-04, -4.069766e-03], [1.480249e-02, 7.280733e-04, -9.998902e-01, -7.631618e-02],
+                  [9.998621e-01, 7.523790e-03, 1.480755e-02, -2.717806e-01], [0.0, 0.0, 0.0, 1.0]])
+    descs = [(K @ V, H0, W0, bool(i % 2)) for i in range(S)]
+    table = torch.frombuffer(bytearray(bytes(FD.raster_desc_table(descs))), dtype=torch.uint8).cuda()
+    staging = torch.empty((packed.numel() * 4,), dtype=torch.uint8, pin_memory=True)
+    cap = len(LINE_SPEC) * 1024
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times.append(a.elapsed_time(b))
+        return float(np.median(times)), min(times), max(times)
+
+    keep = {}
+
+    def sparsify():
+        keep["slab"] = FD.sparsify_scans(packed, 64, 1024, LINE_SPEC, offsets=offsets)[0]
+
+    def random100():
+        FD.sparsify_scans(packed, 64, 1024, random_sample=100, keys=list(range(S)), offsets=offsets)
+
+    def beams():
+        FD.velo_rasterize_batch(keep["slab"], descs, (2 * HEIGHT, 2 * WIDTH), desc_table=table)
+
+    def depth_gt():
+        FD.velo_rasterize_batch(packed, descs[:BATCH], (375, 1242), return_full=True, beam=False, offsets=offsets[:BATCH + 1],
+                                n_max=max(len(p) for p in scans[:BATCH]), desc_table=table[:BATCH * 112])
+
+    say("[5] raw-scan LiDAR path, batch %d: %d scans, %d points (%.1f MB), device events, median of %d (min, max)"
+        % (BATCH, S, ends[-1], 16 * ends[-1] / 1e6, args.iters))
+    comp = 16 * ends[-1] + 16 * S * cap
+    ms = timed(sparsify)
+    say("    fd_sparsify_scans, rows %s (4 launches + 1 memset): %.3f ms (%.3f, %.3f); compulsory traffic (points read once, slab written once) "
+        "%.1f MB = %.1f us at 8 TB/s -> %.1fx the bound, %.2f TB/s" % (LINE_SPEC, ms[0], ms[1], ms[2], comp / 1e6, 1e6 * comp / PEAK_BPS,
+                                                                       ms[0] * 1e-3 / (comp / PEAK_BPS), comp / (ms[0] * 1e-3) / 1e12))
+    comp_r = 16 * ends[-1] + 16 * S * 64 * 1024
+    ms = timed(random100)
+    say("    fd_sparsify_scans, random 100 over all 64 rows (7 launches + 1 memset; the table upload of the keys included): %.3f ms (%.3f, %.3f); "
+        "compulsory %.1f MB = %.1f us -> %.1fx" % (ms[0], ms[1], ms[2], comp_r / 1e6, 1e6 * comp_r / PEAK_BPS, ms[0] * 1e-3 / (comp_r / PEAK_BPS)))
+    ms = timed(beams)
+    say("    fd_velo_rasterize_batch, %d slabs of %d rows -> beam maps %dx%d (4 launches): %.3f ms (%.3f, %.3f)"
+        % (S, cap, WIDTH, HEIGHT, ms[0], ms[1], ms[2]))
+    ms = timed(depth_gt)
+    say("    fd_velo_rasterize_batch, %d raw scans -> depth_gt 1242x375 float64 (4 launches): %.3f ms (%.3f, %.3f)" % (BATCH, ms[0], ms[1], ms[2]))
+    ms = timed(lambda: staging.to("cuda", non_blocking=True))
+    say("    upload of the batch's pinned staging buffer (%.1f MB, one copy): %.3f ms (%.3f, %.3f) = %.1f GB/s; the 4-beam files of a batch are "
+        "%.0f KB" % (staging.numel() / 1e6, ms[0], ms[1], ms[2], staging.numel() / (ms[0] * 1e-3) / 1e9, S * 2000 * 16 / 1e3))
+
+
+def _raw_pair(root, lines, opt, batch_size):
+    from fusiondepth_amd.datasets import KITTIRAWBatches
+    load = _cached_loader()
+    mk = lambda source: KITTIRAWBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".png", opt=opt,
+                                        batch_size=batch_size, shuffle=True, seed=1, workers=WORKERS, loader=load, lidar_source=source)
+    return mk("files"), mk("raw")
+
+
+def step_raw_builder(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    with tempfile.TemporaryDirectory() as root:
+        lines, _ = write_raw_tree(root, 50)
+        files, raw = _raw_pair(root, lines, _opt(BATCH), BATCH)
+
+        def epochs(b, n):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            k = 0
+            for _ in range(n):
+                for batch in b:
+                    k += batch[("color", 0, 0)].shape[0]
+            torch.cuda.synchronize()
+            return k / (time.perf_counter() - t)
+
+        for b in (files, raw):
+            epochs(b, 1)                                              # warm-up: the frame cache, the page cache, code objects
+        res = {"files": [], "raw": []}
+        for _ in range(args.windows):
+            res["files"].append(epochs(files, 2))
+            res["raw"].append(epochs(raw, 2))
+        files.close()
+        raw.close()
+        say("[6] KITTIRAWBatches, batch %d, pre-decoded frames, 4beam + 2channel + depth_gt keys, %d alternating windows of 2 epochs (%d items each):"
+            % (BATCH, args.windows, len(lines) // BATCH * BATCH))
+        for name, what in (("files", "file mode (4beam/*.bin + the raw scan for depth_gt)"), ("raw", "raw mode (velodyne_points only)")):
+            say("    %-55s %7.1f items/s (windows %s)" % (what + ":", float(np.median(res[name])), " ".join("%.1f" % v for v in res[name])))
+
+
+def step_raw_trainer(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.trainer import Trainer
+    torch.manual_seed(1)
+    with tempfile.TemporaryDirectory() as root:
+        lines, _ = write_raw_tree(root, 50)
+        opt = _opt(BATCH)
+        tr = Trainer(opt, verbose=False)
+        per_step = tr.batch_size * tr.accumulate_step
+        files, raw = _raw_pair(root, lines, opt, tr.batch_size)
+
+        def endless(b):
+            while True:
+                for batch in b:
+                    batch.pop("depth_gt", None)                        # as for the synthetic batches: the step itself stays the same
+                    yield batch
+        feeds = {"files": endless(files), "raw": endless(raw)}
+        pool = []
+        for i in range(8):
+            mbs = [synthetic.make_scene_batch(tr.batch_size, HEIGHT, WIDTH, seed=1234 + 17 * i + j, clutter=0.5) for j in range(tr.accumulate_step)]
+            for mb in mbs:
+                mb.pop("depth_gt", None)
+                for f in (-1, 1):
+                    mb.pop(("T_gt", f), None)
+            pool.append(mbs)
+        k = [0]
+
+        def step_syn():
+            k[0] += 1
+            tr.train_step(pool[k[0] % len(pool)])
+
+        steps = {"synthetic": step_syn, "files": lambda: tr.train_step([next(feeds["files"]) for _ in range(tr.accumulate_step)]),
+                 "raw": lambda: tr.train_step([next(feeds["raw"]) for _ in range(tr.accumulate_step)])}
+
+        def window(fn, n):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n
+
+        for _ in range(4):
+            for fn in steps.values():
+                fn()
+        res = {name: [] for name in steps}
+        for _ in range(args.windows):
+            for name, fn in steps.items():
+                res[name].append(window(fn, args.steps))
+        files.close()
+        raw.close()
+        say("[7] Trainer (ResNet-18, %dx%d, --batch_size %d = %d images / step), %d alternating windows of %d steps; the builders also make "
+            "depth_gt (dropped before the step):" % (WIDTH, HEIGHT, BATCH, per_step, args.windows, args.steps))
+        for name, what in (("synthetic", "fed make_scene_batch batches"), ("files", "fed by KITTIRAWBatches, file mode (pre-decoded)"),
+                           ("raw", "fed by KITTIRAWBatches, raw mode (pre-decoded)")):
+            v = float(np.median(res[name]))
+            say("    %-50s %.1f images/s (%.2f ms / step; windows %s)" % (what + ":", per_step / v, 1e3 * v, " ".join("%.2f" % (1e3 * w) for w in res[name])))
+
+
+def step_offline_worker(args):
+    SR = _ref()
+    t = time.perf_counter()
+    n = 0
+    for line in open(args.split_file).read().split("\n")[args.worker::WORKERS]:
+        if not line.strip():
+            continue
+        folder, frame = line.split()[0], int(line.split()[1])
+        scan = np.fromfile(os.path.join(args.root, folder, "velodyne_points/data/%010d.bin" % frame), dtype=np.float32).reshape(-1, 4)
+        out = scan[SR.sparsify_indices(scan, W=1024, line_spec=LINE_SPEC)]
+        os.makedirs(os.path.join(args.root, folder, "4beam_numpy"), exist_ok=True)
+        out.tofile(os.path.join(args.root, folder, "4beam_numpy/%010d.bin" % frame))
+        n += 1
+    say(json.dumps({"scans": n, "seconds": time.perf_counter() - t}))
+
+
+def step_offline(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import sparsify as SP
+    n = 192
+    with tempfile.TemporaryDirectory() as root:
+        lines, split = write_raw_tree(root, n)                       # runs the tool once: warm-up (code objects, page cache)
+        argv = ["--W", "1024", "--H", "64", "--line_spec"] + [str(r) for r in LINE_SPEC] + ["--ptc_path", root + "/", "--output_path", root + "/",
+                                                                                           "--split_file", split]
+        gpu, cpu = [], []
+        for _ in range(args.windows):
+            t = time.perf_counter()
+            SP.run(SP.parse_args(argv))
+            torch.cuda.synchronize()
+            gpu.append(n / (time.perf_counter() - t))
+            t = time.perf_counter()
+            procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--step", "offline_worker", "--root", root, "--split_file", split,
+                                       "--worker", str(w)], stdout=subprocess.PIPE, text=True) for w in range(WORKERS)]
+            outs = [json.loads(p.communicate()[0].strip().splitlines()[-1]) for p in procs]
+            wall = time.perf_counter() - t
+            if any(p.returncode for p in procs):
+                sys.exit("a numpy worker failed")
+            cpu.append((n / max(o["seconds"] for o in outs), n / wall))
+        say("[8] offline tool, %d scans of about 128 k points (2 MB files, page cache warm), rows %s, %d alternating runs:" % (n, LINE_SPEC, args.windows))
+        say("    python -m fusiondepth_amd.sparsify (16 file threads, 32 scans per call): %.0f scans/s (runs %s)"
+            % (float(np.median(gpu)), " ".join("%.0f" % v for v in gpu)))
+        say("    numpy restatement on %d processes:                                      %.0f scans/s over the workers' loops (runs %s); %.0f scans/s "
+            "incl. process start" % (WORKERS, float(np.median([c[0] for c in cpu])), " ".join("%.0f" % c[0] for c in cpu),
+                                     float(np.median([c[1] for c in cpu]))))
+
+
+def drive_raw(args):
+    out = os.path.abspath(args.out)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    me = "%s %s" % (sys.executable, os.path.abspath(__file__))
+    steps = ["timeout -k 10 240 %s --step sparsify --iters 30" % me,
+             "timeout -k 10 420 %s --step raw_builder" % me,
+             "timeout -k 10 540 %s --step raw_trainer" % me,
+             "timeout -k 10 420 %s --step offline" % me]
+    cmd = "set -o pipefail; (" + " && ".join(steps) + ") 2>&1 | grep --line-buffered -v '^{' | tee %s" % out
+    sys.exit(subprocess.call(["bash", "-c", cmd], cwd=ROOT))
+
+
 def drive(args):
     out = os.path.abspath(args.out)
     os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -336,8 +602,12 @@ def drive(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loader_time.log"))
+    ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
+                                                      "raw_builder", "raw_trainer", "offline", "offline_worker"])
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--root", default="")
+    ap.add_argument("--split_file", default="")
+    ap.add_argument("--worker", type=int, default=0)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--items", type=int, default=12)
     ap.add_argument("--steps", type=int, default=12)
@@ -345,7 +615,10 @@ def main():
     ap.add_argument("--colour_ms", type=float, default=0.0)
     ap.add_argument("--trace_dir", default="")
     args = ap.parse_args()
-    {"all": drive, "colour": step_colour, "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker,
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sparsify_time.log" if args.step == "raw" else "loader_time.log")
+    {"raw": drive_raw, "sparsify": step_sparsify, "raw_builder": step_raw_builder, "raw_trainer": step_raw_trainer, "offline": step_offline,
+     "offline_worker": step_offline_worker, "all": drive, "colour": step_colour, "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker,
      "builder": step_builder, "trainer": step_trainer}[args.step](args)
 
 
