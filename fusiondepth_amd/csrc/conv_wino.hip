@@ -40,10 +40,6 @@ __device__ __forceinline__ float wino_act(float v, int act) {
     return act == 1 ? fmaxf(v, 0.f) : v;
 }
 
-#ifndef FD_WINO_ABLATE
-#define FD_WINO_ABLATE 0     // timing experiments only (wrong results): 1 no main loop, 2 no output stores, 4 no epilogue at all, 8 no prologue loads,
-                             // 16 loop loads out of range (no traffic), 32 no operand LDS stores in the loop, 64 loop loads from a 16 KB window
-#endif
 constexpr int WBM = 64, WBN = 64, WBKC = 16, WNT = 256;
 constexpr int LDU = WBM + 1, LDV = WBN, LDM = WBN + 1;
 // k_conv_wino keeps the activations RAW in LDS - one row of the tile's 128 pixels per channel: [0] a cell that stays 0.0,
@@ -310,7 +306,6 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
             mid_off2 = prep_ok2 ? prep_base2 : FD_OOB;
             h_off2 = (prep_ok2 & halo_l) ? prep_base2 - 4u : ((prep_ok2 & halo_r) ? prep_base2 + 8u : FD_OOB);
         }
-        if (FD_WINO_ABLATE & 16) { u_off = mid_off = h_off = FD_OOB; d_off[0] = d_off[1] = d_off[2] = FD_OOB; }   // loads issue, no memory traffic
         pc_c0 += WBKC;
         const bool wrap = pc_c0 >= g.C;
         pc_c0 = wrap ? 0 : pc_c0;
@@ -387,13 +382,12 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
     // of slot i - loaded one whole chunk earlier - are written to the LDS buffer of chunk ch + 1 and immediately re-loaded with
     // chunk ch + 2.  Every global load thus has a full chunk (8 k-steps, >= 2 000 cycles) to return before its s_waitcnt; with
     // load and store of the same chunk four k-steps apart (round 2) the wait stalled the wave - and the MFMAs behind it - whenever
-    // the fabric was slower than that (scripts/wino_ksweep.py + FD_WINO_ABLATE: 14 % of the loop time).
+    // the fabric was slower than that (14 % of the loop time: profiles/round3_experiments.md section 1).
     constexpr int NK = WBKC / 2;       // 8 MFMA k-steps per chunk
     constexpr int LS = NK / 2;         // staging slots: k-steps 0-3
     const int arow = lane >> 5, acol = lane & 31;
     if (ch_lo < ch_hi) {
         prep_a(true); prep_b();
-        if (FD_WINO_ABLATE & 8) { u_off = mid_off = h_off = FD_OOB; }
 #pragma unroll
         for (int t = 0; t < 4; ++t) load_u(t);
         if (VDMA) {
@@ -422,7 +416,7 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __syncthreads();
-        for (int ch = ch_lo; ch < ((FD_WINO_ABLATE & 1) ? ch_lo : ch_hi); ++ch) {
+        for (int ch = ch_lo; ch < ch_hi; ++ch) {
             const int cur = (ch - ch_lo) & 1;
             // operands of component t: A = U_t[k][32 wm + acol], B = input transform of the raw row k at this lane's pair;
             // k = 2 kk + arow
@@ -449,10 +443,8 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][0], bv[cb][0], acc[0], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (kk + 1 < NK) { read_b(2 * (kk + 1)); read_a(nb, 2 * (kk + 1), 0); read_a(nb, 2 * (kk + 1), 1); }
-                if (!(FD_WINO_ABLATE & (32 | 128))) {
-                    if (!VDMA && kk < LS) store_u(cur ^ 1, kk);
-                    if (VDMA && kk >= LS) store_u(cur ^ 1, kk - LS);
-                }
+                if (!VDMA && kk < LS) store_u(cur ^ 1, kk);
+                if (VDMA && kk >= LS) store_u(cur ^ 1, kk - LS);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][1], bv[cb][1], acc[1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
@@ -461,7 +453,7 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
                 __builtin_amdgcn_sched_barrier(0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][2], bv[cb][2], acc[2], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!VDMA && kk < LS && !(FD_WINO_ABLATE & (32 | 256))) store_v(cur ^ 1, kk);
+                if (!VDMA && kk < LS) store_v(cur ^ 1, kk);
                 if (kk + 1 < NK) xform_b(nb);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][3], bv[cb][3], acc[3], 0, 0, 0);
@@ -485,7 +477,6 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
 
     // ---- epilogue: output transform in registers.  C/D layout of the 32x32 MFMA: column (pair) = lane & 31,
     //      row (channel) = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-    if (FD_WINO_ABLATE & 4) { if (acc[0][0] == 123.456f) g.Y[tid] = acc[1][3] + acc[2][2] + acc[3][1]; return; }
     const int po = p0 + 32 * wn + acol;                                   // this lane's output pair
     const bool final_pass = !TWOD && nsplit == 1;
     const unsigned hwo = TWOD ? (unsigned)(HT * g.W) : hw;                // plane of the tensor written: S_ri has H / 2 rows
@@ -530,8 +521,7 @@ __device__ __forceinline__ void conv_wino_body(const WinoArgs& g) {
                     o.x += a2.x; o.y += a2.y;
                 }
             }
-            if (!(FD_WINO_ABLATE & 2) || o.x == 123.456f)
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsY, (int)off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsY, (int)off, 0, 0);
             if (STATS) { const float dd = o.x - o.y; s1[r] = o.x + o.y; s2[r] = 0.5f * dd * dd; }
         }
     };
@@ -1076,9 +1066,6 @@ __global__ void __launch_bounds__(WNT) k_conv_wino2d_limb(WinoArgs g) {
 // K loops a third longer than the 1-D kernel's (4 C / 16 against 3 C / 16 chunks per tile of twice the pixels), and the four row
 // combinations of a tile's input rows are formed by ONE workgroup out of L1 / L2 instead of four.  128 accumulator registers per
 // lane: two waves per SIMD.
-#ifndef FD_W2P_ABLATE
-#define FD_W2P_ABLATE 0      // timing experiments only (wrong results): 1 no fold, 2 loop loads out of range, 4 no LDS stores in the loop, 8 no barrier, 16 no output stores
-#endif
 typedef float f32x16_w2p __attribute__((ext_vector_type(16)));
 // Final outputs of a k_conv_wino2p tile from the two folded accumulator pairs (shared by the register-staged and the direct-to-LDS
 // variant of the kernel)
@@ -1125,10 +1112,8 @@ __device__ __forceinline__ void w2p_epilogue(const WinoArgs& g, const f32x16_w2p
                 const f32x2 a2 = fd_ldg64(rsAdd, off), b2 = fd_ldg64(rsAdd, off + row_b);
                 oa.x += a2.x; oa.y += a2.y; ob.x += b2.x; ob.y += b2.y;
             }
-            if (!(FD_W2P_ABLATE & 16) || oa.x == 123.456f) {
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oa), rsY, (int)off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ob), rsY, (int)(off + row_b), 0, 0);
-            }
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oa), rsY, (int)off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ob), rsY, (int)(off + row_b), 0, 0);
             if (STATS) {
                 const float da = oa.x - oa.y, db = ob.x - ob.y;
                 const float ta = oa.x + oa.y, tb = ob.x + ob.y, dab = ta - tb;
@@ -1241,7 +1226,6 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
         h_off = (prep_ok & halo_l) ? prep_base - 4u : ((prep_ok & halo_r) ? prep_base + 8u : FD_OOB);
         mid_off2 = prep_ok2 ? prep_base2 : FD_OOB;
         h_off2 = (prep_ok2 & halo_l) ? prep_base2 - 4u : ((prep_ok2 & halo_r) ? prep_base2 + 8u : FD_OOB);
-        if ((FD_W2P_ABLATE & 2) && pc_f > 1) { u_off = mid_off = h_off = mid_off2 = h_off2 = FD_OOB; }
         ++pc_f;
         pc_c0 += WBKC;
         const bool wrap = pc_c0 >= g.C;
@@ -1342,7 +1326,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][0], bv[cb][0], acc[0], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (kk + 1 < NK) { read_b(2 * (kk + 1)); read_a(nb, 2 * (kk + 1), 0); read_a(nb, 2 * (kk + 1), 1); }
-                if (kk < LS && !(FD_W2P_ABLATE & 4)) store_u(cur ^ 1, kk);
+                if (kk < LS) store_u(cur ^ 1, kk);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][1], bv[cb][1], acc[1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1351,7 +1335,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 __builtin_amdgcn_sched_barrier(0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][2], bv[cb][2], acc[2], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk < LS && !(FD_W2P_ABLATE & 4)) store_v(cur ^ 1, kk, sgn_regs);
+                if (kk < LS) store_v(cur ^ 1, kk, sgn_regs);
                 if (kk + 1 < NK) xform_b(nb);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][3], bv[cb][3], acc[3], 0, 0, 0);
@@ -1361,7 +1345,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 if (kk == NK - 1) prep_b();
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (ch == next_fold && !(FD_W2P_ABLATE & 1)) {
+            if (ch == next_fold) {
                 // end of row component ri_cur: fold the horizontally transformed products into the two output rows and start afresh
                 const float sa = ri_cur <= 2 ? 1.f : 0.f;             // y[2 ty]     = S0 + S1 + S2
                 const float sb = ri_cur == 0 ? 0.f : (ri_cur == 1 ? 1.f : -1.f);   // y[2 ty + 1] = S1 - S2 - S3
@@ -1377,7 +1361,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 next_fold += cpt;
                 ++ri_cur;
             }
-            if (!(FD_W2P_ABLATE & 8)) __syncthreads();
+            __syncthreads();
         }
     }
     w2p_epilogue<STATS>(g, ya, yb, p0, m0, Np, plane2, W2, hw, lane, wm, wn);
@@ -1462,7 +1446,6 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                     d_off[s_][q] = (live & (refl | inb)) ? d_base[q] + (unsigned)(ruse * g.W * 4) : FD_OOB;   // FD_OOB base + anything stays out of range
                 }
         }
-        if ((FD_W2P_ABLATE & 2) && pc_f > 1) { u_off = FD_OOB; for (int s_ = 0; s_ < 2; ++s_) for (int q = 0; q < 3; ++q) d_off[s_][q] = FD_OOB; }
         ++pc_f;
         pc_c0 += WBKC;
         const bool wrap = pc_c0 >= g.C;
@@ -1557,7 +1540,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][0], bv[cb][0], acc[0], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (kk + 1 < NKW) { read_b(2 * (kk + 1)); read_a(nb, 2 * (kk + 1), 0); read_a(nb, 2 * (kk + 1), 1); }
-                if (!HALFM && kk >= LS && !(FD_W2P_ABLATE & 4)) store_u(cur ^ 1, kk - LS);
+                if (!HALFM && kk >= LS) store_u(cur ^ 1, kk - LS);
                 if (HALFM && kk >= 2) { store_u(cur ^ 1, 2 * (kk - 2)); store_u(cur ^ 1, 2 * (kk - 2) + 1); }     // loaded in k-steps 0, 1
                 __builtin_amdgcn_sched_barrier(0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][1], bv[cb][1], acc[1], 0, 0, 0);
@@ -1583,7 +1566,7 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (ch == next_fold && !(FD_W2P_ABLATE & 1)) {
+            if (ch == next_fold) {
                 const float sa = ri_cur <= 2 ? 1.f : 0.f;
                 const float sb = ri_cur == 0 ? 0.f : (ri_cur == 1 ? 1.f : -1.f);
 #pragma unroll
@@ -1595,11 +1578,12 @@ __global__ void __launch_bounds__(WNT) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
                     for (int t = 0; t < 4; ++t) acc[t][r] = 0.f;
                 }
+                next_fold += cpt;
+                ++ri_cur;
             }
-            if (ch == next_fold) { next_fold += cpt; ++ri_cur; }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this chunk's DMAs (into the other buffer) have landed
             __builtin_amdgcn_sched_barrier(0);
-            if (!(FD_W2P_ABLATE & 8)) __syncthreads();
+            __syncthreads();
         }
     }
     if constexpr (HALFM) {                                           // wm = 0 keeps (its own) + (wm = 1's) partial outputs
@@ -1639,9 +1623,6 @@ struct WinoWgradArgs {
     int adv_n, adv_y, adv_j;   // one chunk of WGP pairs = adv_n images + adv_y rows + adv_j pairs (host: divisions once per launch)
 };
 constexpr int WGP = 16;                                          // pairs per chunk (GEMM-K 16 -> 8 MFMA k-steps)
-#ifndef FD_WGRAD_ABLATE       // timing experiments only (wrong results), scripts/build_ablation.sh: 1 no global loads in the loop,
-#define FD_WGRAD_ABLATE 0     // 2 no LDS stores, 4 no border masks, 8 no chunk index arithmetic, 16 no barrier, 32 no operand
-#endif                        // transforms, 64 no operand reads
 
 // Both operands stay RAW in LDS and the transforms P = (y0, y0+y1, y0-y1, y1), Q = (d0-d2, d1+d2, d2-d1, d1-d3) are applied when the
 // MFMA operands are read.  dY: one row of the chunk's 32 pixels per output channel (stride 34 floats: a lane (= channel) reads
@@ -1730,7 +1711,7 @@ __global__ void __launch_bounds__(WNT) k_wgrad_wino(WinoWgradArgs g) {
     int pf = 0, rf = 0;          // bit 0 / 1: the pair of the PREPARED chunk (pf) / of the chunk whose data sit in ra, rx (rf) starts / ends an image row
     int pc = pp_lo;                                              // first pair of the chunk being prepared
     // (image, row, pair in row) of this thread's pair of the chunk being prepared: divided out once, then advanced by one chunk per
-    // call with two carries - the two integer divisions per chunk of the first version were 15 % of the kernel (ablation, profiles/)
+    // call with two carries - the two integer divisions per chunk of the first version were 15 % of the kernel (profiles/round3_experiments.md)
     int cn, cy, cj;
     {
         const int pq = pp_lo + p;
@@ -1852,24 +1833,24 @@ __global__ void __launch_bounds__(WNT) k_wgrad_wino(WinoWgradArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][0], bv[cb][0], acc[0], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk + 1 < NKW && !(FD_WGRAD_ABLATE & 64)) read_ops(kk + 1);
+                if (kk + 1 < NKW) read_ops(kk + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][1], bv[cb][1], acc[1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk < LS && !(FD_WGRAD_ABLATE & 2)) store_row(cur ^ 1, kk);              // registers loaded one chunk ago -> the other buffer
+                if (kk < LS) store_row(cur ^ 1, kk);              // registers loaded one chunk ago -> the other buffer
                 __builtin_amdgcn_sched_barrier(0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][2], bv[cb][2], acc[2], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk + 1 < NKW) { if (!(FD_WGRAD_ABLATE & 32)) xform(nb); else { for (int t = 0; t < 4; ++t) { av[nb][t] = av[cb][t]; bv[nb][t] = bv[cb][t]; } } }
+                if (kk + 1 < NKW) xform(nb);
                 __builtin_amdgcn_sched_barrier(0);
                 acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][3], bv[cb][3], acc[3], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk < LS && !(FD_WGRAD_ABLATE & 1)) load_row(kk);                        // ... and re-loaded with the chunk after next
+                if (kk < LS) load_row(kk);                        // ... and re-loaded with the chunk after next
                 if (kk == (HALFM ? NKW - 1 : LS)) rf = pf;                                  // the flags travel with the registers (all four rows re-loaded by now)
-                if (kk == NKW - 1 && !(FD_WGRAD_ABLATE & 8)) prep_chunk(ch + 3 < nchunk);
+                if (kk == NKW - 1) prep_chunk(ch + 3 < nchunk);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!(FD_WGRAD_ABLATE & 16)) __syncthreads();
+            __syncthreads();
         }
     }
 

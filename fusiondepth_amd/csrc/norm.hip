@@ -619,9 +619,6 @@ __global__ void __launch_bounds__(NT) k_bn_bwd_small(const float* __restrict__ x
 }
 
 inline bool bn_small(int Ng, long HW, int groups, bool vec) {
-#ifdef FD_ABLATE_NO_BN_SMALL     // timing experiment only: small planes cost nothing (the launches are skipped by the callers)
-    (void)Ng; (void)HW; (void)groups; (void)vec;
-#endif
     return vec && groups <= 16 && (long)Ng * (HW >> 2) <= (long)NT * SMALL_K;
 }
 
@@ -977,18 +974,12 @@ extern "C" int fd_bn_train_fwd(const float* x, const float* weight, const float*
     FD_REQUIRE(x && y && save_mean && save_invstd && ws && N > 0 && C > 0 && H > 0 && W > 0, "fd_bn_train_fwd: bad args");
     FD_REQUIRE(groups >= 1 && N % groups == 0, "fd_bn_train_fwd: batch %d is not divisible into %d groups", N, groups);
     FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "fd_bn_train_fwd: running stats must come in pairs");
-#ifdef FD_ABLATE_NO_BN          // timing experiment only (wrong results): what the step would gain if BatchNorm cost nothing
-    return 0;
-#endif
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     const int Ng = N / groups;
     const int sp = bn_splits(Ng, C, HW, groups);
     const bool vec = bn_vec_ok(HW, x, y, residual, nullptr, nullptr);
     if (bn_small(Ng, HW, groups, vec)) {
-#ifdef FD_ABLATE_NO_BN_SMALL
-        return 0;
-#endif
         hipLaunchKernelGGL(k_bn_train_small, dim3(C), dim3(NT), 0, st, x, weight, bias, residual, y, running_mean, running_var,
                            save_mean, save_invstd, Ng, C, (int)(HW >> 2), eps, momentum, relu, groups);
         FD_LAUNCH_CHECK("fd_bn_train_fwd(small)");
@@ -996,11 +987,9 @@ extern "C" int fd_bn_train_fwd(const float* x, const float* weight, const float*
     }
     auto stats = vec ? k_bn_stats<true> : k_bn_stats<false>;
     auto apply = vec ? k_bn_apply_train<true> : k_bn_apply_train<false>;
-#ifndef FD_ABLATE_NO_BN_STATS    // timing experiment only: the apply pass then normalises with whatever the workspace holds
     float* shifts = ws + (long)groups * C * sp * 2;              // [group][channel], behind the partial sums
     hipLaunchKernelGGL(stats, dim3(C, sp, groups), dim3(NT), 0, st, x, ws, shifts, Ng, C, HW, sp);
     FD_LAUNCH_CHECK("fd_bn_train_fwd(stats)");
-#endif
     hipLaunchKernelGGL(apply, dim3(plane_blocks(HW), N * C), dim3(NT), 0, st, x, weight, bias, residual, y,
                        running_mean, running_var, save_mean, save_invstd, ws, ws + (long)groups * C * sp * 2, Ng, C, HW, sp, eps, momentum,
                        relu, groups);
@@ -1047,9 +1036,6 @@ static int bn_train_bwd_impl(const float* x, const float* y, const float* gy, co
     FD_REQUIRE(x && gy && save_mean && save_invstd && gx && ws && N > 0 && C > 0 && H > 0 && W > 0,
                "fd_bn_train_bwd: bad args");
     FD_REQUIRE(groups >= 1 && N % groups == 0, "fd_bn_train_bwd: batch %d is not divisible into %d groups", N, groups);
-#ifdef FD_ABLATE_NO_BN
-    return 0;
-#endif
     FD_REQUIRE(!relu || y || !g_residual, "fd_bn_train_bwd: a BatchNorm with a residual input needs the forward output for its ReLU mask");
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
@@ -1057,9 +1043,6 @@ static int bn_train_bwd_impl(const float* x, const float* y, const float* gy, co
     const int sp = bn_splits(Ng, C, HW, groups);
     const bool vec = bn_vec_ok(HW, x, y, gy, gx, g_residual);
     if (bn_small(Ng, HW, groups, vec)) {
-#ifdef FD_ABLATE_NO_BN_SMALL
-        return 0;
-#endif
         hipLaunchKernelGGL(k_bn_bwd_small, dim3(C), dim3(NT), 0, st, x, y, gy, weight, save_mean, save_invstd, gx, gweight, gbias,
                            g_residual, Ng, C, (int)(HW >> 2), relu, accumulate, groups, bias);
         FD_LAUNCH_CHECK("fd_bn_train_bwd(small)");
@@ -1067,11 +1050,9 @@ static int bn_train_bwd_impl(const float* x, const float* y, const float* gy, co
     }
     auto reduce = vec ? k_bn_bwd_reduce<true> : k_bn_bwd_reduce<false>;
     auto apply = vec ? k_bn_bwd_apply<true> : k_bn_bwd_apply<false>;
-#ifndef FD_ABLATE_NO_BN_STATS
     hipLaunchKernelGGL(reduce, dim3(C, sp, groups), dim3(NT), 0, st, x, y, gy, save_mean, save_invstd, ws, Ng, C, HW,
                        sp, relu, weight, bias);
     FD_LAUNCH_CHECK("fd_bn_train_bwd(reduce)");
-#endif
     hipLaunchKernelGGL(apply, dim3(plane_blocks(HW), N * C), dim3(NT), 0, st, x, y, gy, weight, save_mean,
                        save_invstd, gx, gweight, gbias, g_residual, ws, Ng, C, HW, sp, relu, accumulate, groups, bias);
     FD_LAUNCH_CHECK("fd_bn_train_bwd(apply)");

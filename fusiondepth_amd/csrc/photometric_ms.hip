@@ -42,11 +42,7 @@ __device__ __forceinline__ float shr1(float v) {   // lane l <- lane l-1 (0 at t
 __device__ __forceinline__ float shl1(float v) {   // lane l <- lane l+1
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
-#ifndef FD_MS_ABLATE
-#define FD_MS_ABLATE 0    // timing experiments only (wrong results): 1 no barrier, 4 no DPP, 8 no LDS lag ring, 16 no LDS exchange
-#endif
 __device__ __forceinline__ float hsum3(float v) {
-    if (FD_MS_ABLATE & 4) return (v + v * 0.99f) + v * 1.01f;
     return (v + shr1(v)) + shl1(v);
 }
 
@@ -303,7 +299,7 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         Lag l2;                                                            // row i-2, consumed by the gradient stage at the end
         if (GRAD) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) l2.q[k] = (FD_MS_ABLATE & 8) ? make_float4(p.fx, p.fy, p.u, p.v) : lagr[f][K2][k][lane];
+            for (int k = 0; k < 4; ++k) l2.q[k] = lagr[f][K2][k][lane];
         }
         Lag lg;
         lg.q[1].z = p.KX; lg.q[1].w = p.KY; lg.q[2].x = p.u; lg.q[2].y = p.v; lg.q[2].z = p.E0; lg.q[2].w = p.E1; lg.q[3].x = p.depth;
@@ -328,10 +324,13 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
             hn[5 * c + 3] = hsum3(yc);
             hn[5 * c + 4] = hsum3(yc * yc);
         }
-        if (GRAD && !(FD_MS_ABLATE & 8)) {
+        if (GRAD) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) lagr[f][KC][k][lane] = lg.q[k];
         } else if (GRAD) {
+            // never taken.  Naming acc3 here fixes the order in which this lambda captures the accumulators, and with it the
+            // register allocation: without the arm the same instructions come out on permuted registers.  Remove it in a change
+            // that is judged by a measurement, not by identical assembly.
             acc3 += lg.q[0].x + lg.q[0].y + lg.q[0].z + lg.q[0].w + lg.q[1].x + lg.q[1].y + lg.q[3].y + lg.q[3].z + lg.q[3].w;
         } else if (has_beam) {
             lagr[f][KC][3][lane] = lg.q[3];
@@ -380,18 +379,16 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         const float vown = IDENT ? fmaf(p.nzv, 0.00001f, p.idv) : 0.f;   // trainer.py:551-552
         // ---- D: exchange with the other frame's wave, 4-way argmin (trainer.py:549-567) ------------------------------------
         const int par = i & 1;
-        if (!(FD_MS_ABLATE & 16)) {
-            xl[par][f][0][lane] = Lown;
-            if (IDENT) xl[par][f][1][lane] = vown;
-        }
-        if (!(FD_MS_ABLATE & 1)) __syncthreads();
-        const float Loth = (FD_MS_ABLATE & 16) ? Lown * 1.01f : xl[par][1 - f][0][lane];
+        xl[par][f][0][lane] = Lown;
+        if (IDENT) xl[par][f][1][lane] = vown;
+        __syncthreads();
+        const float Loth = xl[par][1 - f][0][lane];
         // order of cat(identity -1, identity +1, reprojection -1, reprojection +1); the first minimum wins
         bool selown = f == 0 ? !(Loth < Lown) : (Lown < Loth);
         float best = fminf(Lown, Loth);
         float vmin = 0.f, voth = 0.f;
         if (IDENT) {
-            voth = (FD_MS_ABLATE & 16) ? vown * 0.99f : xl[par][1 - f][1][lane];
+            voth = xl[par][1 - f][1][lane];
             vmin = fminf(vown, voth);
             selown = selown && (Lown < vmin);
             best = fminf(best, vmin);

@@ -1,6 +1,6 @@
 """Step time of the default training step (ResNet-18, 640x192, --batch_size 12) without bench.py's checks: median of three 20-step
-windows.  For what-if builds (FD_LIBFDHIP=...libfdhip_skip.so FD_SKIP=<sites>, scripts/build_skip_ablation.sh) whose results are wrong
-by design.  usage: step_time.py [label]"""
+windows.  FD_LIBFDHIP=<path of another build of libfdhip.so> times that build instead, for a same-box A/B of two builds.
+usage: step_time.py [label]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
@@ -30,5 +30,5 @@ for w in range(3):
     torch.cuda.synchronize()
     win.append((time.perf_counter() - t0) * 50); host.append(th * 50)
 o = sorted(range(3), key=lambda i: win[i])[1]
-print("%-28s step %.2f ms (windows %s), host issue %.2f ms" % (sys.argv[1] if len(sys.argv) > 1 else os.environ.get("FD_SKIP", "-"),
+print("%-28s step %.2f ms (windows %s), host issue %.2f ms" % (sys.argv[1] if len(sys.argv) > 1 else "-",
       win[o], " ".join("%.2f" % x for x in win), host[o]), flush=True)

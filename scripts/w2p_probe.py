@@ -1,5 +1,5 @@
-"""k_conv_wino2p alone: time per launch on the layer1 / layer2 shapes (batch 12 / 24), random data.  Run with FD_LIBFDHIP=<ablation build>
-to see what a loop ingredient costs (scripts/build_ablation.sh w2p_<tag> conv_wino -DFD_W2P_ABLATE=<bits>): w2p_probe.py"""
+"""k_conv_wino2p alone: time per launch on the layer1 / layer2 shapes (batch 12 / 24), random data.  FD_LIBFDHIP=<path of another
+build of libfdhip.so> times that build instead, for a same-box A/B of two builds: w2p_probe.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch

@@ -1,4 +1,4 @@
-"""Stand-alone time of Winograd weight-gradient shapes (with FD_LIBFDHIP = an ablation build: where the loop's time goes).  wgrad_time.py"""
+"""Stand-alone time of Winograd weight-gradient shapes (FD_LIBFDHIP=<path of another build of libfdhip.so> times that build: same-box A/B of two builds).  wgrad_time.py"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
