@@ -63,6 +63,11 @@ class RasterDesc(ctypes.Structure):
     _fields_ = [("P", _D * 12), ("im_h", _I), ("im_w", _I), ("flip", _I), ("reserved", _I)]
 
 
+class ResizeDesc(ctypes.Structure):
+    """Mirror of ``fd_resize_desc``."""
+    _fields_ = [("offset", _L), ("h_in", _I), ("w_in", _I), ("mirror", _I), ("reserved", _I)]
+
+
 class RelayoutJob(ctypes.Structure):
     """Mirror of ``fd_relayout_job``."""
     _fields_ = ([("w", ctypes.c_void_p), ("dst", ctypes.c_void_p)] +
@@ -185,6 +190,7 @@ SIGNATURES = {
     "fd_sparsify_scans": ("pp" "l" "ppppppp" "p", "i"),
     "fd_velo_rasterize_batch_ws_bytes": ("iii", "l"),
     "fd_velo_rasterize_batch": ("pp" "ii" "p" "iiiiii" "ppp" "p", "i"),
+    "fd_resize_bilinear_batch": ("pl" "p" "iii" "p" "p", "i"),
 }
 
 _lock = threading.Lock()

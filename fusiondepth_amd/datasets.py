@@ -41,7 +41,16 @@ the beam maps, ``fd_velo_rasterize_batch`` for ``depth_gt`` (frame 0's scan serv
 instead, with the generator keyed by (``seed``, folder, frame index) - a frame's sparse scan is the same in every epoch, batch and
 worker order, and the same as the offline tool writes with ``--seed``.  The two sources give bit-identical batches.
 
-Not covered (each raises): the stereo frame ``"s"``, ``need_full_res_4beam`` (needs cv2), ``need_inf_gdc`` / ``clone_gdc``.
+The Refiner's loader.  ``KITTIRefinerBatches`` is ``KITTIRAWBatches`` plus the ``"inf_gdc"`` key (mono_dataset.py:224-226,
+kitti_dataset.py:154-173): the dense GDC-corrected depth ``python -m fusiondepth_amd.inf_gdc`` wrote per frame, resized to
+``(height, width)`` with ATen's CPU bilinear rule and mirrored after the resize where the item is flipped - bit-identical to the
+reference's ``F.interpolate`` + ``fliplr`` on the host.  The maps of a batch differ in size with the date; the worker threads load
+them straight into one pinned staging buffer that also carries the descriptor table, so the key costs ONE host-to-device copy and
+ONE library call (``fd_resize_bilinear_batch``) per batch.  Shape ``[B, height, width]``, the reference's squeezed shape (it
+hardcodes ``[192, 640]``: the same deviation as ``4beam``, identical at the default size).  Every other key is the parent's.
+
+Not covered (each raises): the stereo frame ``"s"``, ``need_full_res_4beam`` (needs cv2; ``4beam_full`` / ``2channel_full`` are read by
+nothing in the reference); in ``KITTIRAWBatches`` itself also ``need_inf_gdc`` / ``clone_gdc`` - those are ``KITTIRefinerBatches``'.
 """
 import concurrent.futures
 import ctypes
@@ -96,33 +105,30 @@ def parse_line(line):
 
 class KITTIRAWBatches:
     """See the module docstring.  The first nine arguments are ``KITTIRAWDataset``'s; ``batch_size`` / ``shuffle`` are the
-    ``DataLoader``'s (``drop_last=True``).  ``seed`` seeds the epoch order and the per-item draws, ``workers`` sizes the decode pool
-    (at most 16), ``draws`` = callable ``(epoch, index) -> dict`` that replaces ``item_draws`` (tests inject flags and jitter
-    parameters through it), ``loader`` = callable ``path -> [H,W,3] uint8`` instead of the PIL decoder (pre-decoded frames),
-    ``prefetch`` = issue the next batch on a side stream before handing out the current one, ``lidar_source`` = ``"files"`` (sparse
-    scans written offline) or ``"raw"`` (sparsified here from ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default:
-    the reference's list for ``opt.nbeams``), ``sparsify_grid`` = (H, W) of its angular grid."""
+    ``DataLoader``'s, ``drop_last`` too (default True; False also yields the trailing partial batch).  ``seed`` seeds the epoch
+    order and the per-item draws, ``workers`` sizes the decode pool (at most 16), ``draws`` = callable ``(epoch, index) -> dict``
+    that replaces ``item_draws`` (tests inject flags and jitter parameters through it), ``loader`` = callable ``path -> [H,W,3]
+    uint8`` instead of the PIL decoder (pre-decoded frames), ``prefetch`` = issue the next batch on a side stream before handing
+    out the current one, ``lidar_source`` = ``"files"`` (sparse scans written offline) or ``"raw"`` (sparsified here from
+    ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default: the reference's list for ``opt.nbeams``),
+    ``sparsify_grid`` = (H, W) of its angular grid."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
                  batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
-                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024)):
+                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True):
         self.data_path, self.filenames = data_path, list(filenames)
         self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
         self.frame_idxs = list(frame_idxs)
         self.is_train, self.img_ext, self.opt = bool(is_train), img_ext, opt
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
+        self.drop_last = bool(drop_last)
         self.device = torch.device(device)
         self.workers = max(1, min(int(workers), 16))
         self.jitter_per_image = bool(jitter_per_image)
         self.draws, self.loader, self.prefetch = draws, loader or pil_loader, bool(prefetch)
         if self.batch_size < 1:
             raise ValueError("KITTIRAWBatches: batch_size must be positive")
-        if "s" in self.frame_idxs:
-            raise NotImplementedError("KITTIRAWBatches: the stereo frame 's' is not covered (temporal frames only)")
-        if self._opt("need_full_res_4beam"):
-            raise NotImplementedError("KITTIRAWBatches: need_full_res_4beam is not covered (the reference resizes with cv2)")
-        if self._opt("need_inf_gdc") or self._opt("clone_gdc"):
-            raise NotImplementedError("KITTIRAWBatches: need_inf_gdc / clone_gdc are not covered (no inf_gdc maps are loaded)")
+        self._check_covered()
         if 0 not in self.frame_idxs:
             raise ValueError("KITTIRAWBatches: frame_idxs must contain 0 (the frame every network and the LiDAR keys refer to)")
         self.need_4beam = bool(self._opt("need_4beam"))
@@ -142,11 +148,21 @@ class KITTIRAWBatches:
         self._epoch = 0
         self._pool = None
         self._stream = None
-        self._K = None
+        self._K = {}
         self._calib = {}
 
     def _opt(self, name, default=False):
         return getattr(self.opt, name, default) if self.opt is not None else default
+
+    def _check_covered(self):
+        """Refuse what this class does not build (module docstring, "Not covered"); a subclass that builds more overrides it."""
+        if "s" in self.frame_idxs:
+            raise NotImplementedError("KITTIRAWBatches: the stereo frame 's' is not covered (temporal frames only)")
+        if self._opt("need_full_res_4beam"):
+            raise NotImplementedError("KITTIRAWBatches: need_full_res_4beam is not covered (the reference resizes with cv2)")
+        if self._opt("need_inf_gdc") or self._opt("clone_gdc"):
+            raise NotImplementedError("KITTIRAWBatches: need_inf_gdc / clone_gdc are not covered (no inf_gdc maps are loaded); "
+                                      "KITTIRefinerBatches loads them")
 
     # ---- paths (kitti_dataset.py:44-54, 72-76, 93-103) --------------------------------------------------------------------------
     def get_image_path(self, folder, frame_index, side):
@@ -182,13 +198,14 @@ class KITTIRAWBatches:
 
     # ---- order and draws --------------------------------------------------------------------------------------------------------
     def __len__(self):
-        return len(self.filenames) // self.batch_size            # drop_last=True
+        n, B = len(self.filenames), self.batch_size
+        return n // B if self.drop_last else (n + B - 1) // B
 
     def epoch_order(self, epoch):
-        """Item indices of one epoch, in batch order (the trailing partial batch is dropped)."""
+        """Item indices of one epoch, in batch order (with ``drop_last`` the trailing partial batch is dropped)."""
         n = len(self.filenames)
         order = np.random.default_rng([self.seed, int(epoch)]).permutation(n) if self.shuffle else np.arange(n)
-        return [int(i) for i in order[:len(self) * self.batch_size]]
+        return [int(i) for i in order[:len(self) * self.batch_size if self.drop_last else n]]
 
     def item_draws(self, epoch, index):
         """The random part of one item, a function of (seed, epoch, index) alone: ``do_color_aug`` and ``do_flip`` (``random() > 0.5``
@@ -410,9 +427,9 @@ class KITTIRAWBatches:
             if self._opt("need_path"):
                 batch["path"] = [self.filenames[it["index"]] for it in items]
         self._colour_keys(items, batch)
-        if self._K is None:
-            self._K = synthetic.intrinsics(len(items), self.height, self.width, self.num_scales, self.device)
-        batch.update(self._K)
+        if len(items) not in self._K:                            # by batch size: the trailing partial batch has its own
+            self._K[len(items)] = synthetic.intrinsics(len(items), self.height, self.width, self.num_scales, self.device)
+        batch.update(self._K[len(items)])
         self._lidar_keys(items, batch)
         return batch
 
@@ -462,3 +479,93 @@ class KITTIRAWBatches:
                 for t in self._tensors(batch):
                     t.record_stream(cur)
                 yield batch
+
+
+def _load_map_into(path, dst):
+    """``np.load(path).astype(np.float32)`` (kitti_dataset.py:166-167) straight into ``dst``, a 2-D float32 view of the staging
+    buffer planned from the date's image size."""
+    a = np.load(path)
+    if a.shape != dst.shape:
+        raise RuntimeError("KITTIRefinerBatches: %s holds a map of shape %s; the calibration of its date says %s"
+                           % (path, a.shape, dst.shape))
+    np.copyto(dst, a, casting="unsafe")
+
+
+class KITTIRefinerBatches(KITTIRAWBatches):
+    """``KITTIRAWBatches`` for the Refiner: accepts ``opt.need_inf_gdc`` / ``opt.clone_gdc`` and adds ``batch["inf_gdc"]``
+    ([B, height, width] float32) whenever ``(opt.clone_gdc and is_train) or opt.need_inf_gdc`` (mono_dataset.py:224); see the
+    module docstring.  Same arguments; every other key is the parent's."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.need_gdc = bool((self._opt("clone_gdc") and self.is_train) or self._opt("need_inf_gdc"))
+
+    def _check_covered(self):
+        if "s" in self.frame_idxs:
+            raise NotImplementedError("KITTIRefinerBatches: the stereo frame 's' is not covered (temporal frames only)")
+        if self._opt("need_full_res_4beam"):
+            raise NotImplementedError("KITTIRefinerBatches: need_full_res_4beam is not covered (the reference resizes with cv2)")
+
+    # ---- paths (kitti_dataset.py:154-161) ---------------------------------------------------------------------------------------
+    def gdc_folder(self):
+        random_sample = self._opt("random_sample", -1)
+        return "inf_gdc_r{}".format(random_sample) if random_sample > 0 else "inf_gdc_{}beam".format(self._opt("nbeams", 4))
+
+    def get_gdc_path(self, folder, frame_index, side):
+        return os.path.join(self.data_path, folder, "{}/{}_{}.npy".format(self.gdc_folder(), int(frame_index), side))
+
+    # ---- host side --------------------------------------------------------------------------------------------------------------
+    def plan_batch(self, epoch, indices):
+        items = super().plan_batch(epoch, indices)
+        if self.need_gdc:
+            for it in items:
+                it["gdc"] = self.get_gdc_path(it["folder"], it["frame_index"], it["side"])
+        return items
+
+    def _plan_gdc(self, items):
+        """Layout of the key's staging buffer, before any map is read: the descriptor table, then the planes, each of its date's
+        image size (``inf_gdc`` writes its maps at the size of camera 2's rectified image, whatever the side)."""
+        B = len(items)
+        table_bytes = ctypes.sizeof(_lib.ResizeDesc) * B
+        base = _round16(table_bytes)
+        descs, at = [], 0
+        for it in items:
+            _, (im_h, im_w) = self._projection(it["date"], 2)
+            descs.append((at, int(im_h), int(im_w), it["do_flip"]))
+            at += int(im_h) * int(im_w)
+        return {"descs": descs, "table": (0, table_bytes), "planes": (base, base + 4 * at), "bytes": base + 4 * at}
+
+    def _start_gdc(self, items, pool):
+        """One pinned staging buffer per batch; the pool loads every map straight into its slice."""
+        for it in items:
+            if not os.path.isfile(it["gdc"]):
+                raise FileNotFoundError("KITTIRefinerBatches: %s is missing; `python -m fusiondepth_amd.inf_gdc` writes the inf_gdc maps "
+                                        "(from the inf_depth maps of `python -m fusiondepth_amd.inf_depth_map`)" % it["gdc"])
+        plan = self._plan_gdc(items)
+        staging = torch.empty((plan["bytes"],), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        host[plan["table"][0]:plan["table"][1]] = np.frombuffer(FD.resize_desc_table(plan["descs"]), dtype=np.uint8)
+        planes = host[plan["planes"][0]:plan["planes"][1]].view(np.float32)
+        plan["futures"] = [pool.submit(_load_map_into, it["gdc"], planes[at:at + h * w].reshape(h, w))
+                           for it, (at, h, w, _) in zip(items, plan["descs"])]
+        plan["staging"] = staging
+        return plan
+
+    def _start_host(self, epoch, indices):
+        items = super()._start_host(epoch, indices)
+        if self.need_gdc:
+            items[0]["gdc_plan"] = self._start_gdc(items, self._workers())
+        return items
+
+    # ---- device side ------------------------------------------------------------------------------------------------------------
+    def _finish_batch(self, items):
+        batch = super()._finish_batch(items)
+        if self.need_gdc:
+            plan = items[0]["gdc_plan"]
+            for f in plan["futures"]:
+                f.result()                                       # a size mismatch raises here, with the path
+            dev = _upload(plan["staging"], self.device)
+            table = dev[plan["table"][0]:plan["table"][1]]
+            planes = dev[plan["planes"][0]:plan["planes"][1]].view(torch.float32)
+            batch["inf_gdc"] = FD.resize_bilinear_batch(planes, plan["descs"], (self.height, self.width), desc_table=table)
+        return batch

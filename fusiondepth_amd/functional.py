@@ -520,6 +520,42 @@ def velo_rasterize_batch(points, descs, shape=(384, 1280), return_full=False, ve
     return out if out is not None else full
 
 
+def resize_desc_table(descs):
+    """Host image of the ``fd_resize_desc`` table for ``descs`` = [(offset in floats, h_in, w_in, mirror)]: a ctypes array."""
+    table = (_lib.ResizeDesc * len(descs))()
+    for d, (offset, h_in, w_in, mirror) in zip(table, descs):
+        d.offset, d.h_in, d.w_in, d.mirror = int(offset), int(h_in), int(w_in), 1 if mirror else 0
+    return table
+
+
+def resize_bilinear_batch(packed, descs, size, desc_table=None):
+    """``F.interpolate(plane[None, None], size, mode="bilinear", align_corners=False)`` - ATen's CPU result, bit for bit - for B
+    planes of different sizes in one call (fd_resize_bilinear_batch), each mirrored left-right AFTER the resize where asked
+    (kitti_dataset.py:163-171).  ``packed``: a 1-D float32 CUDA tensor holding the planes; ``descs``: [(offset in floats, h_in, w_in,
+    mirror)] per plane; ``desc_table``: the same table already on the device (a uint8 CUDA tensor holding
+    ``resize_desc_table(descs)``), else it is uploaded here.  Returns [B, size[0], size[1]] float32."""
+    _need_cuda(packed)
+    if packed.dtype != torch.float32 or packed.dim() != 1 or not packed.is_contiguous() or not packed.numel():
+        raise ValueError("resize_bilinear_batch: packed must be a non-empty contiguous 1-D float32 CUDA tensor")
+    B = len(descs)
+    oh, ow = int(size[0]), int(size[1])
+    if B < 1 or oh < 1 or ow < 1:
+        raise ValueError("resize_bilinear_batch: nothing to do (%d planes -> %d x %d)" % (B, oh, ow))
+    for offset, h_in, w_in, _ in descs:
+        if h_in < 1 or w_in < 1 or offset < 0 or offset + h_in * w_in > packed.numel():
+            raise ValueError("resize_bilinear_batch: a %d x %d plane at float %d leaves the packed buffer of %d floats"
+                             % (h_in, w_in, offset, packed.numel()))
+    nbytes = B * ctypes.sizeof(_lib.ResizeDesc)
+    if desc_table is None:
+        desc_table = torch.frombuffer(bytearray(bytes(resize_desc_table(descs))), dtype=torch.uint8).to(packed.device)
+    elif desc_table.dtype != torch.uint8 or not desc_table.is_cuda or desc_table.numel() != nbytes or not desc_table.is_contiguous() \
+            or desc_table.data_ptr() % 8:
+        raise ValueError("resize_bilinear_batch: desc_table must be an 8-byte aligned contiguous uint8 CUDA tensor of %d bytes" % nbytes)
+    out = torch.empty((B, oh, ow), device=packed.device, dtype=torch.float32)
+    call("fd_resize_bilinear_batch", packed.data_ptr(), packed.numel(), desc_table.data_ptr(), B, oh, ow, out.data_ptr(), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------ fused loss --
 class PhotoOptions:
     """The option subset the fused loss reads (options.py:64-71,111-125,242-330)."""

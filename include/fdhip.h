@@ -716,6 +716,26 @@ int fd_velo_rasterize_batch(const float* points, const int* offsets, int n_max, 
                             int max_im_w, int vel_depth, int target_h, int target_w, int padded_h, float* beam_out,
                             double* depth_out, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ batched bilinear resize ("inf_gdc" key) ----
+ * kitti_dataset.py:163-171: F.interpolate(map, [h, w], mode="bilinear", align_corners=False), then fliplr where the item is
+ * flipped - for B planes of different sizes in ONE launch.  packed (device, float32 [packed_floats]) holds the planes; desc
+ * (device, [B]) says where plane b starts (in floats), its size, and whether its result is mirrored.  out [B][out_h][out_w].
+ * Arithmetic = ATen's CPU kernel in float32, bit for bit, per axis:
+ *   scale = (float)n_in / (float)n_out;  src = fmaf(scale, (float)d + 0.5f, -0.5f) (one rounding), clamped below at 0;
+ *   i0 = (int)src, i1 = i0 + (i0 < n_in - 1), l1 = src - (float)i0, l0 = 1.0f - l1
+ * and the blend, width first, the second product of each line rounded on its own:
+ *   top = fmaf(hx, x[y0][x0], lx * x[y0][x1]);  bot = fmaf(hx, x[y1][x0], lx * x[y1][x1]);  out = fmaf(hy, top, ly * bot).
+ * The mirror acts on the resized plane, out[b][y][x] = resized[b][y][out_w - 1 - x]: resizing the mirrored source rounds
+ * differently.  (torch's CPU path for outputs of about 32x64 and below rounds differently again; not covered.)
+ * A descriptor that does not lie inside the packed buffer yields a NaN plane; nothing outside the buffer is read. */
+typedef struct fd_resize_desc {
+    long offset;                  /* first float of the plane in `packed` */
+    int h_in, w_in;
+    int mirror, reserved;
+} fd_resize_desc;
+int fd_resize_bilinear_batch(const float* packed, long packed_floats, const fd_resize_desc* desc, int B, int out_h, int out_w,
+                             float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

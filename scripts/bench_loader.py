@@ -25,6 +25,15 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
   8. ``offline``      scans/s of ``python -m fusiondepth_amd.sparsify`` beside the numpy restatement (tests/sparsify_ref.py) on 16
                       worker processes.
 
+``--step refiner`` measures the Refiner's loader (``KITTIRefinerBatches``, fd_resize_bilinear_batch) and appends to ``--out``:
+
+  9. ``inf_gdc_key``      the ``inf_gdc`` key at batch 6, 375x1242 -> 192x640: upload of the pinned staging buffer and the library call, each
+                          on its own (device events), then the kernel's own time under ``rocprofv3 --kernel-trace --stats`` (a run of its
+                          own) against its compulsory traffic (maps read once, key written once) at 8 TB/s.
+ 10. ``refiner_trainer``  Refiner images/s fed by KITTIRefinerBatches (pre-decoded frames, maps from .npy files) beside the same Refiner
+                          fed synthetic batches, alternating windows; and the condition: colour path (step 1 at batch 6) + the key <=
+                          10 % of the synthetic-fed Refiner step (file mode's LiDAR keys are not in that sum, as in step 4).
+
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
 import argparse
@@ -130,7 +139,7 @@ def step_colour(args):
     import torch
     sys.path.insert(0, ROOT)
     from fusiondepth_amd import functional as FD
-    n = BATCH * FRAMES
+    n = args.items * FRAMES
     frames = torch.from_numpy(np.stack([frame(i % 6) for i in range(n)])).cuda()
     flip = [bool((i // 2) % 2) for i in range(n)]
     jitter = [JITTER if i % 2 else None for i in range(n)]
@@ -148,10 +157,10 @@ def step_colour(args):
     ms = float(np.median(times))
     comp, moved = colour_traffic(n)
     say("[1] colour path, batch %d (%d frames %dx%d -> %dx%d, %d scales, half jittered): %.3f ms / batch (median of %d, min %.3f, max %.3f; "
-        "device events, includes the two small table uploads)" % (BATCH, n, W0, H0, WIDTH, HEIGHT, SCALES, ms, len(times), min(times), max(times)))
+        "device events, includes the two small table uploads)" % (args.items, n, W0, H0, WIDTH, HEIGHT, SCALES, ms, len(times), min(times), max(times)))
     say("    10 launches; compulsory traffic %.1f MB = %.1f us at 6.3 TB/s; the passes move %.1f MB -> %.2f TB/s achieved; %.1fx the bound"
         % (comp / 1e6, 1e6 * comp / HBM_BPS, moved / 1e6, moved / (ms * 1e-3) / 1e12, ms * 1e-3 / (comp / HBM_BPS)))
-    say(json.dumps({"colour_ms_per_batch": ms}))
+    say(json.dumps({"colour_ms_per_batch": ms, "batch": args.items}))
 
 
 def step_trace_report(args):
@@ -567,6 +576,169 @@ def step_offline(args):
             "incl. process start" % (WORKERS, float(np.median([c[0] for c in cpu])), " ".join("%.0f" % c[0] for c in cpu),
                                      float(np.median([c[1] for c in cpu]))))
 
+# ---------------------------------------------------------------------------------------------------- 9 / 10. the Refiner's loader
+GDC_BATCH = 6
+
+
+def step_inf_gdc_key(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import functional as FD
+    B = GDC_BATCH
+    rng = np.random.default_rng(3)
+    descs = [(k * H0 * W0, H0, W0, bool(k % 2)) for k in range(B)]
+    table = np.frombuffer(FD.resize_desc_table(descs), dtype=np.uint8)
+    base = (table.size + 15) // 16 * 16
+    staging = torch.empty((base + 4 * B * H0 * W0,), dtype=torch.uint8, pin_memory=True)
+    staging.numpy()[:table.size] = table
+    staging.numpy()[base:].view(np.float32)[:] = rng.uniform(0.05, 80.0, B * H0 * W0).astype(np.float32)
+    dev = staging.cuda()
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times.append(a.elapsed_time(b))
+        return float(np.median(times)), min(times), max(times)
+
+    read, write = 4 * B * H0 * W0, 4 * B * HEIGHT * WIDTH
+    say("[9] inf_gdc key, batch %d, %dx%d -> %dx%d, device events, median of %d (min, max)" % (B, W0, H0, WIDTH, HEIGHT, args.iters))
+    up = timed(lambda: staging.to("cuda", non_blocking=True))
+    say("    upload of the batch's pinned staging buffer (%.1f MB, one copy): %.3f ms (%.3f, %.3f) = %.1f GB/s"
+        % (staging.numel() / 1e6, up[0], up[1], up[2], staging.numel() / (up[0] * 1e-3) / 1e9))
+    ms = timed(lambda: FD.resize_bilinear_batch(dev[base:].view(torch.float32), descs, (HEIGHT, WIDTH), desc_table=dev[:table.size]))
+    comp = read + write
+    say("    fd_resize_bilinear_batch (1 launch; the output allocation included): %.3f ms (%.3f, %.3f); compulsory traffic read %.1f MB + "
+        "write %.1f MB = %.2f us at 8 TB/s -> %.1fx the bound, %.2f TB/s"
+        % (ms[0], ms[1], ms[2], read / 1e6, write / 1e6, 1e6 * comp / PEAK_BPS, ms[0] * 1e-3 / (comp / PEAK_BPS), comp / (ms[0] * 1e-3) / 1e12))
+    say(json.dumps({"gdc_key_ms_per_batch": up[0] + ms[0], "batch": B}))
+
+
+def step_gdc_trace_report(args):
+    """The kernel's own time from the rocprofv3 results database of a traced ``inf_gdc_key`` run."""
+    import sqlite3
+    files = sorted(glob.glob(os.path.join(args.trace_dir, "**", "*_results.db"), recursive=True))
+    if not files:
+        sys.exit("no rocprofv3 results database under %s" % args.trace_dir)
+    db = sqlite3.connect(files[-1])
+    rows = list(db.execute("select count(*), avg(end-start)/1e3, min(end-start)/1e3, max(end-start)/1e3 from kernels where name like "
+                           "'%k_resize_bilinear_batch%'"))
+    n, avg, lo, hi = rows[0]
+    if not n:
+        sys.exit("k_resize_bilinear_batch is not in the trace")
+    comp = 4 * GDC_BATCH * (H0 * W0 + HEIGHT * WIDTH)
+    say("    rocprofv3 --kernel-trace --stats (a run of its own), k_resize_bilinear_batch, %d launches: avg %.2f us (min %.2f, max %.2f) = %.1fx the "
+        "%.2f us traffic bound, %.2f TB/s (bound by HBM bytes; the arithmetic is 13 float operations per output pixel)"
+        % (n, avg, lo, hi, avg * 1e-6 / (comp / PEAK_BPS), 1e6 * comp / PEAK_BPS, comp / (avg * 1e-6) / 1e12))
+
+
+def step_refiner_trainer(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.datasets import KITTIRefinerBatches
+    from fusiondepth_amd.options import MonodepthOptions
+    from fusiondepth_amd.refiner import Refiner
+    from fusiondepth_amd.trainer import Trainer
+    torch.manual_seed(1)
+    with tempfile.TemporaryDirectory() as root:
+        lines, _ = write_tree(root, 50, (".png",))
+        rng = np.random.default_rng(9)
+        for line in lines:
+            folder, frame, side = line.split()
+            os.makedirs(os.path.join(root, folder, "inf_gdc_4beam"), exist_ok=True)
+            np.save(os.path.join(root, folder, "inf_gdc_4beam", "%d_%s.npy" % (int(frame), side)), rng.uniform(0.05, 80.0, (H0, W0)).astype(np.float32))
+        base = ["--num_layers", "18", "--weights_init", "scratch", "--batch_size", str(BATCH), "--height", str(HEIGHT), "--width", str(WIDTH)]
+        tr = Trainer(MonodepthOptions().parse(base + ["--log_dir", os.path.join(root, "log"), "--model_name", "stage1"]), verbose=False)
+        weights = tr.save_model("stage1")
+        del tr
+        rf = Refiner(MonodepthOptions().parse(base + ["--refine_load_weights_folder", weights]), verbose=False)
+        B = rf.batch_size
+        b = KITTIRefinerBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".png", opt=rf.opt, batch_size=B, shuffle=True,
+                                seed=1, workers=WORKERS, loader=_cached_loader())
+
+        def endless():
+            while True:
+                for batch in b:
+                    yield batch
+        real = endless()
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(5)
+        pool = []
+        for i in range(3):
+            inp = synthetic.make_batch(B, HEIGHT, WIDTH, seed=77 + i)
+            inp["inf_gdc"] = torch.empty(B, 1, HEIGHT, WIDTH, device="cuda").uniform_(0.05, 1.5, generator=gen)
+            pool.append(inp)
+        k = [0]
+        cur = [next(real)]
+
+        def step_syn():                                            # bench.py's refiner configuration: the next batch is announced
+            k[0] += 1
+            rf.train_step(pool[k[0] % 3], pool[(k[0] + 1) % 3])
+
+        def step_real():                                           # Refiner.run_epoch reads one batch ahead in the same way
+            nxt = next(real)
+            rf.train_step(cur[0], nxt)
+            cur[0] = nxt
+
+        def window(fn, n):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n
+
+        for _ in range(4):
+            step_syn()
+            step_real()
+        res = {"builder": [], "synthetic": []}
+        for _ in range(args.windows):
+            res["synthetic"].append(window(step_syn, args.steps))
+            res["builder"].append(window(step_real, args.steps))
+        b.close()
+        syn, rl = float(np.median(res["synthetic"])), float(np.median(res["builder"]))
+        say("[10] Refiner (ResNet-18, %dx%d, --batch_size %d = %d images / step), %d alternating windows of %d steps:" % (WIDTH, HEIGHT, BATCH, B,
+                                                                                                                        args.windows, args.steps))
+        say("    fed synthetic batches (bench.py's refiner configuration): %.1f images/s (%.2f ms / step; windows %s)"
+            % (B / syn, 1e3 * syn, " ".join("%.2f" % (1e3 * v) for v in res["synthetic"])))
+        say("    fed by KITTIRefinerBatches (pre-decoded frames, inf_gdc maps from .npy files): %.1f images/s (%.2f ms / step; windows %s)"
+            % (B / rl, 1e3 * rl, " ".join("%.2f" % (1e3 * v) for v in res["builder"])))
+        if args.colour_ms > 0 or args.gdc_ms > 0:
+            if B != GDC_BATCH:
+                sys.exit("steps 1 and 9 were measured at batch %d, the Refiner's batch is %d" % (GDC_BATCH, B))
+            dev_ms = args.colour_ms + args.gdc_ms
+            share = dev_ms / (1e3 * syn)
+            say("    condition: colour path %.3f ms + inf_gdc key (upload + library call) %.3f ms, both measured at batch %d = %.3f ms = %.1f %% of "
+                "the synthetic-fed Refiner step (%.2f ms): %s the 10 %% limit.  As in step 4, file mode's LiDAR keys (per-item scan uploads, "
+                "rasterisation and scatter launches) are NOT in this sum: the figure is the builder's colour path and the new key, not all "
+                "of its device work" % (args.colour_ms, args.gdc_ms, B, dev_ms, 100 * share, 1e3 * syn, "within" if share <= 0.10 else "ABOVE"))
+
+
+def drive_refiner(args):
+    out = os.path.abspath(args.out)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    scratch = tempfile.mkdtemp(prefix="bench_loader_")
+    me = "%s %s" % (sys.executable, os.path.abspath(__file__))
+    last = "$(tail -1 %s | python -c 'import json,sys; print(json.load(sys.stdin)[\"%s\"])')"
+    colour_json, gdc_json = os.path.join(scratch, "colour.json"), os.path.join(scratch, "gdc.json")
+    trace_dir = os.path.join(scratch, "trace")
+    steps = ["timeout -k 10 240 %s --step colour --iters 30 --items %d | tee %s" % (me, GDC_BATCH, colour_json),
+             "timeout -k 10 240 %s --step inf_gdc_key --iters 30 | tee %s" % (me, gdc_json),
+             "timeout -k 10 300 rocprofv3 --kernel-trace --stats -d %s -- %s --step inf_gdc_key --iters 10 > /dev/null 2>&1" % (trace_dir, me),
+             "%s --step gdc_trace_report --trace_dir %s" % (me, trace_dir),
+             "timeout -k 10 540 %s --step refiner_trainer --colour_ms %s --gdc_ms %s"
+             % (me, last % (colour_json, "colour_ms_per_batch"), last % (gdc_json, "gdc_key_ms_per_batch"))]
+    cmd = "set -o pipefail; (" + " && ".join(steps) + ") 2>&1 | grep --line-buffered -v '^{' | tee -a %s" % out
+    sys.exit(subprocess.call(["bash", "-c", cmd], cwd=ROOT))
+
 
 def drive_raw(args):
     out = os.path.abspath(args.out)
@@ -603,7 +775,8 @@ def drive(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
-                                                      "raw_builder", "raw_trainer", "offline", "offline_worker"])
+                                                      "raw_builder", "raw_trainer", "offline", "offline_worker", "refiner", "inf_gdc_key", "gdc_trace_report",
+                                                      "refiner_trainer"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default="")
     ap.add_argument("--split_file", default="")
@@ -613,13 +786,16 @@ def main():
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--colour_ms", type=float, default=0.0)
+    ap.add_argument("--gdc_ms", type=float, default=0.0)
     ap.add_argument("--trace_dir", default="")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "sparsify_time.log" if args.step == "raw" else "loader_time.log")
-    {"raw": drive_raw, "sparsify": step_sparsify, "raw_builder": step_raw_builder, "raw_trainer": step_raw_trainer, "offline": step_offline,
-     "offline_worker": step_offline_worker, "all": drive, "colour": step_colour, "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker,
-     "builder": step_builder, "trainer": step_trainer}[args.step](args)
+    {"refiner": drive_refiner, "inf_gdc_key": step_inf_gdc_key, "gdc_trace_report": step_gdc_trace_report,
+     "refiner_trainer": step_refiner_trainer, "raw": drive_raw, "sparsify": step_sparsify, "raw_builder": step_raw_builder,
+     "raw_trainer": step_raw_trainer, "offline": step_offline, "offline_worker": step_offline_worker, "all": drive, "colour": step_colour,
+     "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker, "builder": step_builder,
+     "trainer": step_trainer}[args.step](args)
 
 
 if __name__ == "__main__":
