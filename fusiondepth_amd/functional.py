@@ -12,6 +12,9 @@ import torch
 from . import _lib
 from . import tuning
 from ._lib import call, f32, ptr, query, stream
+from .weight_layouts import (build_weight_plan, bump_weights_epoch, enable_weight_cache, evict_dead_weight_layouts,  # noqa: F401
+                             frozen_epoch, invalidate_frozen_layouts, refresh_weight_layouts, release_retired_layouts,
+                             sync_late_layouts, unfreeze, weight_layout, weight_plan_needs_rebuild)
 
 PROJECT_EPS = 1e-7
 
@@ -798,131 +801,13 @@ def _conv_out_hw(d):
     return (d.H + 2 * d.pad - d.KH) // d.stride + 1, (d.W + 2 * d.pad - d.KW) // d.stride + 1
 
 
-# Cache of kernel-side weight layouts for parameters whose owner opted in (``enable_weight_cache``; the Trainer does).
-# A layout is re-derived when the parameter was modified through torch (``_version``) or by the fused Adam kernel
-# (``_WEIGHTS_EPOCH``, bumped by adam_step*), i.e. once per optimiser step instead of once per launch (the six ResNet
-# passes of the two micro-batches reuse the same weights).  Tensors that did not opt in are re-laid-out on every call.
-_WEIGHTS_EPOCH = [0]
-_WT_CACHE = {}            # (cache id, kind, layout floats) -> [stamp, layout buffer, conv descriptor, weakref(parameter)]
-_WT_RETIRED = []          # replaced layout buffers / job tables: a captured hipGraph may still hold their raw pointers
-_NEXT_CACHE_ID = [1]
-
-
-def _drop_plan():
-    if _WT_PLAN[0] is not None:
-        _WT_RETIRED.extend(part[0] for part in _WT_PLAN[0] if part is not None)
-        _WT_PLAN[0] = None
-    _sync_late_layouts(host=True)
-
-
-# The re-layout launch that follows the Adam kernel is pure HBM traffic (~0.5 GB: every 3x3 weight in its forward and its
-# data-gradient layout, the F(2x2, 3x3) ones at 16 floats per tap) with nothing to overlap it on the stream that just finished the
-# step.  Only the small forward layouts of the first layers are needed at once; everything else ("late": data-gradient layouts,
-# forward layouts from 1 MB up = ResNet layer3 / layer4 and the decoder's deep blocks) is refreshed on a side stream while the next
-# step's stems and first blocks run, and a stream that is about to USE a late layout waits for that launch first
-# (``_weight_layout``), as does the next optimiser step before it changes the weights again.  tuning.host.late_relayout = False: one launch.
-_LATE_MIN_FLOATS = 1 << 18
-_LATE = {"event": None, "waited": set(), "stream": None}
-
-
-def _late_relayout_on():
-    return tuning.host.late_relayout and not torch.cuda.is_current_stream_capturing()
-
-
-def _wait_late_layouts():
-    """Order the current stream behind the pending side-stream re-layout (once per stream and optimiser step)."""
-    ev = _LATE["event"]
-    if ev is None:
-        return
-    sid = stream()
-    if sid not in _LATE["waited"]:
-        torch.cuda.current_stream().wait_event(ev)
-        _LATE["waited"].add(sid)
-
-
-def sync_late_layouts():
-    """Order the current stream behind a pending side-stream re-layout and forget it (call before capturing a hipGraph, before
-    touching the cached layouts from outside)."""
-    _sync_late_layouts()
-
-
-def _sync_late_layouts(host=False):
-    """Forget the pending late re-layout after ordering the current stream behind it.  ``host``: wait on the host instead - for
-    callers in the middle of a step (a new layout shape dropped the plan), where other streams may be about to use a late layout
-    without passing through the current stream first."""
-    if _LATE["event"] is not None:
-        if host and not torch.cuda.is_current_stream_capturing():
-            _LATE["event"].synchronize()
-        torch.cuda.current_stream().wait_event(_LATE["event"])
-        _LATE["event"] = None
-        _LATE["waited"] = set()
-
-
-def evict_dead_weight_layouts():
-    """Forget the layouts of parameters that no longer exist (a Trainer that was deleted): their buffers move to the retired
-    list instead of being freed at once, because a hipGraph captured by that Trainer may still reference them; returns the
-    number of entries dropped.  ``release_retired_layouts()`` frees the list once no such graph can be replayed any more."""
-    dead = [k for k, e in _WT_CACHE.items() if e[3]() is None]
-    for k in dead:
-        _WT_RETIRED.append(_WT_CACHE.pop(k)[1])
-    if dead:
-        _drop_plan()
-    return len(dead)
-
-
-def release_retired_layouts():
-    n = len(_WT_RETIRED)
-    _WT_RETIRED.clear()
-    return n
-
-
-def bump_weights_epoch():
-    _WEIGHTS_EPOCH[0] += 1
-
-
-_FROZEN_EPOCH = [0]
-
-
-def invalidate_frozen_layouts():
-    """Frozen weights' layouts ignore the per-optimiser-step epoch; their stamp is (``_version``, this epoch, ``data_ptr``).  A write that
-    torch's version counter does not see - ``p.data.copy_``, a broadcast into ``p.data``, a raw kernel - must be followed by this call
-    (``Refiner._load_pretrained``, ``Trainer.load_model`` and ``dp.broadcast_module_state`` do it): every frozen layout is re-derived
-    at its next use."""
-    _FROZEN_EPOCH[0] += 1
-
-
-def enable_weight_cache(params, frozen=False):
-    """``frozen``: weights that no optimiser touches (the Refiner's stage-1 networks).  Their layouts are derived once and stay valid
-    across optimiser steps (the epoch stamp that invalidates trained weights' layouts after every Adam launch is ignored; an in-place
-    change through torch - ``load_state_dict`` - still bumps ``_version``), and they stay out of the post-Adam refresh launch.
-    Round 4 re-laid them out on EVERY call: 100 launches per Refiner step."""
-    for p in params:
-        if p.dim() == 4 and not hasattr(p, "_fd_cache_id"):
-            p._fd_cache_id = _NEXT_CACHE_ID[0]
-            _NEXT_CACHE_ID[0] += 1
-        if p.dim() == 4:
-            if frozen:
-                p._fd_frozen = True
-            elif getattr(p, "_fd_frozen", False):          # a formerly frozen parameter that is trained now: back under the optimiser epoch
-                p._fd_frozen = False
-                _drop_plan()
-
-
-def _layout_stamp(w):
-    if getattr(w, "_fd_frozen", False):
-        return (w._version, -1 - _FROZEN_EPOCH[0], w.data_ptr())
-    return (w._version, _WEIGHTS_EPOCH[0], w.data_ptr())
-
-
 def enable_direct_grad(params):
     """Opt-in: weight / bias / BatchNorm-affine gradients are accumulated by the backward kernels straight into the
     pre-allocated ``param.grad`` (a view of the trainer's flat gradient buffer) instead of being returned to autograd,
     which would launch one ATen add per parameter per micro-batch (~600 tiny kernels per optimiser step)."""
     for p in params:
         p._fd_direct_grad = True
-        if getattr(p, "_fd_frozen", False):                # it gets gradients, so something will change it
-            p._fd_frozen = False
-            _drop_plan()
+        unfreeze(p)                                        # it gets gradients, so something will change it
 
 
 # ---- "this parameter's gradient is complete" notifications ------------------------------------------------------------------
@@ -986,134 +871,6 @@ def _direct_grad_target(p):
     if p is not None and getattr(p, "_fd_direct_grad", False) and p.grad is not None and p.grad.is_contiguous():
         return p.grad
     return None
-
-
-def _weight_layout(w, cache_id, kind, nfloats, desc=None):
-    """-> (buffer, ready flag) for weight ``w`` and layout ``kind`` ('f' forward, 'd' data-gradient)."""
-    if cache_id is None:
-        return torch.empty((nfloats,), device=w.device, dtype=torch.float32), 0
-    # nfloats is part of the key: the layout FORMAT of a weight depends on the kernel family its input shape is routed to (12 or 16
-    # floats per tap: conv_wino.hip::wino_fwd_mode looks at N*H*W), so a weight used at two batch sizes (the stacked training batch and
-    # a smaller validation batch) keeps both layouts resident instead of rebuilding one over the other on every switch (ADVICE round 4)
-    key = (cache_id, kind, nfloats)
-    stamp = _layout_stamp(w)
-    ent = _WT_CACHE.get(key)
-    if _lib.RECORDER[0] is not None:
-        _lib.RECORDER[0].side("layout", (w, key))
-    if ent is not None:
-        if _LATE["event"] is not None and ent[4]:
-            _wait_late_layouts()
-        if ent[6] and not getattr(w, "_fd_frozen", False) and _WEIGHTS_EPOCH[0] - ent[5] > _PLAN_IDLE_STEPS:
-            _drop_plan()                # it left the per-step refresh while idle and is in use again: let the next plan include it
-        ent[5] = _WEIGHTS_EPOCH[0]
-        if ent[0] == stamp:
-            return ent[1], 1
-        ent[0] = stamp
-        return ent[1], 0
-    buf = torch.empty((nfloats,), device=w.device, dtype=torch.float32)
-    # [stamp, layout buffer, conv descriptor, weakref(parameter), refreshed on the side stream, epoch of the last use, left out of the plan]
-    _WT_CACHE[key] = [stamp, buf, desc, weakref.ref(w), False, _WEIGHTS_EPOCH[0], False]
-    if not getattr(w, "_fd_frozen", False):
-        _drop_plan()                    # a layout the plan does not know: fall back to per-call re-layout until rebuilt
-    return buf, 0
-
-
-# One-launch refresh of every cached layout (fd_relayout_batch): built once the cache is populated (after the first full
-# forward + backward), run by adam_step* right after the weights change.
-# A trained weight keeps one layout per input shape it was used at (the stacked training batch AND the validation batch: the format
-# depends on the kernel family).  A layout that no convolution has used for _PLAN_IDLE_STEPS optimiser steps stays OUT of the per-step
-# refresh - it is re-derived lazily by its next user through the stamp mismatch, which also drops the plan so that the layout is
-# refreshed with the others again while it stays in use (a validation pass of several batches: one rebuild, then one launch per step) -
-# and after _RETIRE_IDLE_STEPS its buffer is released (ADVICE round 5: a rare shape no longer costs traffic and memory on every step).
-_WT_PLAN = [None]
-_PLAN_IDLE_STEPS = 8
-_RETIRE_IDLE_STEPS = 512
-
-
-def build_weight_plan():
-    """Collect the re-layout jobs of every cached weight layout into a device table; returns the number of jobs."""
-    from ._lib import RelayoutJob
-    evict_dead_weight_layouts()
-    _PLAN_STALE[0] = False
-    now = _WEIGHTS_EPOCH[0]
-    for k in [k for k, e in _WT_CACHE.items() if now - e[5] > _RETIRE_IDLE_STEPS and not getattr(e[3](), "_fd_frozen", False)]:
-        _WT_RETIRED.append(_WT_CACHE.pop(k)[1])
-    ents = []
-    for k, e in _WT_CACHE.items():
-        if e[2] is None or getattr(e[3](), "_fd_frozen", False):
-            continue
-        e[6] = now - e[5] > _PLAN_IDLE_STEPS
-        if not e[6]:
-            ents.append((k, e))
-    if not ents:
-        _drop_plan()
-        return 0
-    def table(part):
-        if not part:
-            return None, 0
-        jobs = (RelayoutJob * (4 * len(part)))()
-        n = 0
-        for (cid, kind, _nf), e in part:
-            n += query("fd_conv2d_relayout_jobs", ctypes.addressof(e[2]), 0 if kind == "f" else 1, ptr(e[3]()), ptr(e[1]),
-                       ctypes.addressof(jobs) + n * ctypes.sizeof(RelayoutJob))
-        if n == 0:
-            return None, 0
-        blocks = query("fd_relayout_plan", ctypes.addressof(jobs), n)
-        raw = bytes(memoryview(jobs))[: n * ctypes.sizeof(RelayoutJob)]
-        dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(part[0][1][1].device)
-        return (dev, n, blocks, [k for k, _ in part]), n
-    is_late = lambda k, e: k[1] != "f" or e[1].numel() >= _LATE_MIN_FLOATS
-    for k, e in ents:
-        e[4] = bool(is_late(k, e))
-    early, n_early = table([(k, e) for k, e in ents if not e[4]])
-    late, n_late = table([(k, e) for k, e in ents if e[4]])
-    _drop_plan()
-    if n_early + n_late == 0:
-        return 0
-    _WT_PLAN[0] = (early, late)
-    return n_early + n_late
-
-
-def refresh_weight_layouts():
-    """Re-derive every planned layout from the current weights (one launch) and mark them valid for this epoch."""
-    plan = _WT_PLAN[0]
-    if plan is None:
-        return False
-    early, late = plan
-    _sync_late_layouts()                       # (a refresh without an optimiser step in between: never two in flight)
-    for part in (early, late):
-        if part is None:
-            continue
-        dev, n, blocks, keys = part
-        if part is late and _late_relayout_on():
-            cur = torch.cuda.current_stream()
-            if _LATE["stream"] is None:
-                _LATE["stream"] = torch.cuda.Stream()
-            side = _LATE["stream"]
-            side.wait_stream(cur)              # behind the Adam kernel (and everything that read the old layouts)
-            with torch.cuda.stream(side):
-                call("fd_relayout_batch", ptr(dev), n, blocks, stream())
-                ev = torch.cuda.Event()
-                ev.record(side)
-            _LATE["event"], _LATE["waited"] = ev, set()
-        else:
-            call("fd_relayout_batch", ptr(dev), n, blocks, stream())
-        for k in keys:
-            e = _WT_CACHE[k]
-            w = e[3]()
-            if w is not None:
-                e[0] = _layout_stamp(w)
-            if _WEIGHTS_EPOCH[0] - e[5] > _PLAN_IDLE_STEPS:
-                _PLAN_STALE[0] = True          # refreshed, but nobody has read it for a while: the owner rebuilds the plan without it
-    return True
-
-
-_PLAN_STALE = [False]
-
-
-def weight_plan_needs_rebuild():
-    """No plan yet, or the plan carries layouts that have gone idle (``_PLAN_IDLE_STEPS``): ``build_weight_plan`` leaves those out."""
-    return _WT_PLAN[0] is None or _PLAN_STALE[0]
 
 
 # Shape-keyed plans: the descriptor of a convolution and the workspace / layout sizes the library reports for it depend only on
@@ -1196,7 +953,7 @@ def _conv_forward(ctx, x, w, bias, stride, pad, pad_mode, act, in_norm, want_sta
     y = _empty((d.N, d.Cout, Ho, Wo), x)
     _tally(d, Ho, Wo)
     ws = _empty((nws,), x) if nws > 0 else None
-    wt, ready = _weight_layout(w, cache_id, "f", nwt, d) if nwt > 0 else (None, 0)
+    wt, ready = weight_layout(w, cache_id, "f", nwt, d) if nwt > 0 else (None, 0)
     part = None
     # a view off a 16-byte boundary: some statistics epilogues need an aligned input, so BatchNorm makes its own pass instead
     if want_stats and plan.stat_slots > 0 and x.data_ptr() % 16 == 0:
@@ -1235,7 +992,7 @@ def _conv_backward(ctx, gy, gx_add=None):
         gx = torch.empty_like(x)
         n_ws, n_wt = plan.data_sizes()
         ws = _empty((n_ws,), x)
-        wt, ready = _weight_layout(w, ctx.cache_id, "d", n_wt, d)
+        wt, ready = weight_layout(w, ctx.cache_id, "d", n_wt, d)
         if in_act:
             # x is an activation output consumed by this layer alone: hand its producer the gradient w.r.t. the PRE-activation
             call("fd_conv2d_bwd_data_inact", dp, ptr(gy), ptr(w), ptr(x), in_act, ptr(gx), ptr(wt), ready, ptr(ws), stream())
@@ -1557,7 +1314,7 @@ def _conv_bn_fused_forward(c, b, x, w, bn_w, bn_b, residual, running_mean, runni
     out = torch.empty_like(y)
     _tally(d, plan.Ho, plan.Wo)
     ws = _empty((nws,), xf)
-    wt, ready = _weight_layout(wf, cache_id, "f", nwt, d)
+    wt, ready = weight_layout(wf, cache_id, "f", nwt, d)
     res = f32(residual) if residual is not None else None
     C = d.Cout
     mean, invstd = _empty((groups * C,), xf), _empty((groups * C,), xf)
@@ -1625,7 +1382,7 @@ def conv_bn_frozen(x, conv_weight, bn, stride=1, pad=0, relu=False):
     of k_bn_apply_eval), ReLU in the convolution's epilogue - the pass over the activation that applied them is gone.  The folded pair
     is derived once and kept until the weights / statistics change (their version counters, ``invalidate_frozen_layouts``).  The
     result differs from the two-launch form by the rounding of w * a (one ulp per weight)."""
-    stamp = (conv_weight._version, _FROZEN_EPOCH[0], conv_weight.data_ptr(), bn.weight._version, bn.bias._version,
+    stamp = (conv_weight._version, frozen_epoch(), conv_weight.data_ptr(), bn.weight._version, bn.bias._version,
              bn.running_mean._version, bn.running_var._version)
     ent = _FOLDED.get(id(conv_weight))
     if ent is None or ent[0] != stamp or ent[1]() is not conv_weight:
@@ -2004,7 +1761,7 @@ def depth_errors(gt, pred):
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
     """One torch.optim.Adam update of a flat fp32 tensor, in place."""
     bc1, bc2 = 1.0 - betas[0] ** step, 1.0 - betas[1] ** step
-    _sync_late_layouts()
+    sync_late_layouts()
     bump_weights_epoch()
     call("fd_adam_step", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr), betas[0],
          betas[1], float(eps), bc1, bc2, float(grad_scale), stream())
@@ -2013,7 +1770,7 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
 
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
     """Adam update whose step counter / lr live in ``state`` (device, [step, lr]) — hipGraph-replay safe."""
-    _sync_late_layouts()
+    sync_late_layouts()
     bump_weights_epoch()
     call("fd_adam_step_dev", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(state), betas[0],
          betas[1], float(eps), float(grad_scale), stream())

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from .. import functional as FD
 from .. import tuning
+from .. import weight_layouts
 
 _SPEC = {18: ("basic", [2, 2, 2, 2]), 34: ("basic", [3, 4, 6, 3]), 50: ("bottleneck", [3, 4, 6, 3]),
          101: ("bottleneck", [3, 4, 23, 3]), 152: ("bottleneck", [3, 8, 36, 3])}
@@ -34,7 +35,7 @@ def _conv_bn(x, conv, bn, residual=None, relu=False, tap=False):
         out = FD.batch_norm(y, bn, residual=residual, relu=relu, conv_stats=stats)
         return (out, res[2]) if tap else out
     if (not bn.training and residual is None and conv.bias is None and tuning.host.fold_frozen_bn and not torch.is_grad_enabled()
-            and getattr(conv.weight, "_fd_frozen", False) and bn.weight is not None):
+            and weight_layouts.is_frozen(conv.weight) and bn.weight is not None):
         y = FD.conv_bn_frozen(x, conv.weight, bn, stride=conv.stride[0], pad=conv.padding[0], relu=relu)   # frozen network: BN folded
         return (y, x) if tap else y
     if tap:

@@ -14,6 +14,7 @@ import torch
 
 from . import functional as FD
 from . import networks
+from . import weight_layouts
 
 PREDICTOR_MODELS = ("encoder", "beam_encoder", "depth")
 
@@ -60,8 +61,7 @@ class Predictor:
                 for k, v in loaded.items():
                     if k in own:
                         own[k].copy_(v)
-        FD.bump_weights_epoch()
-        FD.invalidate_frozen_layouts()
+        weight_layouts.weights_replaced()
 
     def _run_module(self, name, *tensors):
         """``Refiner._run_module``: recorded once per input signature, replayed afterwards.  ``depth`` takes the encoder features

@@ -23,6 +23,7 @@ from . import dp
 from . import functional as FD
 from . import tuning
 from . import networks
+from . import weight_layouts
 from .layers import disp_to_depth
 from .trainer import Outputs, Trainer, derived_hparams
 
@@ -162,8 +163,7 @@ class Refiner(Trainer):
                 for k, v in loaded.items():
                     if k in own:
                         own[k].copy_(v)
-        FD.bump_weights_epoch()
-        FD.invalidate_frozen_layouts()
+        weight_layouts.weights_replaced()
 
     def set_train(self):
         """refiner.py:80-160: the depth / pose networks stay in eval mode; only the refine decoder trains."""

@@ -24,6 +24,7 @@ from torch.utils import _pytree
 
 from . import _lib
 from . import tuning
+from . import weight_layouts
 
 MAX_ARGS = 24
 
@@ -220,10 +221,9 @@ class Replayable:
         self.plans, self.seen, self.disabled = {}, {}, None
 
     def _fingerprint(self, frozen_only=True):
-        from . import functional as FD
         # trained weights inside the region: their layouts are refreshed once per optimiser step behind events this replay does not
         # see - such a plan is only good until the next optimiser step (i.e. useless, but never wrong)
-        return (tuning.generation(), FD._FROZEN_EPOCH[0], 0 if frozen_only else FD._WEIGHTS_EPOCH[0])
+        return (tuning.generation(),) + weight_layouts.epoch_fingerprint(frozen_only)
 
     def __call__(self, *inputs):
         if self.disabled is not None or not tuning.host.replay_frozen or torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
@@ -267,7 +267,7 @@ class Replayable:
             if not all(t is None or torch.is_tensor(t) for t in flat):
                 raise NotRecordable("the region returns non-tensor leaves")
             persistent = [t for t in self.persistent() if torch.is_tensor(t) and t.is_cuda]
-            persistent += [e[1] for e in FD._WT_CACHE.values()] + FD.folded_tensors()
+            persistent += weight_layouts.layout_buffers() + FD.folded_tensors()
             plan = build_plan(rec, list(inputs), flat, tree, persistent, tally)
             again = plan.replay(list(inputs))
             flat2, _ = _pytree.tree_flatten(again)
@@ -283,7 +283,7 @@ class Replayable:
             self.disabled = str(e)
             warnings.warn("fusiondepth_amd.replay: %s stays on the eager path: %s" % (self.name, e))
             return out
-        frozen_only = all(getattr(t, "_fd_frozen", False) or not isinstance(t, torch.nn.Parameter) or t.dim() != 4 for t in self.persistent())
+        frozen_only = all(weight_layouts.is_frozen(t) or not isinstance(t, torch.nn.Parameter) or t.dim() != 4 for t in self.persistent())
         self.plans[key] = (plan, self._fingerprint(frozen_only), [(t.data_ptr(), t._version) for t in plan.keep], frozen_only)
         return out
 
@@ -298,7 +298,7 @@ class _ReplayedNet(torch.autograd.Function):
     def forward(ctx, state, x, anchor):
         from . import functional as FD
         if state.late_f:
-            FD._wait_late_layouts()
+            weight_layouts.wait_late_layouts()
         for kind, payload in state.fwd_effects:
             if kind == "note_use":
                 FD._note_use(*payload)
@@ -321,7 +321,7 @@ class _ReplayedNet(torch.autograd.Function):
         # an output of the pattern without a gradient this time (a loss that skips a scale): zeros give the same sums
         gs = [_lib.f32(gouts[i]) if gouts[i] is not None else torch.zeros(st.out_shapes[i], device=ctx.x.device) for i in st.pattern]
         if st.late_b or st.late_f:
-            FD._wait_late_layouts()
+            weight_layouts.wait_late_layouts()
         out = st.bwd.replay(gs + [ctx.x, ctx.arena])
         ctx.arena = None
         for kind, payload in st.bwd_effects:
@@ -383,11 +383,10 @@ class TrainReplayable:
             return self._record(st, x)
         late_f = late_b = False
         for w, k, ptr_ in st.layouts:                         # every weight layout the recorded calls read must be current
-            ent = FD._WT_CACHE.get(k)
-            if ent is None or ent[0] != FD._layout_stamp(w) or ent[1].data_ptr() != ptr_:
+            late = weight_layouts.use_if_current(k, w, ptr_)
+            if late is None:
                 return self.call(x)                           # (the eager call re-derives it; the plan stays valid for the next step)
-            ent[5] = FD._WEIGHTS_EPOCH[0]
-            if ent[4]:                                        # refreshed on the side stream behind Adam: its readers wait for that launch
+            if late:                                          # refreshed on the side stream behind Adam: its readers wait for that launch
                 if k[1] == "f":
                     late_f = True
                 else:
@@ -430,7 +429,7 @@ class TrainReplayable:
         flat = list(outs)
         persistent = [t for t in self.params + [b for m in self.modules for b in m.buffers()] if t.is_cuda]
         persistent += [p.grad for p in self.params if p.grad is not None]
-        persistent += [e[1] for e in FD._WT_CACHE.values()]
+        persistent += weight_layouts.layout_buffers()
         try:
             fwd = build_plan(rec, [x], flat, None, persistent, 0.0)
         except NotRecordable as e:
@@ -505,9 +504,9 @@ class TrainReplayable:
         for kind, payload in rec.effects + rec2.effects:
             if kind == "layout":
                 w, k = payload
-                ent = FD._WT_CACHE.get(k)
-                if ent is not None:
-                    lay[k] = (w, k, ent[1].data_ptr())
+                buf = weight_layouts.layout_buffer(k)
+                if buf is not None:
+                    lay[k] = (w, k, buf.data_ptr())
         st.layouts = list(lay.values())
         return outs
 

@@ -24,6 +24,7 @@ from . import dp
 from . import functional as FD
 from . import networks
 from . import tuning
+from . import weight_layouts
 from .layers import SSIM, BackprojectDepth, Project3D, disp_to_depth, transformation_from_parameters
 
 MODEL_ORDER = ["encoder", "beam_encoder", "beam_encoder_pose", "depth", "pose_encoder", "pose", "predictive_mask"]
@@ -312,9 +313,7 @@ class Trainer:
         re-layout work into one device job table, so that from now on Adam is followed by ONE re-layout launch instead of
         ~220 small ones spread over the next step.  (Not capturable: call outside graph capture.)"""
         if FD.weight_plan_needs_rebuild():
-            had_plan = FD._WT_PLAN[0] is not None
-            if FD.build_weight_plan() > 0 and not had_plan:
-                FD.refresh_weight_layouts()
+            weight_layouts.rebuild_weight_plan()
 
     def optimizer_step(self, grad_scale=1.0):
         """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel.  The step
@@ -461,7 +460,7 @@ class Trainer:
         if self._graph == "warm":
             with torch.cuda.stream(self._side):
                 self._ensure_weight_plan()     # layouts valid now; inside the graph Adam is followed by the batched refresh
-            if FD._WT_PLAN[0] is None:
+            if not weight_layouts.has_plan():
                 FD.bump_weights_epoch()        # no plan: the captured step must re-derive every weight layout at first use
             FD.sync_late_layouts()             # no event from outside the capture may be waited on inside it
             torch.cuda.synchronize()
@@ -1138,8 +1137,7 @@ class Trainer:
                 for k, v in pretrained.items():
                     if k in model_dict:
                         model_dict[k].copy_(v)              # in place: parameters stay views of the flat buffer
-        FD.bump_weights_epoch()
-        FD.invalidate_frozen_layouts()
+        weight_layouts.weights_replaced()
         FD.refresh_weight_layouts()       # a captured step holds no per-conv re-layout launches: refresh the cached copies now
         adam = os.path.join(folder, "adam.pth")
         if os.path.isfile(adam):

@@ -966,6 +966,70 @@ def test_winograd_routing_forward_and_data_gradient_match_torch(Ci, Co, two_d_mi
     relclose(cpu(gx2), cpu(1.5 * gx), "dx after batched re-layout", rtol=1e-6, arel=1e-6)
 
 
+def test_idle_weight_layout_leaves_the_plan_comes_back_and_is_retired():
+    """The idle policy of weight_layouts: a layout no convolution has used for _PLAN_IDLE_STEPS optimiser steps is left out of the
+    next plan but stays cached, its next user re-derives it through the stamp mismatch (bit-equal to a per-call re-layout) and drops
+    the plan so that it is included again, and after _RETIRE_IDLE_STEPS idle steps its buffer moves to the retired list."""
+    import gc
+    import fusiondepth_amd.functional as FD
+    from fusiondepth_amd import weight_layouts as WL
+    FD.evict_dead_weight_layouts(); FD.release_retired_layouts()
+    torch.manual_seed(6)
+    x = torch.randn(2, 64, 12, 40, device="cuda", requires_grad=True)
+    wa = torch.nn.Parameter(torch.randn(64, 64, 3, 3, device="cuda") * 0.05)
+    wb = torch.nn.Parameter(torch.randn(64, 64, 3, 3, device="cuda") * 0.05)
+    FD.enable_weight_cache([wa, wb])
+    gy = torch.randn(2, 64, 12, 40, device="cuda")
+
+    def run(w):                                 # forward and input gradient: one 'f' and one 'd' layout per weight
+        y = FD.conv2d(x, w, None, 1, 1)
+        return y, torch.autograd.grad(y, x, gy)[0]
+
+    def step(scale):
+        with torch.no_grad():
+            wa.mul_(scale); wb.mul_(scale)
+        FD.bump_weights_epoch()
+        FD.refresh_weight_layouts()
+
+    keys = lambda w: [k for k in WL._entries if k[0] == w._fd_cache_id]
+    # 1. both weights in use: both in the plan
+    run(wa); run(wb)
+    n_all = FD.build_weight_plan()
+    assert n_all >= 4 and WL.has_plan()
+    assert len(keys(wa)) == 2 and len(keys(wb)) == 2
+    # 2. wb idle for more than _PLAN_IDLE_STEPS optimiser steps: the next plan leaves it out, the cache keeps it
+    assert WL._PLAN_IDLE_STEPS == 8
+    for _ in range(WL._PLAN_IDLE_STEPS + 1):
+        step(1.01)
+        run(wa)
+    assert FD.weight_plan_needs_rebuild()
+    n = FD.build_weight_plan()
+    assert 0 < n < n_all, (n, n_all)
+    assert len(keys(wb)) == 2 and all(WL._entries[k].unplanned for k in keys(wb))
+    assert not any(WL._entries[k].unplanned for k in keys(wa))
+    # 3. wb is used again: re-derived by that call from the current weights, and the plan is dropped so that the next one has it
+    step(1.5)
+    assert WL.has_plan()
+    y, gx = run(wb)
+    y0, gx0 = run(wb.detach().clone())          # no cache id: a per-call re-layout
+    assert torch.equal(y, y0) and torch.equal(gx, gx0)
+    assert not WL.has_plan() and FD.weight_plan_needs_rebuild()
+    # 4. wb idle for more than _RETIRE_IDLE_STEPS: its buffers are retired by the next build, wa's stay
+    assert WL._RETIRE_IDLE_STEPS == 512
+    n_retired = len(WL._retired)
+    for _ in range(WL._RETIRE_IDLE_STEPS + 1):
+        FD.bump_weights_epoch()
+    run(wa)
+    assert FD.build_weight_plan() > 0
+    assert not keys(wb) and len(keys(wa)) == 2
+    assert len(WL._retired) >= n_retired + 2
+    assert torch.equal(FD.conv2d(x, wb, None, 1, 1), FD.conv2d(x, wb.detach().clone(), None, 1, 1))
+    torch.cuda.synchronize()
+    del wa, wb, y, gx, y0, gx0
+    gc.collect()
+    FD.evict_dead_weight_layouts(); FD.release_retired_layouts()
+
+
 @pytest.mark.parametrize("two_d", [2, 1, 0])
 @pytest.mark.parametrize("N,Ci,Co,H,W,mode", [
     (2, 272, 128, 24, 80, "reflect"),   # Refiner decoder (channel-padded concatenations): Cin % 32 == 16, 2-D only with two_d = 2

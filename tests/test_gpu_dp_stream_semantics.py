@@ -135,7 +135,7 @@ def test_trainer_under_nccl_stream_semantics_matches_the_single_process_run(monk
 def test_graphed_step_with_an_eager_exchange_behind_it(monkeypatch, fdtune):
     """train_step_graphed with world_size > 1: forward / backward replayed from the hipGraph, all-reduce + Adam + the (late,
     side-stream) re-layout eager behind it - the path ADVICE round 3 found unordered against the next replay."""
-    from fusiondepth_amd import functional as FD
+    from fusiondepth_amd import functional as FD, weight_layouts as WL
     fake = _FakeNccl()
     _patch(monkeypatch, fake)
     solo, _, _ = _run_trainer(1, True, None, fdtune, graphed=True, steps=5)
@@ -144,14 +144,15 @@ def test_graphed_step_with_an_eager_exchange_behind_it(monkeypatch, fdtune):
 
     def held_back():
         # queue ~50 ms in front of the side-stream re-layout this refresh is about to issue
-        if FD._LATE["stream"] is not None and not torch.cuda.is_current_stream_capturing():
-            with torch.cuda.stream(FD._LATE["stream"]):
+        if WL.late_stream() is not None and not torch.cuda.is_current_stream_capturing():
+            with torch.cuda.stream(WL.late_stream()):
                 for _ in range(40):
                     fake.junk @ fake.junk
         r = orig()
-        late.append(FD._LATE["event"] is not None)
+        late.append(WL.late_event() is not None)
         return r
-    monkeypatch.setattr(FD, "refresh_weight_layouts", held_back)
+    monkeypatch.setattr(FD, "refresh_weight_layouts", held_back)          # the refresh behind every Adam launch ...
+    monkeypatch.setattr(WL, "refresh_weight_layouts", held_back)          # ... and the one that follows the first plan
     dp2, _, _ = _run_trainer(2, True, fake, fdtune, graphed=True, steps=5)
     assert sum(late) >= 2, "the side-stream re-layout never ran behind a graph replay"
     assert torch.equal(solo, dp2), "%d entries differ" % int((solo != dp2).sum())

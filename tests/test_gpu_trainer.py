@@ -889,7 +889,7 @@ def test_late_weight_relayout_is_ordered_before_its_readers(fdtune):
     1 MB up) to a side stream and lets every stream that is about to use such a layout wait for it first.  Five optimiser steps with
     that side stream held back by ~50 ms of queued matrix products must leave the parameters bit-identical to the one-launch
     refresh (tuning.host.late_relayout = False): a reader that did not wait would have convolved with the previous step's weights."""
-    from fusiondepth_amd import functional as FD
+    from fusiondepth_amd import functional as FD, weight_layouts as WL
     from fusiondepth_amd.trainer import Trainer
     B, H, W = 2, 64, 96
     batches = []
@@ -906,12 +906,12 @@ def test_late_weight_relayout_is_ordered_before_its_readers(fdtune):
         tr = Trainer(_opts(batch_size=B), verbose=False)
         assert tr.accumulate_step == 1
         for g in batches:
-            if mode == "1" and FD._LATE["stream"] is not None:
-                with torch.cuda.stream(FD._LATE["stream"]):      # queued in front of this step's re-layout launch
+            if mode == "1" and WL.late_stream() is not None:
+                with torch.cuda.stream(WL.late_stream()):        # queued in front of this step's re-layout launch
                     for _ in range(40):
                         junk @ junk
             tr.train_step([g])
-            used += int(mode == "1" and FD._LATE["event"] is not None)
+            used += int(mode == "1" and WL.late_event() is not None)
         torch.cuda.synchronize()
         params[mode] = tr.flat.flat_param.clone()
         FD.sync_late_layouts()
@@ -1229,20 +1229,20 @@ def test_weight_layout_cache_forgets_dead_trainers():
     """the process-global layout cache must not keep the layouts (and re-layout jobs) of a deleted Trainer alive
     for ever, and must not free buffers a captured graph may still read: entries of dead parameters move to a retired list."""
     import gc
-    from fusiondepth_amd import functional as FD, synthetic
+    from fusiondepth_amd import functional as FD, synthetic, weight_layouts as WL
     from fusiondepth_amd.trainer import Trainer
     FD.evict_dead_weight_layouts(); FD.release_retired_layouts()
     tr = Trainer(_opts(), verbose=False)
     mb = [synthetic.make_batch(tr.batch_size, 64, 96, seed=3 + i) for i in range(tr.accumulate_step)]
     tr.train_step(mb); tr.train_step(mb)
     ids = {p._fd_cache_id for p in tr.parameters_to_train if hasattr(p, "_fd_cache_id")}
-    mine = [k for k in FD._WT_CACHE if k[0] in ids]
-    assert len(mine) > 50 and FD._WT_PLAN[0] is not None
+    mine = [k for k in WL._entries if k[0] in ids]
+    assert len(mine) > 50 and WL.has_plan()
     del tr, mb
     gc.collect()
     tr2 = Trainer(_opts(), verbose=False)                 # evicts on construction
-    assert not [k for k in FD._WT_CACHE if k[0] in ids], "layouts of the deleted trainer are still cached"
-    assert FD._WT_PLAN[0] is None and len(FD._WT_RETIRED) >= len(mine)
+    assert not [k for k in WL._entries if k[0] in ids], "layouts of the deleted trainer are still cached"
+    assert not WL.has_plan() and len(WL._retired) >= len(mine)
     mb = [synthetic.make_batch(tr2.batch_size, 64, 96, seed=3 + i) for i in range(tr2.accumulate_step)]
     losses = tr2.train_step(mb)
     assert np.isfinite(float(losses["loss"]))
