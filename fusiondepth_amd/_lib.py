@@ -288,3 +288,13 @@ def f32(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _empty(shape, like, dtype=torch.float32):
+    return torch.empty(shape, device=like.device, dtype=dtype)
+
+
+def _need_cuda(*ts):
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("fusiondepth_amd: tensors must live on the GPU (no CPU fallback); got %s" % t.device)

@@ -10,7 +10,7 @@ What runs where
   * host, on a thread pool of at most 16 workers: ``PIL.Image.open(path).convert("RGB")`` per frame and ``np.fromfile`` per
     LiDAR scan (PIL is imported here, lazily, and nowhere else in the package);
   * device: the frames are uploaded as uint8 and everything after the decoder runs in HIP kernels - the four-level Lanczos
-    pyramid, colour jitter and ``ToTensor`` (``FD.image_pyramid``), the ``4beam`` rasterisation, the ``2channel`` scatter
+    pyramid, colour jitter and ``ToTensor`` (``data_ops.image_pyramid``), the ``4beam`` rasterisation, the ``2channel`` scatter
     (computed online from the beam map: no ``.npy`` files are read) and ``depth_gt``.
   * the builder issues batch i + 1 on its own stream before it hands batch i to the consumer; the hand-over is an event the
     consumer's stream waits on (the pattern of ``refiner.prefetch_frozen``).  All device work is issued from the calling thread.
@@ -60,7 +60,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import functional as FD
+from . import data_ops
 from . import kitti_utils
 from . import sparsify as SP
 from . import synthetic
@@ -141,9 +141,9 @@ class KITTIRAWBatches:
         self.random_sample = max(int(self._opt("random_sample", -1)), 0)
         if line_spec is None and not self.random_sample:
             nbeams = int(self._opt("nbeams", 4))
-            if lidar_source == "raw" and nbeams not in FD.SPARSIFY_LINE_SPEC:
+            if lidar_source == "raw" and nbeams not in data_ops.SPARSIFY_LINE_SPEC:
                 raise ValueError("KITTIRAWBatches: no default row list for nbeams = %d; pass line_spec" % nbeams)
-            line_spec = FD.SPARSIFY_LINE_SPEC.get(nbeams)
+            line_spec = data_ops.SPARSIFY_LINE_SPEC.get(nbeams)
         self.line_spec = None if line_spec is None else [int(r) for r in line_spec]
         self._epoch = 0
         self._pool = None
@@ -289,7 +289,7 @@ class KITTIRAWBatches:
         for it, _, _ in plan["scans"]:
             P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
             descs.append((P, im_h, im_w, it["do_flip"]))
-        table = FD.raster_desc_table(descs)
+        table = data_ops.raster_desc_table(descs)
         host[plan["descs"][0]:plan["descs"][1]] = np.frombuffer(table, dtype=np.uint8)
         base = plan["points"][0]
         plan["futures"] = [pool.submit(_read_into, path, host[base + 16 * int(ends[k]):base + 16 * int(ends[k + 1])])
@@ -338,7 +338,7 @@ class KITTIRAWBatches:
                 for fi, b in members:
                     j = items[b]["jitter"]
                     jitter.append(j[fi] if isinstance(j, list) else j)
-            pyr = FD.image_pyramid(stack, self.height, self.width, self.num_scales, flip, jitter)
+            pyr = data_ops.image_pyramid(stack, self.height, self.width, self.num_scales, flip, jitter)
             if len(groups) == 1:
                 whole = pyr
                 break
@@ -368,12 +368,12 @@ class KITTIRAWBatches:
         zero = 0
         if plan["sparse"]:
             H, W = self.sparsify_grid
-            slab, _ = FD.sparsify_scans(points, H, W, None if self.random_sample else self.line_spec, 1, self.random_sample, None,
+            slab, _ = data_ops.sparsify_scans(points, H, W, None if self.random_sample else self.line_spec, 1, self.random_sample, None,
                                         self.seed, keys, offsets=offsets)
-            beams = FD.velo_rasterize_batch(slab, descs, (2 * self.height, 2 * self.width), desc_table=table).unsqueeze(1)
+            beams = data_ops.velo_rasterize_batch(slab, descs, (2 * self.height, 2 * self.width), desc_table=table).unsqueeze(1)
             zero = self.frame_idxs.index(0) if self.need_2_channel else 0
             if self.need_2_channel:
-                two = FD.scatter_2channel(beams, FD.scaled_roi(self.height, self.width))
+                two = data_ops.scatter_2channel(beams, data_ops.scaled_roi(self.height, self.width))
                 for fi, f in enumerate(self.frame_idxs):
                     batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
             if self.need_4beam:
@@ -382,7 +382,7 @@ class KITTIRAWBatches:
                     batch["2channel"] = two[zero * B:(zero + 1) * B]
         if self.load_depth:                                      # frame 0's scans are B consecutive entries of the same tables
             size = ctypes.sizeof(_lib.RasterDesc)
-            full = FD.velo_rasterize_batch(points, descs[zero * B:(zero + 1) * B], (375, 1242), return_full=True, beam=False,
+            full = data_ops.velo_rasterize_batch(points, descs[zero * B:(zero + 1) * B], (375, 1242), return_full=True, beam=False,
                                            offsets=offsets[zero * B:(zero + 1) * B + 1], n_max=max(plan["lengths"][zero * B:(zero + 1) * B]),
                                            desc_table=table[zero * B * size:(zero + 1) * B * size])
             batch["depth_gt"] = full.float().unsqueeze(1)
@@ -397,13 +397,13 @@ class KITTIRAWBatches:
                 for it in items:
                     P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
                     pts = torch.from_numpy(it["beam_futures"][k].result()).to(self.device, non_blocking=True)
-                    beam = FD.velo_rasterize(pts, P, im_h, im_w, (2 * self.height, 2 * self.width))     # [384, 1280] at 192x640
+                    beam = data_ops.velo_rasterize(pts, P, im_h, im_w, (2 * self.height, 2 * self.width))     # [384, 1280] at 192x640
                     beams.append(torch.flip(beam, dims=[1]) if it["do_flip"] else beam)
             beams = torch.stack(beams).unsqueeze(1).contiguous()
             B = len(items)
             zero = self.frame_idxs.index(0) if self.need_2_channel else 0
             if self.need_2_channel:                              # mono_dataset.py:162-163: one per frame, with or without need_4beam
-                two = FD.scatter_2channel(beams, FD.scaled_roi(self.height, self.width))
+                two = data_ops.scatter_2channel(beams, data_ops.scaled_roi(self.height, self.width))
                 for fi, f in enumerate(self.frame_idxs):
                     batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
             if self.need_4beam:                                  # mono_dataset.py:193-206
@@ -415,7 +415,7 @@ class KITTIRAWBatches:
             for it in items:
                 P, (im_h, im_w) = self._projection(it["date"], SIDE_MAP[it["side"]])
                 pts = torch.from_numpy(it["velo_future"].result()).to(self.device, non_blocking=True)
-                full = FD.velo_rasterize(pts, P, im_h, im_w, (375, 1242), return_full=True, beam=False)
+                full = data_ops.velo_rasterize(pts, P, im_h, im_w, (375, 1242), return_full=True, beam=False)
                 maps.append((torch.flip(full, dims=[1]) if it["do_flip"] else full).float())
             batch["depth_gt"] = torch.stack(maps).unsqueeze(1).contiguous()
 
@@ -544,7 +544,7 @@ class KITTIRefinerBatches(KITTIRAWBatches):
         plan = self._plan_gdc(items)
         staging = torch.empty((plan["bytes"],), dtype=torch.uint8, pin_memory=True)
         host = staging.numpy()
-        host[plan["table"][0]:plan["table"][1]] = np.frombuffer(FD.resize_desc_table(plan["descs"]), dtype=np.uint8)
+        host[plan["table"][0]:plan["table"][1]] = np.frombuffer(data_ops.resize_desc_table(plan["descs"]), dtype=np.uint8)
         planes = host[plan["planes"][0]:plan["planes"][1]].view(np.float32)
         plan["futures"] = [pool.submit(_load_map_into, it["gdc"], planes[at:at + h * w].reshape(h, w))
                            for it, (at, h, w, _) in zip(items, plan["descs"])]
@@ -567,5 +567,5 @@ class KITTIRefinerBatches(KITTIRAWBatches):
             dev = _upload(plan["staging"], self.device)
             table = dev[plan["table"][0]:plan["table"][1]]
             planes = dev[plan["planes"][0]:plan["planes"][1]].view(torch.float32)
-            batch["inf_gdc"] = FD.resize_bilinear_batch(planes, plan["descs"], (self.height, self.width), desc_table=table)
+            batch["inf_gdc"] = data_ops.resize_bilinear_batch(planes, plan["descs"], (self.height, self.width), desc_table=table)
         return batch

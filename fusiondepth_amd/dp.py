@@ -13,6 +13,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import pass_state
+
 
 # ---- host placement -----------------------------------------------------------------------------------------------------------
 # One process per GPU issues ~830 launches per step from Python; the step is within 1.2 - 1.6x of that issue time, so a rank whose
@@ -161,8 +163,7 @@ class FlatParameters:
                 p.grad = self.flat_grad[o:o + n].view(p.shape)
 
     def zero_grad(self):
-        from . import functional as FD
-        FD.join_wgrad_streams()          # side-stream weight gradients still accumulating into the buffer come first
+        pass_state.join_wgrad_streams()          # side-stream weight gradients still accumulating into the buffer come first
         self.flat_grad.zero_()
         for p, o in zip(self.params, self.offsets):     # autograd may have replaced .grad; re-attach the views
             if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * o:
@@ -180,7 +181,7 @@ class GradientSynchronizer:
     the kernel that completes its last gradient has been LAUNCHED: the asynchronous collective is ordered behind that kernel
     through the stream the backward node runs on (RCCL waits on an event of the current stream), so it overlaps with the rest
     of the backward pass that is still being issued.  Two notification paths: autograd's post-accumulate hooks (gradients that
-    autograd produces) and ``functional.add_grad_ready_callback`` (gradients the HIP kernels accumulate in place).  Few large
+    autograd produces) and ``pass_state.add_grad_ready_callback`` (gradients the HIP kernels accumulate in place).  Few large
     messages by design: xGMI is point-to-point, a ring all-reduce is bound by one link (~153 GB/s), not by a switch."""
 
     def __init__(self, flat, world_size, bucket_bytes=25 << 20, group=None, segments=None, overlap=None, never_used=()):
@@ -221,8 +222,7 @@ class GradientSynchronizer:
             for i, p in enumerate(flat.params):
                 if p.requires_grad:
                     p.register_post_accumulate_grad_hook(self._make_hook(i))
-            from . import functional as FD
-            FD.add_grad_ready_callback(self._on_direct_grad)
+            pass_state.add_grad_ready_callback(self._on_direct_grad)
 
     def _arrived(self, i):
         # Two notification paths can report the same parameter: the in-place kernels' callback, and autograd's post-accumulate
@@ -238,16 +238,15 @@ class GradientSynchronizer:
             self.n_overlapped += 1
 
     def _on_direct_grad(self, param):
-        """functional._grad_ready: a kernel that accumulates into ``param.grad`` (a view of the flat buffer) has been launched;
+        """pass_state.grad_ready: a kernel that accumulates into ``param.grad`` (a view of the flat buffer) has been launched;
         the gradient is complete once that has happened as often as the parameter was used in the forward pass."""
         if self.armed:
             i = self.index.get(id(param))
             if i is not None:
-                from . import functional as FD
                 if self.launched[self.param_bucket[i]]:
-                    self.late.append((i, self.done.get(i, 0), FD.param_uses(param)))   # a kernel AFTER its bucket went out
+                    self.late.append((i, self.done.get(i, 0), pass_state.param_uses(param)))   # a kernel AFTER its bucket went out
                 self.done[i] = self.done.get(i, 0) + 1
-                if self.done[i] == FD.param_uses(param):
+                if self.done[i] == pass_state.param_uses(param):
                     self._arrived(i)
 
     def _make_hook(self, i):

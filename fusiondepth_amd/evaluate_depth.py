@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import functional as FD
-from ._lib import call, stream
+from ._lib import _need_cuda, call, stream
 
 MIN_DEPTH = 1e-3          # evaluate_depth.py:28-29
 MAX_DEPTH = 80
@@ -26,7 +26,7 @@ def compute_errors(gt, pred):
 def batch_post_process_disparity(l_disp, r_disp):
     """evaluate_depth.py:62-70: [B,H,W] float32 device tensors -> [B,H,W] float64 device tensor."""
     l_disp, r_disp = FD.f32(l_disp), FD.f32(r_disp)
-    FD._need_cuda(l_disp, r_disp)
+    _need_cuda(l_disp, r_disp)
     assert l_disp.shape == r_disp.shape and l_disp.dim() == 3
     out = torch.empty(l_disp.shape, device=l_disp.device, dtype=torch.float64)
     call("fd_post_process_disparity", l_disp.data_ptr(), r_disp.data_ptr(), out.data_ptr(), l_disp.shape[0], l_disp.shape[1],

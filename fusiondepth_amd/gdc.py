@@ -41,8 +41,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import functional as FD
-from ._lib import call, query, stream
+from ._lib import _need_cuda, call, query, stream
 
 POLL = 32            # CG iterations enqueued between two reads of the solver state
 
@@ -134,7 +133,7 @@ def GDC(pred_depth, gt_depth, calib, k=10, W_tol=1e-5, recon_tol=1e-4, verbose=F
     Returns the corrected [H,W] float32 device tensor, and with ``return_info`` a ``GDCInfo(N_PL, N_L, iterations,
     rel_residual, status)`` (status: "converged", "maxiter" or "failed").  ``maxiter`` defaults to 10 * N_PL (scipy's);
     ``W_tol`` does not enter the closed-form weights (module docstring); ``idx`` only named the reference's debug files."""
-    FD._need_cuda(pred_depth, gt_depth)
+    _need_cuda(pred_depth, gt_depth)
     if subsample:
         raise NotImplementedError("GDC: subsample=True (gdc_old.py's random grid subsampling) is not supported")
     if verbose:

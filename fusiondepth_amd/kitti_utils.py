@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import functional as FD
+from . import data_ops
 
 
 def load_velodyne_points(filename):
@@ -93,7 +93,7 @@ def _device_scan(velo_filename, device):
 def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False, shape=None, device="cuda"):
     """kitti_utils.py:40-102."""
     P, (im_h, im_w) = velo_to_image(calib_dir, cam)
-    full = FD.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, shape, return_full=True, vel_depth=vel_depth,
+    full = data_ops.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, shape, return_full=True, vel_depth=vel_depth,
                              beam=False)
     return full.cpu().numpy()
 
@@ -101,14 +101,14 @@ def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False, shape=N
 def get_4beam_device(calib_dir, velo_filename, cam=2, do_flip=False, device="cuda"):
     """kitti_dataset.py:93-110 + mono_dataset.py:196-198 on the device: [192,640] float32, metres / 100."""
     P, (im_h, im_w) = velo_to_image(calib_dir, cam)
-    beam = FD.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, (384, 1280))
+    beam = data_ops.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, (384, 1280))
     return torch.flip(beam, dims=[1]).contiguous() if do_flip else beam
 
 
 def get_4beam(calib_dir, velo_filename, cam=2, do_flip=False, device="cuda"):
     """gen2channel.py:42-58: the pooled map in metres (float64 numpy, before the / 100)."""
     P, (im_h, im_w) = velo_to_image(calib_dir, cam)
-    full = FD.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, (384, 1280), return_full=True, beam=False)
+    full = data_ops.velo_rasterize(_device_scan(velo_filename, device), P, im_h, im_w, (384, 1280), return_full=True, beam=False)
     pooled = torch.nn.functional.max_pool2d(full[None], 2, ceil_mode=True)[0].cpu().numpy()
     return np.fliplr(pooled) if do_flip else pooled
 
@@ -118,7 +118,7 @@ def get_4beam_2channel(fourbeam, height=192, width=640, expand=2):
     fourbeam = torch.as_tensor(fourbeam, dtype=torch.float32)
     if not fourbeam.is_cuda:
         fourbeam = fourbeam.cuda()
-    two = FD.scatter_2channel(fourbeam.contiguous(), FD.scaled_roi(height, width), expand)
+    two = data_ops.scatter_2channel(fourbeam.contiguous(), data_ops.scaled_roi(height, width), expand)
     return two[0], two[1]
 
 
@@ -132,7 +132,7 @@ def gen2channel(calib_dir, velo_filename, out_path, idx, side, regenerate=True, 
         return paths
     for flip, path in zip((False, True), paths):
         beam = get_4beam_device(calib_dir, velo_filename, side_map[side], flip, device)
-        np.save(path, FD.scatter_2channel(beam).cpu().numpy())
+        np.save(path, data_ops.scatter_2channel(beam).cpu().numpy())
     return paths
 
 

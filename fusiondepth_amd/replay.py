@@ -23,6 +23,8 @@ import torch
 from torch.utils import _pytree
 
 from . import _lib
+from . import functional
+from . import pass_state
 from . import tuning
 from . import weight_layouts
 
@@ -94,9 +96,8 @@ class Plan:
                 outs.append(arena[off:off + n * dtype.itemsize].view(dtype).view(shape))
             else:                                   # an output that IS an input (or a view of one)
                 outs.append(inputs[idx])
-        from . import functional as FD
-        if FD.CONV_FLOP_TALLY is not None:
-            FD.CONV_FLOP_TALLY[0] += self.tally
+        if functional.CONV_FLOP_TALLY is not None:
+            functional.CONV_FLOP_TALLY[0] += self.tally
         res = _pytree.tree_unflatten(outs, self.out_tree) if self.out_tree is not None else outs
         return (res, arena) if keep_arena else res
 
@@ -243,31 +244,30 @@ class Replayable:
         return self._record(key, inputs)
 
     def _record(self, key, inputs):
-        from . import functional as FD
         for t in inputs:
             if not (t.is_cuda and t.is_contiguous()):
                 return self.fn(*inputs)
         rec = Recorder()
         rec.stream = _lib.stream()
-        tally0 = FD.CONV_FLOP_TALLY[0] if FD.CONV_FLOP_TALLY is not None else None
-        had_tally = FD.CONV_FLOP_TALLY is not None
+        tally0 = functional.CONV_FLOP_TALLY[0] if functional.CONV_FLOP_TALLY is not None else None
+        had_tally = functional.CONV_FLOP_TALLY is not None
         if not had_tally:
-            FD.CONV_FLOP_TALLY = [0.0]
+            functional.CONV_FLOP_TALLY = [0.0]
             tally0 = 0.0
         _lib.RECORDER[0] = rec
         try:
             out = self.fn(*inputs)
         finally:
             _lib.RECORDER[0] = None
-            tally = FD.CONV_FLOP_TALLY[0] - tally0
+            tally = functional.CONV_FLOP_TALLY[0] - tally0
             if not had_tally:
-                FD.CONV_FLOP_TALLY = None
+                functional.CONV_FLOP_TALLY = None
         flat, tree = _pytree.tree_flatten(out)
         try:
             if not all(t is None or torch.is_tensor(t) for t in flat):
                 raise NotRecordable("the region returns non-tensor leaves")
             persistent = [t for t in self.persistent() if torch.is_tensor(t) and t.is_cuda]
-            persistent += weight_layouts.layout_buffers() + FD.folded_tensors()
+            persistent += weight_layouts.layout_buffers() + functional.folded_tensors()
             plan = build_plan(rec, list(inputs), flat, tree, persistent, tally)
             again = plan.replay(list(inputs))
             flat2, _ = _pytree.tree_flatten(again)
@@ -292,18 +292,17 @@ class Replayable:
 class _ReplayedNet(torch.autograd.Function):
     """ONE autograd node for a whole network: forward = its recorded calls replayed into a fresh arena (which is what the backward's
     saved tensors live in), backward = the recorded calls of its backward pass.  Parameter gradients accumulate straight into the flat
-    gradient buffer (functional.enable_direct_grad), so the node returns no gradient at all for them."""
+    gradient buffer (pass_state.enable_direct_grad), so the node returns no gradient at all for them."""
 
     @staticmethod
     def forward(ctx, state, x, anchor):
-        from . import functional as FD
         if state.late_f:
             weight_layouts.wait_late_layouts()
         for kind, payload in state.fwd_effects:
             if kind == "note_use":
-                FD._note_use(*payload)
+                pass_state.note_use(*payload)
             elif kind == "bn_counter":
-                FD.bump_bn_counter(*payload)
+                pass_state.bump_bn_counter(*payload)
         outs, arena = state.fwd.replay([x], keep_arena=True)
         ctx.state, ctx.arena, ctx.x = state, arena, x
         ctx.set_materialize_grads(False)
@@ -311,7 +310,6 @@ class _ReplayedNet(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        from . import functional as FD
         st = ctx.state
         got = tuple(i for i, g in enumerate(gouts) if g is not None)
         if not set(got) <= set(st.pattern):
@@ -326,7 +324,7 @@ class _ReplayedNet(torch.autograd.Function):
         ctx.arena = None
         for kind, payload in st.bwd_effects:
             if kind == "grad_ready":
-                FD._grad_ready(*payload)
+                pass_state.grad_ready(*payload)
         return None, (out[0] if out else None), None
 
 
@@ -367,11 +365,10 @@ class TrainReplayable:
         return outs
 
     def __call__(self, x):
-        from . import functional as FD
         if (self.disabled is not None or not tuning.host.replay_train or not torch.is_grad_enabled() or not self.training
                 or self.anchor is None or torch.cuda.is_current_stream_capturing() or not (x.is_cuda and x.is_contiguous())):
             return self.call(x)
-        key = (tuple(x.shape), x.dtype, getattr(x, "_fd_normalized", False), bool(x.requires_grad), FD._BN_GROUPS[0], tuning.generation(),
+        key = (tuple(x.shape), x.dtype, getattr(x, "_fd_normalized", False), bool(x.requires_grad), pass_state.current_bn_groups(), tuning.generation(),
                self.key_extra())
         st = self.states.get(key)
         if st is None:
@@ -400,16 +397,15 @@ class TrainReplayable:
         return [b for m in self.modules for b in m.buffers() if b.is_floating_point()]
 
     def _record(self, st, x):
-        from . import functional as FD
         try:
-            return self._record_inner(st, x, FD)
+            return self._record_inner(st, x)
         except NotRecordable as e:
             self.disabled = str(e)
             warnings.warn("fusiondepth_amd.replay: %s stays on the eager path: %s" % (self.name, e))
             return self.call(x) if not hasattr(e, "outs") else e.outs
 
-    def _record_inner(self, st, x, FD):
-        if not all(getattr(p, "_fd_direct_grad", False) and p.grad is not None for p in self.params if p.requires_grad):
+    def _record_inner(self, st, x):
+        if not all(pass_state.has_direct_grad(p) for p in self.params if p.requires_grad):
             raise NotRecordable("parameters without direct gradient accumulation")
         bufs = self._buffers()
         before = [b.clone() for b in bufs]

@@ -8,7 +8,7 @@ same folders and file names (``<output_path><folder>/{nbeams}beam/%010d.bin`` or
 written on a host thread pool (``--threads``, at most 16); the scans go to the device in batches (``--batch``) and each batch is one
 ``fd_sparsify_scans`` call.
 
-Arithmetic: numpy 2's evaluation of the reference (``FD.sparsify_scans``); only ``arcsin`` is not matched bit for bit, so a point
+Arithmetic: numpy 2's evaluation of the reference (``data_ops.sparsify_scans``); only ``arcsin`` is not matched bit for bit, so a point
 within a few float32 spacings of a bin edge may land in the neighbouring cell.  ``--random_sample`` draws from the
 library's counter-based generator keyed by (``--seed``, folder, frame index): the reference's ``np.random`` draws depend on the
 order its process pool happens to work in and are not reproduced; their distribution is.
@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import functional as FD
+from . import data_ops
 
 REFUSED = {
     "fill_in_map_dir": "line maps are float64 .npy dumps of the reference's --store_line_map_dir runs, which this tool does not write",
@@ -51,7 +51,7 @@ def sparsify(points, H=64, W=1024, line_spec=None, slice=1, random_sample=0, uni
     """One scan ([n,4], CUDA tensor or numpy array) -> the compacted [m,4] float32 CUDA tensor ``gen_sparse_points`` returns."""
     if not torch.is_tensor(points):
         points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).cuda()
-    slab, counts = FD.sparsify_scans([points], H, W, line_spec, slice, random_sample,
+    slab, counts = data_ops.sparsify_scans([points], H, W, line_spec, slice, random_sample,
                                      None if uniforms is None else [uniforms], seed, [key])
     return slab[0, :int(counts[0])].clone()
 
@@ -129,7 +129,7 @@ def run(args, device="cuda"):
             if ci + 1 < len(chunks):                             # the next batch's files are read while this one is on the device
                 reads = [pool.submit(load_scan, input_path(args, *e)) for e in chunks[ci + 1]]
             dev = [torch.from_numpy(s).to(device, non_blocking=True) for s in scans]
-            slab, counts = FD.sparsify_scans(dev, args.H, args.W, args.line_spec, args.slice, args.random_sample, None, args.seed,
+            slab, counts = data_ops.sparsify_scans(dev, args.H, args.W, args.line_spec, args.slice, args.random_sample, None, args.seed,
                                              [scan_key(*e) for e in chunk])
             counts = counts.cpu().numpy()
             slab = slab[:, :max(int(counts.max()), 1)].cpu().numpy()

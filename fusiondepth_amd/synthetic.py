@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import functional as FD
+from . import data_ops
 
 K_NORMALISED = np.array([[0.58, 0, 0.5, 0], [0, 1.92, 0.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float32)  # kitti_dataset.py:36-39
 
@@ -75,10 +75,10 @@ def make_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -1, 1),
             inputs[("color", f, s)] = lvl.contiguous()
             inputs[("color_aug", f, s)] = inputs[("color", f, s)]     # no colour augmentation in the synthetic feed
     inputs.update(intrinsics(batch, height, width, num_scales, device))
-    roi = FD.scaled_roi(height, width)
+    roi = data_ops.scaled_roi(height, width)
     for i, f in enumerate(frame_ids):
         beam = lidar_4beam(batch, height, width, gen, device, shift=i)
-        two = FD.scatter_2channel(beam, roi)
+        two = data_ops.scatter_2channel(beam, roi)
         inputs[("2channel", f, 0)] = two
         if f == 0:
             inputs["4beam"] = beam
@@ -179,7 +179,7 @@ def make_scene_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -
             lvl = img if s == 0 else F.avg_pool2d(img, 2 ** s)
             inputs[("color", f, s)] = lvl.contiguous()
             inputs[("color_aug", f, s)] = inputs[("color", f, s)]
-    roi = FD.scaled_roi(height, width)
+    roi = data_ops.scaled_roi(height, width)
     rows = [int(height * q) for q in (0.52, 0.625, 0.73, 0.835)]
     for i, f in enumerate(frame_ids):
         beam = torch.zeros(batch, 1, height, width, device=device)
@@ -193,7 +193,7 @@ def make_scene_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -
                 ladder = 2.0 + 76.0 * (torch.arange(n_cl, device=device, dtype=torch.float32) + 0.5) / max(n_cl, 1)
                 ranges[:, pick] = ladder.unsqueeze(0).expand(batch, n_cl)
             beam[:, 0, r, cols] = ranges / 100.0                                                     # metres / 100
-        two = FD.scatter_2channel(beam, roi) if scatter is None else scatter(beam)
+        two = data_ops.scatter_2channel(beam, roi) if scatter is None else scatter(beam)
         inputs[("2channel", f, 0)] = two
         if f == 0:
             inputs["4beam"], inputs["2channel"] = beam, two

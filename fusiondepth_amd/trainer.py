@@ -182,7 +182,7 @@ class Trainer:
         FD.evict_dead_weight_layouts()         # cached layouts / re-layout plan of trainers that no longer exist
         FD.enable_weight_cache(self.parameters_to_train)
         FD.enable_direct_grad(self.parameters_to_train)
-        # the depth decoder is the serial section of the step: its weight gradients leave the main stream (functional.enable_side_wgrad)
+        # the depth decoder is the serial section of the step: its weight gradients leave the main stream (pass_state.enable_side_wgrad)
         for k in tuning.host.side_wgrad:
             if k in self.models:
                 FD.enable_side_wgrad(self.models[k].parameters())
@@ -469,7 +469,7 @@ class Trainer:
                 self._static_losses = self._graph_body(self._static_in)
             self._graph = g
         # A refresh of the cached weight layouts issued eagerly since the last replay - the optimiser step that follows the graph when
-        # world_size > 1, load_model() - puts the large layouts on a side stream behind an event (functional.refresh_weight_layouts).
+        # world_size > 1, load_model() - puts the large layouts on a side stream behind an event (weight_layouts.refresh_weight_layouts).
         # The captured kernels were recorded with "layout ready" and never look at that event: the replay stream waits for it here.
         FD.sync_late_layouts()
         self._graph.replay()

@@ -625,7 +625,7 @@ int fd_gdc_finish(const float* pred, const double* gt, const int* pix, int N_PL,
  * fd_resize_lanczos_u8: Pillow's 8-bit antialiased Lanczos resample, src [N][Hin][Win][3] -> dst [N][Hout][Wout][3]: a horizontal
  *   pass into ws (uint8), then a vertical pass.  xtab / ytab (device, int32): per output column / row the record
  *   (first tap, tap count, k coefficients), k = kx / ky = 2 * ceil(3 * max(in, out) / out) + 1; coefficient = int(w * 2^22 +- 0.5) of
- *   the float64 weight, built by the caller on the host (functional.lanczos_table).  pixel = clip((2^21 + sum) >> 22).
+ *   the float64 weight, built by the caller on the host (data_ops.lanczos_table).  pixel = clip((2^21 + sum) >> 22).
  *   mirror (device, int32 [N], may be NULL): frames with a non-zero entry are read flipped left-right (kitti_dataset.py:59-60 flips
  *   before resizing).  src and ws 16-byte aligned; ws: fd_resize_lanczos_u8_ws_bytes bytes.
  * fd_color_jitter_u8: n_images images described by a device table, one launch sequence for all of them whatever their sizes.

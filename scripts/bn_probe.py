@@ -34,17 +34,16 @@ def main():
         bn = nn.BatchNorm2d(C).cuda()
         x = torch.randn(N, C, H, W, device="cuda")
         res = torch.randn(N, C, H, W, device="cuda")
-        FD._BN_GROUPS[0] = G
-        xr = x.clone().requires_grad_(True)
-        y = FD.batch_norm(xr, bn, residual=res, relu=True)
-        gy = torch.randn_like(y)
-        nbytes = x.numel() * 4
-        t_f = timed(lambda: FD.batch_norm(x, bn, residual=res, relu=True))
-        t_b = timed(lambda: torch.autograd.grad(y, xr, gy, retain_graph=True))
+        with FD.bn_groups(G):
+            xr = x.clone().requires_grad_(True)
+            y = FD.batch_norm(xr, bn, residual=res, relu=True)
+            gy = torch.randn_like(y)
+            nbytes = x.numel() * 4
+            t_f = timed(lambda: FD.batch_norm(x, bn, residual=res, relu=True))
+            t_b = timed(lambda: torch.autograd.grad(y, xr, gy, retain_graph=True))
         # fwd: stats read x; apply read x + residual, write y = 4 passes.  bwd: reduce reads x, y, gy; apply reads x, y, gy, writes gx, g_res = 8
         print("%-22s %10.1f %10.0f %10.1f %10.0f" % (str((N, C, H, W, G)), t_f, 4 * nbytes / t_f / 1e3, t_b, 8 * nbytes / t_b / 1e3))
         tot_f += t_f; tot_b += t_b
-    FD._BN_GROUPS[0] = 1
     print("sum fwd %.1f us, bwd %.1f us" % (tot_f, tot_b))
 
 

@@ -104,7 +104,7 @@ def test_flat_parameters_views_and_buckets():
 
 class _InPlaceLinear(torch.autograd.Function):
     """Stand-in for the HIP backward kernels: accumulates the weight gradient straight into ``w.grad`` (a view of the flat
-    buffer), returns no parameter gradient to autograd and reports completion through functional._grad_ready."""
+    buffer), returns no parameter gradient to autograd and reports completion through pass_state.grad_ready."""
 
     @staticmethod
     def forward(ctx, x, w):
@@ -114,10 +114,10 @@ class _InPlaceLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from fusiondepth_amd import functional as FD
+        from fusiondepth_amd import pass_state
         (x,) = ctx.saved_tensors
         ctx.w.grad += gy.t() @ x
-        FD._grad_ready(ctx.w)
+        pass_state.grad_ready(ctx.w)
         return gy @ ctx.w, None
 
 
@@ -157,7 +157,7 @@ def _worker_direct(rank, world, port, out):
 
 def test_in_place_gradients_trigger_overlapped_buckets():
     """The trainer's kernels accumulate parameter gradients in place, so autograd's hooks never fire: the buckets must leave
-    through functional.add_grad_ready_callback instead, one per segment, and the unused parameter's bucket at finish()."""
+    through pass_state.add_grad_ready_callback instead, one per segment, and the unused parameter's bucket at finish()."""
     world = 2
     mgr = mp.Manager()
     out = mgr.dict()

@@ -225,6 +225,7 @@ def test_image_pyramid_equals_the_restatement():
 
 def test_bad_arguments_return_an_error_not_a_crash():
     from fusiondepth_amd import _lib
+    from fusiondepth_amd import data_ops
     from fusiondepth_amd import functional as FD
     x = torch.zeros((1, 8, 8, 3), dtype=torch.uint8, device="cuda")
     y = torch.zeros((1, 4, 4, 3), dtype=torch.uint8, device="cuda")
@@ -254,12 +255,12 @@ def test_bad_arguments_return_an_error_not_a_crash():
     assert _lib.query("fd_color_jitter_u8_ws_bytes", 0) == 0
     # a table entry whose extent leaves the buffers is skipped on the device: the output keeps its contents
     out = torch.full((1, 8, 8, 3), 7, dtype=torch.uint8, device="cuda")
-    means = FD._run_jitter(x.view(-1), [(64, 0, -1, -1, 8, 8, (1.0, 1.0, 1.0, 0.0), [])], out.view(-1), None, 64)
+    means = data_ops._run_jitter(x.view(-1), [(64, 0, -1, -1, 8, 8, (1.0, 1.0, 1.0, 0.0), [])], out.view(-1), None, 64)
     assert (host(out) == 7).all() and means.numel() == 1
     # an operation listed twice: refused by the wrapper, skipped by the kernel
     with pytest.raises(ValueError, match="distinct"):
         FD.color_jitter_u8(x, [((1.1, 0.9, 1.0, 0.0), [1, 0, 1])])
-    FD._run_jitter(x.view(-1), [(0, 0, -1, -1, 8, 8, (1.1, 0.9, 1.0, 0.0), [1, 1])], out.view(-1), None, 64)
+    data_ops._run_jitter(x.view(-1), [(0, 0, -1, -1, 8, 8, (1.1, 0.9, 1.0, 0.0), [1, 1])], out.view(-1), None, 64)
     assert (host(out) == 7).all()
     with pytest.raises(RuntimeError, match="uint8"):
         FD.resize_lanczos_u8(torch.zeros((1, 8, 8, 3), device="cuda"), (4, 4))

@@ -963,19 +963,19 @@ def test_fused_pose_head_is_bit_identical(fdtune):
     """tuning.host.fused_pose_head (FD.pose_head: the stacked pose network's slices, concatenations and pose matrices as one launch each
     way) against the slice-by-slice path: parameters after three optimiser steps of two accumulated micro-batches identical bit for
     bit, and the fused node really used."""
-    from fusiondepth_amd import functional as FD
+    from fusiondepth_amd import loss_ops
     from fusiondepth_amd.trainer import Trainer
     B, H, W = 12, 64, 96                 # --batch_size 12 = two accumulated micro-batches of 6 (trainer.py:28-41)
     res = {}
     for fused in (True, False):
         fdtune.host(fused_pose_head=fused)
         n_apply = [0]
-        orig = FD._PoseHead.forward
+        orig = loss_ops._PoseHead.forward
 
         def counting(ctx, *a, _orig=orig):
             n_apply[0] += 1
             return _orig(ctx, *a)
-        FD._PoseHead.forward = staticmethod(counting)
+        loss_ops._PoseHead.forward = staticmethod(counting)
         try:
             torch.manual_seed(1357)
             tr = Trainer(_opts(batch_size=B), verbose=False)
@@ -990,7 +990,7 @@ def test_fused_pose_head_is_bit_identical(fdtune):
                 tr.train_step(mbs)
             torch.cuda.synchronize()
         finally:
-            FD._PoseHead.forward = staticmethod(orig)
+            loss_ops._PoseHead.forward = staticmethod(orig)
         assert (n_apply[0] > 0) == fused, n_apply
         res[fused] = tr.flat.flat_param.clone()
         del tr
@@ -999,11 +999,11 @@ def test_fused_pose_head_is_bit_identical(fdtune):
 
 
 def test_decoder_weight_gradients_on_the_side_stream_are_bit_identical(fdtune):
-    """functional.enable_side_wgrad (default for the depth decoder): its weight gradients, slab reductions and bias sums run on a side
+    """pass_state.enable_side_wgrad (default for the depth decoder): its weight gradients, slab reductions and bias sums run on a side
     stream beside the data gradients of the following layers.  Same kernels, same accumulation targets: the gradient buffer after a
     backward pass must equal the all-on-one-stream result bit for bit, also under background GPU load (a tensor freed or reused on
     the main stream while the side stream still reads it would show up here), and the side stream must really have been used."""
-    from fusiondepth_amd import functional as FD
+    from fusiondepth_amd import pass_state
     from fusiondepth_amd.trainer import Trainer
     B, H, W = 2, 64, 96
     inp, noise = _batch(B, H, W, 991)
@@ -1016,7 +1016,7 @@ def test_decoder_weight_gradients_on_the_side_stream_are_bit_identical(fdtune):
         fdtune.host(side_wgrad=() if mode == "none" else (mode,))
         torch.manual_seed(4321)                                  # the same initial weights for both trainers
         tr = Trainer(_opts(batch_size=B), verbose=False)
-        marked = [p for p in tr.models["depth"].parameters() if getattr(p, "_fd_side_wgrad", False)]
+        marked = [p for p in tr.models["depth"].parameters() if pass_state.has_side_wgrad(p)]
         assert (len(marked) > 0) == (mode == "depth")
         for rep in range(3):
             tr.flat.zero_grad()
@@ -1028,9 +1028,9 @@ def test_decoder_weight_gradients_on_the_side_stream_are_bit_identical(fdtune):
             outputs, losses = tr.process_batch(ginp, groups=tr.accumulate_step)
             losses["loss"].backward()
             if mode == "depth":
-                assert len(FD._WGRAD_KEEPALIVE) >= len(marked) // 2          # the side stream has pending work to be joined
+                assert pass_state.pending_side_wgrads() >= len(marked) // 2         # the side stream has pending work to be joined
             tr._join_side_streams()
-            assert not FD._WGRAD_KEEPALIVE
+            assert pass_state.pending_side_wgrads() == 0
             torch.cuda.synchronize()
             g = tr.flat.flat_grad.clone()
             with torch.no_grad():
