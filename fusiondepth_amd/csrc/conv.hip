@@ -1,20 +1,13 @@
-// FP32 implicit-GEMM convolution on the CDNA4 matrix cores (v_mfma_f32_32x32x2_f32: exact f32, k-ordered
-// fmaf chain) — forward, data-gradient and weight-gradient for every conv of the hot path:
-//   ResNet trunk   networks/resnet_encoder.py:92-103  (7x7 s2, 3x3 s1/s2, 1x1 s1/s2; zero pad)
-//   DepthDecoder   networks/depth_decoder.py:63-96     (3x3 reflect pad + bias + ELU / sigmoid)
-//   PoseDecoder    networks/pose_decoder.py:29-51      (1x1 / 3x3 + bias + ReLU)
-//
-// One "gather GEMM" kernel does forward AND data-gradient:  D[m][p] = sum_k A[m][k] * G[k][p]
-//   A   dense row-major [M][K] matrix in HBM (weights, or a re-laid-out copy made by the prep kernels)
-//   G   never materialised: k = (c, a, b) indexes channel c and tap (a,b); p = (n, y, x) indexes a pixel of
-//       the GEMM-N domain; G[k][p] = X[n][c][y*sy+oy+a*da][x*sx+ox+b*db]  (zero or reflect outside)
-//   D   written through an affine pixel map (so stride-2 dgrad parity classes scatter into dX directly).
-// NCHW keeps pixels contiguous, so both the G loads and the D stores are coalesced along the 64 lanes.
-// Tiles: workgroup = WAVES_M x WAVES_N waves, each wave owns WM x WN accumulators of 32x32, K-chunk 16,
-// register-staged double-buffered LDS (one barrier per chunk).
+// The convolution entry points of the C ABI (fd_conv2d_*) and everything that decides for them: the shape checks, the three
+// routes (route_fwd / route_dgrad / route_wgrad: which kernel family computes a convolution, with which weight layout and
+// workspace), the *_impl functions that follow a route, and the small passes around the kernels - weight re-layouts, the
+// reflect-padding folds, the bias gradient.  The kernels live in one unit per family: conv_generic.hip (the implicit GEMM every
+// shape can fall back to), conv_fast.hip, conv_limb.hip, conv_wino*.hip, conv_n16.hip, conv_narrow.hip, conv_c1.hip, conv_stem.hip.
 #include "../../include/fdhip.h"
 #include "fd_common.h"
 #include "conv_fast.h"
+#include "conv_generic.h"
+#include "conv_wino.h"
 #include "conv_limb.h"
 #include <stdio.h>
 #include <algorithm>
@@ -24,382 +17,6 @@ extern "C" int fd_axpby(const float* a, const float* b, float* out, long n, floa
 extern "C" int fd_act_bwd(const float* y, const float* gy, float* gpre, long n, int act, void* stream);   // pool.hip
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BK = 16;
-
-struct GemmArgs {
-    const float* A; const float* X; float* Y; const float* bias;
-    int M, K;
-    int Nb, C, Hi, Wi;
-    int NY, NX;
-    int sy, oy, da, sx, ox, db;
-    int pad_mode;   // 0 zero, 1 reflect
-    long out_ns, out_cs;
-    int out_w, osy, ooy, osx, oox;
-    int act;        // 0 none, 1 relu, 2 elu, 3 sigmoid, 4 tanh
-    int in_norm;    // conv1: (x - 0.45) / 0.225 on in-bounds taps (resnet_encoder.py:94)
-    int xcd_swizzle;
-};
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return v > 0.f ? v : expm1f(v);
-    if (act == 3) return 1.0f / (1.0f + expf(-v));
-    if (act == 4) return tanhf(v);
-    return v;
-}
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
-template <int TA, int TB, int WAVES_M, int WAVES_N, int WM, int WN, bool NORM>
-__global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) k_gather_gemm(GemmArgs g) {
-    constexpr int NT = 64 * WAVES_M * WAVES_N;
-    constexpr int BM = WAVES_M * 32 * WM, BN = WAVES_N * 32 * WN;
-    constexpr int LDA = BM + 2, LDB = BN;
-    constexpr int RP = NT / BN;            // k rows covered per pass of the G loader
-    constexpr int NB_LOAD = BK / RP;       // G elements per thread per chunk
-    constexpr int MP = NT / BK;            // m rows covered per pass of the A loader
-    constexpr int NA_LOAD = BM / MP;
-    static_assert(NT % BN == 0 && BK % RP == 0 && BM % MP == 0, "tile/loader mismatch");
-    __shared__ float sA[2][BK * LDA];
-    __shared__ float sB[2][BK * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
-
-    // block -> tile (optionally XCD-aware: consecutive pixel tiles stay on one XCD / one L2)
-    int bx = blockIdx.x;
-    if (g.xcd_swizzle) { const int per = gridDim.x >> 3; bx = (bx & 7) * per + (bx >> 3); }
-    const int m0 = blockIdx.y * BM;
-    const long p0 = (long)bx * BN;
-    const long plane = (long)g.NY * g.NX, Np = (long)g.Nb * plane;
-    const long chw = (long)g.Hi * g.Wi;
-
-    // ---- G loader: this thread always fetches pixel column jn, k rows kr + RP*i
-    const int jn = tid % BN;
-    const int kr = __builtin_amdgcn_readfirstlane(tid / BN);
-    const long pg = p0 + jn;
-    const bool pvalid = pg < Np;
-    int ry0 = 0, cx0 = 0;
-    unsigned nbase = 0u;
-    {
-        const long pp = pvalid ? pg : 0;
-        const int n = (int)(pp / plane);
-        const int rem = (int)(pp - (long)n * plane);
-        const int y = rem / g.NX, x = rem - y * g.NX;
-        ry0 = y * g.sy + g.oy; cx0 = x * g.sx + g.ox;
-        nbase = (unsigned)n * (unsigned)g.C * (unsigned)chw;
-    }
-    // ---- A loader: k column ka, m rows ma + MP*i
-    const int ka = tid % BK, ma = tid / BK;
-    const __amdgpu_buffer_rsrc_t rsA = fd_make_rsrc(g.A), rsX = fd_make_rsrc(g.X);
-    const bool refl = g.pad_mode == 1;
-
-    // Raw buffer loads (32-bit byte offsets, out-of-range = 0.0f): padding taps, k >= K, rows >= M and pixels past the end
-    // need no selects; only the NORM variant keeps a validity mask because its padding must stay 0 AFTER the affine map.
-    float ra[NA_LOAD], rb[NB_LOAD];
-    unsigned okmask = 0u;
-    int k0 = 0;                                        // first k of the chunk being fetched
-    auto load_a = [&](int i) __attribute__((always_inline)) {
-        const int m = m0 + ma + MP * i, k = k0 + ka;
-        ra[i] = fd_ldg32(rsA, (m < g.M) & (k < g.K) ? 4u * ((unsigned)m * (unsigned)g.K + (unsigned)k) : FD_OOB);
-    };
-    auto load_b = [&](int i) __attribute__((always_inline)) {
-        const int k = k0 + kr + RP * i;                // wave-uniform
-        const int c = k / (TA * TB), t = k - c * (TA * TB);
-        const int ta = t / TB, tb = t - ta * TB;
-        int r = ry0 + ta * g.da, cc = cx0 + tb * g.db;
-        const bool inside = ((unsigned)r < (unsigned)g.Hi) & ((unsigned)cc < (unsigned)g.Wi);
-        const int rr = reflect_idx(r, g.Hi), cr = reflect_idx(cc, g.Wi);
-        r = refl ? rr : r; cc = refl ? cr : cc;
-        const bool ok = pvalid & (k < g.K) & (refl | inside);
-        rb[i] = fd_ldg32(rsX, ok ? 4u * (nbase + (unsigned)c * (unsigned)chw + (unsigned)(r * g.Wi + cc)) : FD_OOB);
-        if (NORM) okmask = (okmask & ~(1u << i)) | (ok ? (1u << i) : 0u);
-    };
-    auto store_a = [&](int buf, int i) __attribute__((always_inline)) { sA[buf][ka * LDA + ma + MP * i] = ra[i]; };
-    auto store_b = [&](int buf, int i) __attribute__((always_inline)) {
-        float v = rb[i];
-        if (NORM) v = ((okmask >> i) & 1u) ? (v - 0.45f) / 0.225f : 0.f;          // resnet_encoder.py:94, padding stays 0
-        sB[buf][(kr + RP * i) * LDB + jn] = v;
-    };
-
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nchunk = (g.K + BK - 1) / BK;
-    constexpr int NK = BK / 2, LS = NK / 2;           // first LS k-steps issue the next chunk's loads, the last LS store them
-#pragma unroll
-    for (int i = 0; i < NA_LOAD; ++i) load_a(i);
-#pragma unroll
-    for (int i = 0; i < NB_LOAD; ++i) load_b(i);
-#pragma unroll
-    for (int i = 0; i < NA_LOAD; ++i) store_a(0, i);
-#pragma unroll
-    for (int i = 0; i < NB_LOAD; ++i) store_b(0, i);
-    __syncthreads();
-    const int arow = lane >> 5, acol = lane & 31;
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int cur = ch & 1;
-        k0 = (ch + 1) * BK;                            // past the end: k >= K, every load out of range
-        const float* pa = &sA[cur][arow * LDA + wave_m * 32 * WM + acol];
-        const float* pb = &sB[cur][arow * LDB + wave_n * 32 * WN + acol];
-        float av[2][WM], bv[2][WN];
-#pragma unroll
-        for (int i = 0; i < WM; ++i) av[0][i] = pa[i * 32];
-#pragma unroll
-        for (int j = 0; j < WN; ++j) bv[0][j] = pb[j * 32];
-#pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-            const int cb = kk & 1, nb = cb ^ 1;
-            if (kk + 1 < NK) {
-#pragma unroll
-                for (int i = 0; i < WM; ++i) av[nb][i] = pa[(kk + 1) * 2 * LDA + i * 32];
-#pragma unroll
-                for (int j = 0; j < WN; ++j) bv[nb][j] = pb[(kk + 1) * 2 * LDB + j * 32];
-            }
-            if (kk < LS) {
-#pragma unroll
-                for (int i = 0; i < NA_LOAD; ++i) if ((i * LS) / NA_LOAD == kk) load_a(i);
-#pragma unroll
-                for (int i = 0; i < NB_LOAD; ++i) if ((i * LS) / NB_LOAD == kk) load_b(i);
-            } else if (kk >= NK - LS) {
-#pragma unroll
-                for (int i = 0; i < NA_LOAD; ++i) if ((i * LS) / NA_LOAD == kk - (NK - LS)) store_a(cur ^ 1, i);
-#pragma unroll
-                for (int i = 0; i < NB_LOAD; ++i) if ((i * LS) / NB_LOAD == kk - (NK - LS)) store_b(cur ^ 1, i);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][i], bv[cb][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: bias + activation, affine pixel map.  C/D layout of 32x32 MFMA:
-    //      col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const long p = p0 + wave_n * 32 * WN + j * 32 + acol;
-        if (p >= Np) continue;
-        const int n = (int)(p / plane);
-        const int rem = (int)(p - (long)n * plane);
-        const int y = rem / g.NX, x = rem - y * g.NX;
-        float* yo = g.Y + (long)n * g.out_ns + (long)(y * g.osy + g.ooy) * g.out_w + (x * g.osx + g.oox);
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wave_m * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * arow;
-                if (m < g.M) {
-                    float v = acc[i][j][r];
-                    if (g.bias) v += g.bias[m];
-                    yo[(long)m * g.out_cs] = apply_act(v, g.act);
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient:  dW[m][j] = sum_p dY[m][p] * G[j][p]   (j = (c,a,b) as above, p over the OUTPUT pixels
-// of the forward conv), split over the pixel axis; partial slabs are reduced in a fixed order.
-struct WgradArgs {
-    const float* dY; const float* X; float* out;   // out: dW (splits == 1) or slabs [splits][M][J]
-    int M, J;
-    int Nb, C, Hi, Wi;
-    int NY, NX;
-    int sy, oy, da, sx, ox, db;
-    int pad_mode, in_norm;
-    long dy_ns, dy_cs;      // dY[n*dy_ns + m*dy_cs + y*NX + x]
-    long pix_per_split;
-};
-
-// Loader design (same recipe as conv_fast.hip): raw buffer loads with 32-bit byte offsets, out-of-range = 0.0f; every
-// per-row quantity (dY row offset, the (channel, tap) decode of a G row) is fixed per thread and precomputed; the pixel
-// decode advances incrementally; loads of chunk ch+1 / their LDS stores are interleaved with the MFMAs of chunk ch.
-template <int TA, int TB, int WAVES_M, int WAVES_N, int WM, int WN, bool REFL, bool NORM>
-__global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) k_wgrad(WgradArgs g) {
-    constexpr int NT = 64 * WAVES_M * WAVES_N;
-    constexpr int BM = WAVES_M * 32 * WM, BN = WAVES_N * 32 * WN;
-    constexpr int BP = 32;                       // pixels (GEMM-K) per chunk
-    constexpr int LDA = BM + 1, LDB = BN + 1;
-    constexpr int RPW = NT / BP;                 // rows (m or j) covered per pass
-    constexpr int NA_LOAD = BM / RPW, NB_LOAD = BN / RPW;
-    static_assert(BM % RPW == 0 && BN % RPW == 0, "tile/loader mismatch");
-    __shared__ float sA[2][BP * LDA];
-    __shared__ float sB[2][BP * LDB];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
-    const int m0 = blockIdx.y * BM, j0 = blockIdx.x * BN;
-    const int plane = g.NY * g.NX;
-    const long Np = (long)g.Nb * plane;
-    const unsigned chw = (unsigned)(g.Hi * g.Wi);
-    const long pbeg = (long)blockIdx.z * g.pix_per_split;
-    long pend = pbeg + g.pix_per_split;
-    if (pend > Np) pend = Np;
-
-    const int pl = tid % BP, rw = tid / BP;      // pixel within chunk, first row handled
-    const __amdgpu_buffer_rsrc_t rsY = fd_make_rsrc(g.dY), rsX = fd_make_rsrc(g.X);
-    const int nrow = g.M - m0 < BM ? g.M - m0 : BM;
-    // dY rows past M are clamped to the last valid row: their products land in accumulator rows that are never stored
-    unsigned rowa[NA_LOAD];
-#pragma unroll
-    for (int i = 0; i < NA_LOAD; ++i) {
-        const int r = rw + RPW * i < nrow ? rw + RPW * i : nrow - 1;
-        rowa[i] = 4u * (unsigned)(m0 + r) * (unsigned)g.dy_cs;
-    }
-    // G rows j = (channel, tap): byte offset of the (channel, tap) relative to the pixel's gather origin, and the tap
-    // displacement for the bounds / reflect logic.  Rows >= J are clamped to row J-1 (their output columns are never stored).
-    unsigned joff[NB_LOAD];
-    int jro[NB_LOAD], jco[NB_LOAD];
-#pragma unroll
-    for (int i = 0; i < NB_LOAD; ++i) {
-        const int j = j0 + rw + RPW * i < g.J ? j0 + rw + RPW * i : g.J - 1;
-        const int c = j / (TA * TB), t = j - c * (TA * TB);
-        const int ta = t / TB, tb = t - ta * TB;
-        jro[i] = ta * g.da; jco[i] = tb * g.db;
-        if (REFL) joff[i] = 4u * (unsigned)c * chw;
-        else joff[i] = 4u * ((unsigned)c * chw + (unsigned)(jro[i] * g.Wi + jco[i]));
-    }
-
-    float ra[NA_LOAD], rb[NB_LOAD];
-    unsigned offa = FD_OOB, xbase = FD_OOB, okmask = 0u;
-    int ry0 = 0, cx0 = 0;
-    int pn, prem;
-    { const long p = pbeg + pl; pn = (int)(p / plane); prem = (int)(p - (long)pn * plane); }
-    long pcur = pbeg + pl;
-    const float inv_nx = 1.0f / (float)g.NX;
-    auto prep_chunk = [&]() __attribute__((always_inline)) {      // pixels >= pend: everything out of range (zeros)
-        const bool pv = pcur < pend;
-        int y = (int)(((float)prem + 0.5f) * inv_nx);             // estimate within +-1 for planes < 2^23; fixed up below
-        int x = prem - y * g.NX;
-        if (x < 0) { --y; x += g.NX; }
-        if (x >= g.NX) { ++y; x -= g.NX; }
-        offa = pv ? 4u * ((unsigned)pn * (unsigned)g.dy_ns + (unsigned)prem) : FD_OOB;
-        ry0 = y * g.sy + g.oy; cx0 = x * g.sx + g.ox;
-        // zero padding: origin of the gather window (may lie outside the image: the sum with joff is used only in bounds)
-        if (REFL) xbase = pv ? 4u * (unsigned)pn * (unsigned)g.C * chw : FD_OOB;
-        else xbase = 4u * ((unsigned)pn * (unsigned)g.C * chw + (unsigned)(ry0 * g.Wi + cx0));
-        if (!REFL && !pv) ry0 = -(1 << 20);                       // fails every bounds test below
-        pcur += BP; prem += BP;
-        while (prem >= plane) { prem -= plane; ++pn; }
-        okmask = 0u;
-    };
-    auto load_a = [&](int i) __attribute__((always_inline)) { ra[i] = fd_ldg32(rsY, offa + rowa[i]); };
-    auto load_b = [&](int i) __attribute__((always_inline)) {
-        const int r = ry0 + jro[i], cc = cx0 + jco[i];
-        unsigned off;
-        bool ok;
-        if (REFL) {
-            const int rr = reflect_idx(r, g.Hi), cr = reflect_idx(cc, g.Wi);
-            off = xbase + joff[i] + 4u * (unsigned)(rr * g.Wi + cr);          // xbase carries FD_OOB for pixels past the end
-            ok = true;
-        } else {
-            ok = ((unsigned)r < (unsigned)g.Hi) & ((unsigned)cc < (unsigned)g.Wi);
-            off = ok ? xbase + joff[i] : FD_OOB;
-        }
-        if (NORM) okmask |= ok ? (1u << i) : 0u;
-        rb[i] = fd_ldg32(rsX, off);
-    };
-    auto store_a = [&](int buf, int i) __attribute__((always_inline)) { sA[buf][pl * LDA + rw + RPW * i] = ra[i]; };
-    auto store_b = [&](int buf, int i) __attribute__((always_inline)) {
-        float v = rb[i];
-        if (NORM) v = ((okmask >> i) & 1u) ? (v - 0.45f) / 0.225f : 0.f;      // resnet_encoder.py:94, padding stays 0
-        sB[buf][pl * LDB + rw + RPW * i] = v;
-    };
-
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nchunk = pend > pbeg ? (int)((pend - pbeg + BP - 1) / BP) : 0;
-    constexpr int NK = BP / 2, HS = NK / 2;
-    const int arow = lane >> 5, acol = lane & 31;
-    if (nchunk > 0) {
-        prep_chunk();
-#pragma unroll
-        for (int i = 0; i < NA_LOAD; ++i) load_a(i);
-#pragma unroll
-        for (int i = 0; i < NB_LOAD; ++i) load_b(i);
-#pragma unroll
-        for (int i = 0; i < NA_LOAD; ++i) store_a(0, i);
-#pragma unroll
-        for (int i = 0; i < NB_LOAD; ++i) store_b(0, i);
-        __syncthreads();
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int cur = ch & 1;
-            prep_chunk();
-            const float* pa = &sA[cur][arow * LDA + wave_m * 32 * WM + acol];
-            const float* pb = &sB[cur][arow * LDB + wave_n * 32 * WN + acol];
-            float av[2][WM], bv[2][WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) av[0][i] = pa[i * 32];
-#pragma unroll
-            for (int j = 0; j < WN; ++j) bv[0][j] = pb[j * 32];
-#pragma unroll
-            for (int kk = 0; kk < NK; ++kk) {
-                const int cb = kk & 1, nb = cb ^ 1;
-                if (kk + 1 < NK) {
-#pragma unroll
-                    for (int i = 0; i < WM; ++i) av[nb][i] = pa[(kk + 1) * 2 * LDA + i * 32];
-#pragma unroll
-                    for (int j = 0; j < WN; ++j) bv[nb][j] = pb[(kk + 1) * 2 * LDB + j * 32];
-                }
-                if (kk < HS) {
-#pragma unroll
-                    for (int i = 0; i < NA_LOAD; ++i) if ((i * HS) / NA_LOAD == kk) load_a(i);
-#pragma unroll
-                    for (int i = 0; i < NB_LOAD; ++i) if ((i * HS) / NB_LOAD == kk) load_b(i);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NA_LOAD; ++i) if ((i * HS) / NA_LOAD == kk - HS) store_a(cur ^ 1, i);
-#pragma unroll
-                    for (int i = 0; i < NB_LOAD; ++i) if ((i * HS) / NB_LOAD == kk - HS) store_b(cur ^ 1, i);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < WN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cb][i], bv[cb][j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-        }
-    }
-    float* out = g.out + (long)blockIdx.z * g.M * g.J;
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int jj = j0 + wave_n * 32 * WN + j * 32 + acol;
-        if (jj >= g.J) continue;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wave_m * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * arow;
-                if (m < g.M) out[(long)m * g.J + jj] = acc[i][j][r];
-            }
-    }
-}
 
 __global__ void k_reduce_slabs(const float* __restrict__ slabs, float* __restrict__ out, long n, int splits, int accumulate) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -467,7 +84,7 @@ __global__ void __launch_bounds__(256) k_relayout_batch(const fd_relayout_job* _
                 const unsigned tap = (unsigned)(j.kh0 + j.dkh * (int)a) * (unsigned)j.KW + (unsigned)(j.kw0 + j.dkw * (int)bb);
                 j.dst[((size_t)(co0 + r) * T + t) * Ci + ci0 + c] = tile[r][c * KK + tap];
             }
-        } else if (j.mode == 3) {                        // Winograd U[t][co][ky][ci] (conv_wino.hip), ci fastest
+        } else if (j.mode == 3) {                        // Winograd U[t][co][ky][ci] (conv_wino_route.hip: k_wino_weight), ci fastest
             const size_t n = (size_t)Co * 3 * Ci;
             for (unsigned i = threadIdx.x; i < nco * 3 * nci; i += 256) {
                 const unsigned c = i % nci, q = i / nci, ky = q % 3, r = q / 3;
@@ -500,7 +117,7 @@ __global__ void __launch_bounds__(256) k_relayout_batch(const fd_relayout_job* _
                 float* o = dg ? j.dst + ((size_t)(ci0 + c) * 4 + ri) * Co + co0 + r : j.dst + ((size_t)(co0 + r) * 4 + ri) * Ci + ci0 + c;
                 o[0] = v[0]; o[n] = 0.5f * (v[0] + v[1] + v[2]); o[2 * n] = 0.5f * (v[0] - v[1] + v[2]); o[3 * n] = v[2];
             }
-        } else if (j.mode == 11 || j.mode == 12) {       // F(2x2, 3x3): the limb image of U2 (conv_wino.hip: wino_limb_piece); 12: of the flipped kernel, m = ci
+        } else if (j.mode == 11 || j.mode == 12) {       // F(2x2, 3x3): the limb image of U2 (conv_wino_slab.hip: wino_limb_piece); 12: of the flipped kernel, m = ci
             const bool dg = j.mode == 12;
             const unsigned nm = dg ? nci : nco, nk8 = (dg ? nco : nci) / 8;
             const long Mrows = dg ? Ci : Co;
@@ -721,89 +338,6 @@ __global__ void k_channel_sum_fin(const float* __restrict__ part, float* __restr
     out[c] = s;
 }
 
-// ------------------------------------------------------------------------------------------------
-template <int TA, int TB>
-int launch_gemm(const GemmArgs& g, hipStream_t st) {
-    const long Np = (long)g.Nb * g.NY * g.NX;
-    GemmArgs a = g;
-    auto go = [&](auto kern, int BM, int BN, int nt) {
-        const int gx = fd_cdiv(Np, BN), gy = fd_cdiv(g.M, BM);
-        a.xcd_swizzle = (gx % 8 == 0 && gx >= 16) ? 1 : 0;
-        hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(nt), 0, st, a);
-    };
-    // pick the largest tile that still yields >= ~2 workgroups per CU
-    auto blocks = [&](int BM, int BN) { return (long)fd_cdiv(Np, BN) * fd_cdiv(g.M, BM); };
-    constexpr bool CAN_NORM = (TA == 7 && TB == 7);
-    if (g.in_norm && !CAN_NORM) { fd_set_error("conv: in_norm is only built for the 7x7 stem"); return -1; }
-    if (CAN_NORM && g.in_norm) {
-        if (blocks(64, 128) >= 512) go(k_gather_gemm<TA, TB, 2, 2, 1, 2, CAN_NORM>, 64, 128, 256);
-        else go(k_gather_gemm<TA, TB, 2, 2, 1, 1, CAN_NORM>, 64, 64, 256);
-        return 0;
-    }
-    if (g.M <= 32) {
-        go(k_gather_gemm<TA, TB, 1, 4, 1, 1, false>, 32, 128, 256);
-    } else if (g.M >= 128 && blocks(128, 128) >= 512) {
-        go(k_gather_gemm<TA, TB, 2, 2, 2, 2, false>, 128, 128, 256);
-    } else if (blocks(64, 128) >= 512) {
-        go(k_gather_gemm<TA, TB, 2, 2, 1, 2, false>, 64, 128, 256);
-    } else {
-        go(k_gather_gemm<TA, TB, 2, 2, 1, 1, false>, 64, 64, 256);
-    }
-    return 0;
-}
-
-int dispatch_gemm(int TA, int TB, const GemmArgs& g, hipStream_t st) {
-    if (TA == 1 && TB == 1) return launch_gemm<1, 1>(g, st);
-    if (TA == 3 && TB == 3) return launch_gemm<3, 3>(g, st);
-    if (TA == 7 && TB == 7) return launch_gemm<7, 7>(g, st);
-    if (TA == 5 && TB == 5) return launch_gemm<5, 5>(g, st);
-    if (TA == 1 && TB == 2) return launch_gemm<1, 2>(g, st);
-    if (TA == 2 && TB == 1) return launch_gemm<2, 1>(g, st);
-    if (TA == 2 && TB == 2) return launch_gemm<2, 2>(g, st);
-    if (TA == 3 && TB == 4) return launch_gemm<3, 4>(g, st);
-    if (TA == 4 && TB == 3) return launch_gemm<4, 3>(g, st);
-    if (TA == 4 && TB == 4) return launch_gemm<4, 4>(g, st);
-    if (TA == 2 && TB == 3) return launch_gemm<2, 3>(g, st);
-    if (TA == 3 && TB == 2) return launch_gemm<3, 2>(g, st);
-    fd_set_error("conv: unsupported tap shape %dx%d", TA, TB);
-    return -1;
-}
-
-template <int TA, int TB>
-int launch_wgrad(const WgradArgs& g, int splits, hipStream_t st) {
-    constexpr bool CAN_REFL = (TA == 3 && TB == 3), CAN_NORM = (TA == 7 && TB == 7);
-    if (g.pad_mode == 1 && !CAN_REFL) { fd_set_error("conv wgrad: reflect padding is only built for 3x3"); return -1; }
-    if (g.in_norm && !CAN_NORM) { fd_set_error("conv wgrad: in_norm is only built for the 7x7 stem"); return -1; }
-    auto go = [&](auto kern, int BM, int BN) {
-        dim3 grid(fd_cdiv(g.J, BN), fd_cdiv(g.M, BM), splits);
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, g);
-    };
-    const bool refl = CAN_REFL && g.pad_mode == 1, norm = CAN_NORM && g.in_norm;
-    if (g.J <= 64) {
-        if (refl) go(k_wgrad<TA, TB, 2, 2, 1, 1, CAN_REFL, false>, 64, 64);
-        else if (norm) go(k_wgrad<TA, TB, 2, 2, 1, 1, false, CAN_NORM>, 64, 64);
-        else go(k_wgrad<TA, TB, 2, 2, 1, 1, false, false>, 64, 64);
-    } else if (g.M <= 32) {
-        if (refl) go(k_wgrad<TA, TB, 1, 4, 1, 1, CAN_REFL, false>, 32, 128);
-        else if (norm) go(k_wgrad<TA, TB, 1, 4, 1, 1, false, CAN_NORM>, 32, 128);
-        else go(k_wgrad<TA, TB, 1, 4, 1, 1, false, false>, 32, 128);
-    } else {
-        if (refl) go(k_wgrad<TA, TB, 2, 2, 1, 2, CAN_REFL, false>, 64, 128);
-        else if (norm) go(k_wgrad<TA, TB, 2, 2, 1, 2, false, CAN_NORM>, 64, 128);
-        else go(k_wgrad<TA, TB, 2, 2, 1, 2, false, false>, 64, 128);
-    }
-    return 0;
-}
-
-int dispatch_wgrad(int TA, int TB, const WgradArgs& g, int splits, hipStream_t st) {
-    if (TA == 1 && TB == 1) return launch_wgrad<1, 1>(g, splits, st);
-    if (TA == 3 && TB == 3) return launch_wgrad<3, 3>(g, splits, st);
-    if (TA == 7 && TB == 7) return launch_wgrad<7, 7>(g, splits, st);
-    if (TA == 5 && TB == 5) return launch_wgrad<5, 5>(g, splits, st);
-    fd_set_error("conv wgrad: unsupported kernel %dx%d", TA, TB);
-    return -1;
-}
-
 struct ConvShape {
     int Ho, Wo;
 };
@@ -856,7 +390,7 @@ void conv_log(const char* what, const char* path, const fd_conv_desc* d) {
     if (fd_tun().log) fprintf(stderr, "FDCONV %s %s N=%d Cin=%d H=%d W=%d Cout=%d K=%d s=%d pad_mode=%d\n", what, path, d->N, d->Cin, d->H, d->W, d->Cout, d->KH,
                               d->stride, d->pad_mode);
 }
-// 1-D Winograd F(2,3) path (conv_wino.hip): 3x3 stride-1 pad-1 convs with >= 64 output channels (its tile is 64 channels tall).
+// 1-D Winograd F(2,3) path (conv_wino_x.hip): 3x3 stride-1 pad-1 convs with >= 64 output channels (its tile is 64 channels tall).
 // layer1's 64x64 weight gradient (3 tiles x 256 pixel-splits) is 10 % slower than the direct kernel when run alone and still the
 // better choice inside the step (449.6 vs 442 images/s): what the step is short of is MFMA cycles, not launch latency
 inline bool wino_use_wgrad(const fd_conv_desc* d) { return fd_tun().wino_wgrad != 0 && wino_wgrad_ok(d); }
@@ -939,10 +473,10 @@ inline int wino_layout_mode(const fd_conv_desc* g, bool dgrad) {
 // Routing: the kernel family of a convolution, its weight layouts and its buffer sizes, decided ONCE per (descriptor, direction) by
 // route_fwd / route_dgrad / route_wgrad from the descriptor and fd_tuning alone.  The size queries, fd_conv2d_relayout_jobs and the
 // launchers all read the route; only pointer-dependent refinements stay at launch (stem7 without a bias, the 16-byte alignment of
-// the limb weight gradients, the alignment checks inside conv_wino.hip).
+// the limb weight gradients, the alignment checks inside wino_conv_launch).
 //   C1 one-output-channel stencil (conv_c1.hip), N16 16 / 32-channel 3x3 blocks (conv_n16.hip), STEM7 / STEM_WGRAD 7x7 stems
 //   (conv_stem.hip / conv_narrow.hip), NARROW narrow weight gradients (conv_narrow.hip), LIMB_1X1 / LIMB_S2 1x1 stride-1 GEMM and
-//   stride-2 implicit GEMM on bf16 limbs (conv_limb.hip), WINO Winograd on `g` (conv_wino.hip), DIRECT implicit GEMM (conv_fast.hip),
+//   stride-2 implicit GEMM on bf16 limbs (conv_limb.hip), WINO Winograd on `g` (conv_wino*.hip), DIRECT implicit GEMM (conv_fast.hip),
 //   GENERIC gather GEMM (this file); reflect-padded data gradients: WINO_PADDED one Winograd convolution over the zero-bordered dY
 //   (`g`) + fold, RING_* the interior on the Winograd (`g`) / 16-channel / implicit-GEMM kernel + the ring, DIRECT / GENERIC the
 //   padded grid + fold.
@@ -1165,7 +699,7 @@ int conv2d_fwd_impl(const fd_conv_desc* d, const Route& r, const float* x, const
     }
     default: break;
     }
-    GemmArgs g = {};
+    GemmProblem g = {};
     g.A = w; g.X = x; g.Y = y; g.bias = bias;
     g.M = d->Cout; g.K = d->Cin * d->KH * d->KW;
     g.Nb = d->N; g.C = d->Cin; g.Hi = d->H; g.Wi = d->W;
@@ -1227,7 +761,7 @@ int bwd_data_impl(const fd_conv_desc* d, const Route& r, const float* gy, const 
     const bool fast = r.fam != Fam::GENERIC;
 
     // common geometry of "a conv over gy": channels = Cout, spatial = Ho x Wo
-    GemmArgs g = {};
+    GemmProblem g = {};
     g.X = gy; g.bias = nullptr; g.act = 0; g.in_norm = 0; g.pad_mode = 0;
     g.M = d->Cin; g.Nb = d->N; g.C = d->Cout; g.Hi = s.Ho; g.Wi = s.Wo;
     auto run = [&](const float* A, int TA, int TB, const float* add) -> int {
@@ -1497,7 +1031,7 @@ extern "C" int fd_conv2d_bwd_weight(const fd_conv_desc* d, const float* x, const
     default: {
         const int sp = wgrad_splits(d, s);
         const bool staged = sp > 1 || accumulate;
-        WgradArgs g = {};
+        WgradProblem g = {};
         g.dY = gy; g.X = x; g.out = staged ? ws : gw;
         g.M = d->Cout; g.J = d->Cin * d->KH * d->KW;
         g.Nb = d->N; g.C = d->Cin; g.Hi = d->H; g.Wi = d->W;

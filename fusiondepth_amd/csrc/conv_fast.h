@@ -1,4 +1,5 @@
-// Internal interface between conv.hip (C-ABI entry points, shape logic) and conv_fast.hip (fast-path kernels).
+// Internal interfaces of the direct-convolution kernel units behind conv.hip: conv_fast.hip, conv_n16.hip, conv_c1.hip, conv_stem.hip,
+// conv_limb.hip.  (The Winograd units: conv_wino.h; the generic implicit GEMM: conv_generic.h; the narrow kernels: conv_narrow.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/fdhip.h"
@@ -55,30 +56,10 @@ int fast_weight_relayout(const float* W, float* A2, int Co, int Ci, int KH, int 
 int fast_wgrad_splits(int M, int C, int T, long Np);
 int fast_wgrad_launch(const FastWgradArgs& a, float* gw, int splits, int accumulate, hipStream_t st);
 
-// Y[i] = act(sum_z slabs[z][i] + bias[channel(i)]) - the deterministic split-K epilogue (also used by conv_wino.hip)
+// Y[i] = act(sum_z slabs[z][i] + bias[channel(i)]) - the deterministic split-K epilogue (also used by conv_wino_route.hip)
 int fast_splitk_finish_launch(const float* slabs, float* Y, const float* bias, long total, long slab_stride, int splits, long out_cs,
                               int M, int act, hipStream_t st, const float* add = nullptr);
 
-// conv_wino.hip: 3x3 stride-1 convolutions through the 1-D Winograd F(2,3) transform
-bool wino_fwd_ok(const fd_conv_desc* d);
-long wino_wt_floats(const fd_conv_desc* d);
-bool wino_fwd_2d(const fd_conv_desc* d);
-bool wino_fwd_limb(const fd_conv_desc* d);      // k_conv_wino2d_limb: the weight layout is the limb image of U2 (re-layout modes 11 / 12)
-long wino_ws_floats(const fd_conv_desc* d);
-int wino_weight_launch(const fd_conv_desc* d, const float* w, float* U, int flip, hipStream_t st);
-// the BatchNorm that follows a slab-route convolution, fused with the slab reduction (norm.hip: k_bn_train_small_slabs)
-struct BnAfterConv {
-    const float* weight; const float* bias; const float* residual; float* out;
-    float* running_mean; float* running_var; float* save_mean; float* save_invstd;
-    int groups; float eps, momentum; int relu;
-};
-bool bn_small_slabs_ok(int N, int C, int H, int W, int groups);
-int bn_small_slabs_launch(const float* slabs, long slab_stride, int ksplit, float* y, const BnAfterConv& bn, int N, int C, int H, int W,
-                          hipStream_t st);
-bool wino_fwd_slab_route(const fd_conv_desc* d);
-int wino_conv_launch(const fd_conv_desc* d, const float* x, const float* U, const float* bias, float* y, float* ws, hipStream_t st,
-                     const float* add = nullptr, float* stat_part = nullptr, const BnAfterConv* bn = nullptr);
-int wino_stat_slots(const fd_conv_desc* d);
 // conv_n16.hip: 3x3 stride-1 convolutions with 16 / 32 channels on either side (the decoder's full-resolution blocks)
 bool n16_shape_ok(const fd_conv_desc* d, int M, int C);
 int n16_launch(const fd_conv_desc* d, int M, int C, const float* x, const float* w, const float* bias, float* y, int flip,
@@ -90,9 +71,6 @@ int c1_dgrad_launch(const fd_conv_desc* d, const float* gy, const float* w, floa
 // conv_stem.hip: the 7x7 stride-2 encoder stems (2..6 input channels) on a patch-staged MFMA kernel
 bool stem7_fwd_ok(const fd_conv_desc* d);
 int stem7_fwd_launch(const fd_conv_desc* d, const float* x, const float* w, const float* bias, float* y, hipStream_t st);
-bool wino_wgrad_ok(const fd_conv_desc* d);
-long wino_wgrad_ws_floats(const fd_conv_desc* d);
-int wino_wgrad_launch(const fd_conv_desc* d, const float* x, const float* gy, float* gw, float* ws, int accumulate, hipStream_t st);
 // gw[m][c][t] (+)= sum_z slabs[z][m][t][c]
 int fast_wgrad_finish_launch(const float* slabs, float* gw, int M, int C, int T, int splits, int accumulate, hipStream_t st);
 

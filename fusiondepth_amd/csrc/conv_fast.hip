@@ -1,7 +1,7 @@
 // Fast path of the FP32 MFMA implicit-GEMM convolution for channel counts that are multiples of 16 (every
 // ResNet / decoder / pose conv except the 7x7 stems, 1-channel dispconv gradients and 12-channel pose output).
 //
-// What changed w.r.t. the generic kernel in conv.hip (measured there: ~19 VALU per MFMA, 25-40 TFLOP/s):
+// What changed w.r.t. the generic kernel in conv_generic.hip (measured there: ~19 VALU per MFMA, 25-40 TFLOP/s):
 //   * GEMM-K is ordered (tap, channel) instead of (channel, tap): a K-chunk = ONE tap x BKC consecutive channels,
 //     so the tap's bounds / reflect logic runs once per chunk and the BKC loads of a thread are
 //     base + i * stride (one v_add each) with a wave-uniform base pointer (SGPR) + 32-bit lane offsets;
@@ -566,13 +566,7 @@ void launch_cfg(const FastGemmArgs& a, int splits, hipStream_t st) {
     FastGemmArgs g = a;
     g.xcd_swizzle = (gx % 8 == 0 && gx >= 16) ? 1 : 0;
     const size_t lds = sizeof(float) * 2 * BKC * ((BM + 1) + BN);
-    auto kern = k_conv_fast<WAVES_M, WAVES_N, WM, WN, BKC>;
-    static FdLdsAttrOnce attr_set;
-    if (attr_set.needed()) {   // allow > 64 KiB of dynamic LDS
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set.mark();
-    }
-    hipLaunchKernelGGL(kern, dim3(gx, gy, splits), dim3(64 * WAVES_M * WAVES_N), lds, st, g);
+    fd_launch_lds<k_conv_fast<WAVES_M, WAVES_N, WM, WN, BKC>>(dim3(gx, gy, splits), dim3(64 * WAVES_M * WAVES_N), lds, st, g);
 }
 
 }  // namespace
@@ -628,13 +622,7 @@ void launch_grp(const FastGemmArgs& a, const FastGemmGroup& q, hipStream_t st) {
     for (int j = 0; j < q.n; ++j) { grp.first_bx[j] = gx; gx += fd_cdiv((long)a.Nb * q.NY[j] * q.NX[j], BN); }
     grp.first_bx[q.n] = gx;
     const size_t lds = sizeof(float) * 2 * BKC * ((BM + 1) + BN);
-    auto kern = k_conv_fast_grp<WAVES_M, WAVES_N, WM, WN, BKC>;
-    static FdLdsAttrOnce attr_set;
-    if (attr_set.needed()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set.mark();
-    }
-    hipLaunchKernelGGL(kern, dim3(gx, fd_cdiv(a.M, BM), 1), dim3(64 * WAVES_M * WAVES_N), lds, st, a, grp);
+    fd_launch_lds<k_conv_fast_grp<WAVES_M, WAVES_N, WM, WN, BKC>>(dim3(gx, fd_cdiv(a.M, BM), 1), dim3(64 * WAVES_M * WAVES_N), lds, st, a, grp);
 }
 }  // namespace
 

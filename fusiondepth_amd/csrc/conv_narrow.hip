@@ -357,20 +357,9 @@ int narrow_wgrad_launch(const fd_conv_desc* d, const float* x, const float* gy, 
     if (cg == 1) {
         hipLaunchKernelGGL(k_wgrad_narrow<1>, dim3(blocks), dim3(256), lds, st, a);
     } else if (mg == 2) {                       // the Refiner decoder's 32 -> 32 layers (refine_decoder: upconv(1,*) / (0,*) after padding)
-        static FdLdsAttrOnce attr2;
-        if (attr2.needed()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_narrow<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-            attr2.mark();
-        }
-        hipLaunchKernelGGL((k_wgrad_narrow<2, 2>), dim3(blocks), dim3(256), lds, st, a);
+        fd_launch_lds<k_wgrad_narrow<2, 2>>(dim3(blocks), dim3(256), lds, st, a);
     } else {
-        static FdLdsAttrOnce attr;
-        if (attr.needed()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_narrow<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr.mark();
-        }
-        hipLaunchKernelGGL(k_wgrad_narrow<2>, dim3(blocks), dim3(256), lds, st, a);
+        fd_launch_lds<k_wgrad_narrow<2>>(dim3(blocks), dim3(256), lds, st, a);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { fd_set_error("k_wgrad_narrow launch failed: %s", hipGetErrorString(e)); return (int)e; }

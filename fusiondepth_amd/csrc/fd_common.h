@@ -31,8 +31,8 @@ void fd_set_error(const char* fmt, ...);
         }                                                                                  \
     } while (0)
 
-// hipFuncAttributeMaxDynamicSharedMemorySize (> 64 KiB of dynamic LDS) is a PER-DEVICE property of a kernel: a launcher keeps one
-// of these per kernel family - bit d says that device d has the attribute.  Two host threads may both set it (idempotent); the bit
+// hipFuncAttributeMaxDynamicSharedMemorySize (> 64 KiB of dynamic LDS) is a PER-DEVICE property of a kernel: fd_launch_lds keeps one
+// of these per kernel - bit d says that device d has the attribute.  Two host threads may both set it (idempotent); the bit
 // is published after the attribute is in place, so a thread that sees it never launches without.
 struct FdLdsAttrOnce {
     std::atomic<unsigned long long> done{0};
@@ -40,6 +40,17 @@ struct FdLdsAttrOnce {
     bool needed() const { return !((done.load(std::memory_order_acquire) >> dev_bit()) & 1ull); }
     void mark() { done.fetch_or(1ull << dev_bit(), std::memory_order_release); }
 };
+// The launch of a kernel that may ask for more than 64 KiB of dynamic LDS: the kernel is the template argument, so every
+// instantiation that is launched at all has raised its own limit on the current device first - there is no list to keep.
+template <auto Kern, class... A>
+void fd_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    static FdLdsAttrOnce attr;
+    if (attr.needed()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr.mark();
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+}
 
 static inline int fd_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

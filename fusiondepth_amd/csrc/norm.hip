@@ -8,7 +8,7 @@
 // slice order by every consumer.
 #include "../../include/fdhip.h"
 #include "fd_common.h"
-#include "conv_fast.h"
+#include "conv_wino.h"      // BnAfterConv, bn_small_slabs_*
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(NT) k_bn_train_small(const float* __restrict__
     }
 }
 
-// k_bn_train_small fed by the SLABS of the F(2x2, 3x3) convolution in front of it (conv_wino.hip: k_conv_wino2d / _m128 write the
+// k_bn_train_small fed by the SLABS of the F(2x2, 3x3) convolution in front of it (conv_wino_x.hip / conv_wino_slab.hip: k_conv_wino2d / _m128 write the
 // horizontally transformed products S_ri [N][C][H/2][W] per row component ri and channel split): the slab reduction and the vertical
 // output transform  y[2 ty] = S0 + S1 + S2,  y[2 ty + 1] = S1 - S2 - S3  of k_wino2d_finish (same order of additions: the convolution
 // output is bit-identical) happen where the values are needed - one launch and one pass over y less per deep-layer convolution.

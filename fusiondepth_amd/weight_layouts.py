@@ -206,7 +206,7 @@ def weight_layout(w, cache_id, kind, nfloats, desc=None):
     if cache_id is None:
         return torch.empty((nfloats,), device=w.device, dtype=torch.float32), 0
     # nfloats is part of the key: the layout FORMAT of a weight depends on the kernel family its input shape is routed to (12 or 16
-    # floats per tap: conv_wino.hip::wino_fwd_mode looks at N*H*W), so a weight used at two batch sizes (the stacked training batch and
+    # floats per tap: conv_wino_route.hip::wino_fwd_mode looks at N*H*W), so a weight used at two batch sizes (the stacked training batch and
     # a smaller validation batch) keeps both layouts resident instead of rebuilding one over the other on every switch
     key = (cache_id, kind, nfloats)
     stamp = _layout_stamp(w)

@@ -848,7 +848,7 @@ def _wino_conv(x, w, bias, reflect, act=0):
     (2, 32, 16, 8, 12, True, 0),         # 16 output channels, two chunks per row component
 ])
 def test_winograd_conv_vs_float64_reference(N, Ci, Co, H, W, reflect, act, two_d, fdtune):
-    """conv_wino.hip through its own entry point against torch float64 conv2d: error within a few fp32 ulps of the output scale,
+    """The Winograd forward (conv_wino_route.hip and the kernel units behind it) through its own entry point against torch float64 conv2d: error within a few fp32 ulps of the output scale,
     i.e. no worse than the direct implicit GEMM (transform coefficients are +-1 and 1/2).  two_d = 1: F(2x2, 3x3) (k_conv_wino2d +
     k_wino2d_finish) forced onto every shape with an even height; 2: F(2x2, 3x3) with the 16 components in one workgroup
     (k_conv_wino2p, round 4) forced likewise; 0: F(2, 3) per kernel row everywhere."""
