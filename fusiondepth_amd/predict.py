@@ -4,9 +4,8 @@ the reference's ``inf_depth_map.py`` runs them (:53-84 model set, :159-172 ``pro
     p = Predictor(folder, num_layers=18)
     disp = p.predict(batch)[("disp", 0)]            # batch: "color_aug", 0, 0 and "2channel", as KITTIRAWBatches builds them
 
-The forward passes go through the same machinery as the Refiner's frozen block (``Refiner._run_module``): eval-mode networks
-under ``torch.no_grad``, kernel-side weight layouts derived once (the frozen weight cache), each network's libfdhip calls recorded
-once per input signature and replayed by one ``fd_replay`` call afterwards.
+The forward passes go through ``FrozenRunner``, which the Refiner's frozen block uses too: eval-mode networks under
+``torch.no_grad``, kernel-side weight layouts derived once (the frozen weight cache), recorded call sequences.
 """
 import os
 
@@ -15,8 +14,34 @@ import torch
 from . import functional as FD
 from . import networks
 from . import weight_layouts
+from .checkpoint import load_state_by_key
 
 PREDICTOR_MODELS = ("encoder", "beam_encoder", "depth")
+
+
+class FrozenRunner:
+    """Runs the networks of ``models`` that nothing trains.  Under no_grad and in eval mode a network's libfdhip calls are recorded
+    once per input signature and replayed by ONE ``fd_replay`` call afterwards (replay.py; ~45 launches per ResNet-18 encoder, ~40
+    per depth decoder), through ``replays[name]``.  With gradients enabled, in training mode, or for a network in ``trained``: eagerly."""
+
+    def __init__(self, models, owner, trained=()):
+        self.models, self.owner, self.trained = models, owner, trained
+        self.replays = {}
+
+    def run(self, name, *tensors):
+        net = self.models[name]      # ``depth`` takes the encoder features (+ the LiDAR encoder's) as a flat argument list
+        if name == "depth":
+            n = len(net.num_ch_enc)
+            call = lambda *f: net(list(f[:n]), beam_features=list(f[n:])) if len(f) > n else net(list(f))
+        else:
+            call = lambda x: list(net(x))
+        if name in self.trained or torch.is_grad_enabled() or net.training:
+            return call(*tensors)
+        rp = self.replays.get(name)
+        if rp is None:
+            from .replay import Replayable
+            rp = self.replays[name] = Replayable(call, lambda: list(net.parameters()) + list(net.buffers()), name="%s.%s" % (self.owner, name))
+        return rp(*tensors)
 
 
 class Predictor:
@@ -40,11 +65,10 @@ class Predictor:
         for p in params:
             p.requires_grad_(False)
         FD.enable_weight_cache(params, frozen=True)
-        self._replays = {}
+        self.frozen = FrozenRunner(self.models, "Predictor")
 
     def _load(self, folder):
-        """The three networks' tensors copied in place by key, as ``Refiner._load_pretrained`` does - but stricter: a key missing
-        from a file raises for the encoder too (the Refiner tolerates that one); extra keys of the encoder file are skipped."""
+        """Every key of every network must be in its file; extra keys of the encoder file are skipped."""
         folder = os.path.expanduser(folder)
         if not os.path.isdir(folder):
             raise FileNotFoundError("Cannot find a folder at {}".format(folder))
@@ -52,31 +76,8 @@ class Predictor:
             path = os.path.join(folder, "{}.pth".format(name))
             if not os.path.isfile(path):
                 raise FileNotFoundError("load_weights_folder: %s is missing" % path)
-            own = net.state_dict()
-            loaded = torch.load(path, map_location="cpu")
-            missing = [k for k in own if k not in loaded]
-            if missing:
-                raise RuntimeError("%s: missing keys %s" % (path, missing[:4]))
-            with torch.no_grad():
-                for k, v in loaded.items():
-                    if k in own:
-                        own[k].copy_(v)
+            load_state_by_key(net, path)
         weight_layouts.weights_replaced()
-
-    def _run_module(self, name, *tensors):
-        """``Refiner._run_module``: recorded once per input signature, replayed afterwards.  ``depth`` takes the encoder features
-        followed by the LiDAR encoder's as a flat argument list."""
-        net = self.models[name]
-        if name == "depth":
-            n = len(net.num_ch_enc)
-            call = lambda *f: net(list(f[:n]), beam_features=list(f[n:]))
-        else:
-            call = lambda x: list(net(x))
-        rp = self._replays.get(name)
-        if rp is None:
-            from .replay import Replayable
-            rp = self._replays[name] = Replayable(call, lambda: list(net.parameters()) + list(net.buffers()), name="Predictor." + name)
-        return rp(*tensors)
 
     def predict(self, batch):
         """inf_depth_map.py:159-172 -> {("disp", s)} for the decoder's scales."""
@@ -84,6 +85,6 @@ class Predictor:
         if color.device != self.device:
             color, two = color.to(self.device), two.to(self.device)
         with torch.no_grad():
-            features = self._run_module("encoder", color.contiguous())
-            beam_features = self._run_module("beam_encoder", two.contiguous())
-            return dict(self._run_module("depth", *features, *beam_features))
+            features = self.frozen.run("encoder", color.contiguous())
+            beam_features = self.frozen.run("beam_encoder", two.contiguous())
+            return dict(self.frozen.run("depth", *features, *beam_features))

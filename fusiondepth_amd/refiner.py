@@ -19,13 +19,14 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import dp
 from . import functional as FD
 from . import tuning
 from . import networks
 from . import weight_layouts
+from .checkpoint import load_state_by_key
 from .layers import disp_to_depth
-from .trainer import Outputs, Trainer, derived_hparams
+from .predict import FrozenRunner
+from .trainer import Outputs, Trainer
 
 REFINER_MODEL_ORDER = ["encoder", "beam_encoder", "beam_encoder_pose", "depth", "pose_encoder", "pose", "refine2d_decoder"]
 
@@ -47,96 +48,40 @@ class Refiner(Trainer):
     """Same method names as the reference's ``Refiner``; batches are dicts with the reference's keys (+ ``"inf_gdc"``)."""
 
     def __init__(self, options, device=None, rank=0, world_size=1, verbose=True):
-        self.opt = options
-        self.verbose = verbose
-        if self.opt.no_cuda or not torch.cuda.is_available():
-            raise RuntimeError("fusiondepth_amd.Refiner needs an MI355X: there is no CPU path (use oracle/ for CPU checks)")
-        self.opt.clone_gdc, self.opt.refine_2d = True, True                                   # refiner.py:29-30
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.index is not None:
-            torch.cuda.set_device(self.device)           # every raw-stream launch below targets the current device
-        self.rank, self.world_size = rank, world_size
-        self.materialize_outputs = False
-        self.log_path = os.path.join(self.opt.log_dir, self.opt.model_name)
-        vram = torch.cuda.get_device_properties(self.device).total_memory / 1024 ** 3
-        hp = derived_hparams(self.opt, vram)                                                  # refiner.py:32-45 (same rule)
-        self.opt.num_epochs = hp["num_epochs"]
-        self.accumulate_step, self.learning_rate = hp["accumulate_step"], hp["learning_rate"]
-        self.scheduler_step_size, self.batch_size = hp["scheduler_step_size"], hp["micro_batch"]
-        self.eval_scales = self.opt.scales
+        options.clone_gdc, options.refine_2d = True, True                                     # refiner.py:29-30
+        super().__init__(options, device=device, rank=rank, world_size=world_size, verbose=verbose)
+        self.frozen = FrozenRunner(self.models, "Refiner", trained=self.trained)
+        self._frozen_stream, self._prefetched = None, None
+        self.parallel_streams = tuning.host.refiner_streams
+        self.stack_microbatches = False
+        self._groups = 1
+
+    # ---- the steps of Trainer.__init__ that differ (refiner.py:80-167) -------------------------------
+    _SI_CONSTANTS = dict(si_depth_scale=1.0, si_beam_scale=1.0, si_lo=1e-3)                   # refiner.py:557-563
+
+    def _check_options(self):
         assert self.opt.height % 32 == 0 and self.opt.width % 32 == 0, "'height' / 'width' must be multiples of 32"
-        assert self.opt.frame_ids[0] == 0, "frame_ids must start with 0"
         if self.opt.train_entire_net:
-            # refiner.py:306-313 computes `features` only under `if not self.opt.train_entire_net`, so the reference itself
-            # stops with an UnboundLocalError at the first batch: there is no behaviour to reproduce
             raise NotImplementedError("--train_entire_net: the reference's Refiner.process_batch (refiner.py:306-313) never "
                                       "computes the encoder features on that path (UnboundLocalError at the first batch)")
         if self.opt.use_stereo or self.opt.predictive_mask or self.opt.pose_model_type != "separate_resnet" or \
                 self.opt.v1_multiscale or not self.opt.beam_encoder:
             raise NotImplementedError("Refiner: only the default path (frozen nets, separate_resnet pose net, beam encoder, "
                                       "full-resolution sampling) is implemented")
-        self.num_scales = len(self.opt.scales)
-        self.num_input_frames = len(self.opt.frame_ids)
-        self.num_pose_frames = 2 if self.opt.pose_model_input == "pairs" else self.num_input_frames
-        self.use_pose_net = True
 
-        m = {}                                                                                # refiner.py:80-160
-        m["encoder"] = networks.ResnetEncoder(self.opt.num_layers, False, cat4beam_to_color=self.opt.cat_4beam_to_color,
-                                              cat2channel=self.opt.cat2start)
-        m["beam_encoder"] = networks.ResnetEncoder(self.opt.num_layers, False, beam_encoder=True)
-        m["beam_encoder_pose"] = networks.ResnetEncoder(self.opt.num_layers, False, num_input_images=self.num_pose_frames,
-                                                        beam_encoder=True)
-        m["depth"] = networks.DepthDecoder(m["encoder"].num_ch_enc, self.opt.scales, cat2end=self.opt.cat2end)
-        m["pose_encoder"] = networks.ResnetEncoder(self.opt.num_layers, False, num_input_images=self.num_pose_frames)
-        m["pose"] = networks.PoseDecoder(m["pose_encoder"].num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
+    def _build_networks(self):
+        """refiner.py:80-160: the Trainer's networks (never ImageNet weights: they are loaded), frozen, and the refine decoder, the one
+        network that is trained.  (``stem_feature_needed``, which the Trainer clears for its pose encoders, is read in training mode only.)"""
+        m = super()._build_networks(pretrained=False)[0]
         m["refine2d_decoder"] = networks.DepthDecoder(m["encoder"].num_ch_enc, self.opt.scales, road=True,
                                                       catxy=(self.opt.catxy == "true"), deep=(self.opt.refine2d_deep == "true"))
-        self.models = {k: m[k].to(self.device) for k in REFINER_MODEL_ORDER}
-        self._load_pretrained()                                                                # refiner.py:56-60, 84-152
-        if world_size > 1:
-            dp.broadcast_module_state(self.models.values())
-        self.parameters_to_train = list(self.models["refine2d_decoder"].parameters())          # refiner.py:148-160
-        for k, net in self.models.items():
-            if k != "refine2d_decoder":
-                for p in net.parameters():
-                    p.requires_grad_(False)          # frozen: no data gradient is propagated into them either
+        return m, REFINER_MODEL_ORDER, ["refine2d_decoder"]
 
-        self.flat = dp.FlatParameters(self.parameters_to_train)
-        FD.evict_dead_weight_layouts()
-        FD.enable_weight_cache(self.parameters_to_train)
-        FD.enable_direct_grad(self.parameters_to_train)
-        # the refine decoder is the step's serial chain (one batch-6 launch at a time): its weight gradients - leaves of the backward
-        # graph - run on a side stream beside the following layers' data gradients, like the depth decoder's in the Trainer
-        if "refine2d_decoder" in tuning.host.side_wgrad:
-            FD.enable_side_wgrad(self.parameters_to_train)
-        # the frozen stage-1 networks: kernel-side weight layouts derived once, not on every call
-        FD.enable_weight_cache([p for k, net in self.models.items() if k != "refine2d_decoder" for p in net.parameters()], frozen=True)
-        self.exp_avg = torch.zeros_like(self.flat.flat_param)
-        self.exp_avg_sq = torch.zeros_like(self.flat.flat_param)
-        self.adam_step_count = 0
-        self.lr = self.learning_rate
-        self.adam_state = torch.tensor([0.0, self.lr], device=self.device)
-        self._graph, self._streams = None, []
-        self._replays = {}
-        self._frozen_stream, self._prefetched = None, None
-        self.parallel_streams = tuning.host.refiner_streams
-        self.stack_microbatches = False
-        self._groups = 1
-        self.grad_sync = dp.GradientSynchronizer(self.flat, world_size)
-        self.photo_options = FD.PhotoOptions(self.opt.min_depth, self.opt.max_depth, self.opt.no_ssim, self.opt.avg_reprojection,
-                                             self.opt.gdc_loss_threshold, self.opt.si_var, si_depth_scale=1.0,
-                                             si_beam_scale=1.0, si_lo=1e-3)
-        self.depth_metric_names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
-        self.epoch, self.step, self.batch_idx = 0, 0, 0
-        self.best = 10.0
-        self.start_time = time.time()
-        self.set_train()
-        self.flat.zero_grad()
-        if verbose:
-            n = sum(p.numel() for p in self.parameters_to_train)
-            print("fusiondepth_amd.Refiner: training refine2d_decoder, %d parameters (%.1f MB fp32), lr %.3g" % (n, n * 4 / 1e6, self.lr))
+    def _announce(self):
+        n = sum(p.numel() for p in self.parameters_to_train)
+        print("fusiondepth_amd.Refiner: training refine2d_decoder, %d parameters (%.1f MB fp32), lr %.3g" % (n, n * 4 / 1e6, self.lr))
 
-    def _load_pretrained(self):
+    def _load_weights(self):
         """refiner.py:56-60 + the ``load_state_dict`` after every constructor (:84-152): the frozen depth / pose networks come
         from ``--refine_load_weights_folder`` (stage-1 ``Trainer.save_model`` output; the encoder file also carries height /
         width / use_stereo, filtered by key like the reference does), ``refine2d_decoder.pth`` is optional (resume).
@@ -154,21 +99,8 @@ class Refiner(Trainer):
                 if name == "refine2d_decoder":
                     continue
                 raise FileNotFoundError("refine_load_weights_folder: %s is missing" % path)
-            own = net.state_dict()
-            loaded = torch.load(path, map_location="cpu")
-            missing = [k for k in own if k not in loaded]
-            if missing and name != "encoder":
-                raise RuntimeError("%s: missing keys %s" % (path, missing[:4]))
-            with torch.no_grad():
-                for k, v in loaded.items():
-                    if k in own:
-                        own[k].copy_(v)
+            load_state_by_key(net, path, allow_missing=(name == "encoder"))
         weight_layouts.weights_replaced()
-
-    def set_train(self):
-        """refiner.py:80-160: the depth / pose networks stay in eval mode; only the refine decoder trains."""
-        for k, net in self.models.items():
-            net.train() if k == "refine2d_decoder" else net.eval()
 
     # ------------------------------------------------------------------------------------------------
     def refine_inputs(self, inputs, outputs):
@@ -216,11 +148,6 @@ class Refiner(Trainer):
             else:
                 res[("disp", scale)] = torch.cat([scaled_disp, two_cha], 1)
         return res
-
-    def _to_device(self, inputs):
-        for key, ipt in inputs.items():
-            if torch.is_tensor(ipt) and ipt.device != self.device:
-                inputs[key] = ipt.to(self.device)
 
     def _frozen_block(self, inputs, val):
         """Everything of refiner.py:299-330 that involves only the batch and frozen networks (no parameter that is trained, no
@@ -317,31 +244,14 @@ class Refiner(Trainer):
         return features, beam_features, depth, poses
 
     def _run_module(self, name, *tensors):
-        """A frozen stage-1 network under no_grad: its libfdhip calls are recorded once per input signature and replayed by ONE
-        ``fd_replay`` call afterwards (replay.py; ~45 launches per ResNet-18 encoder, ~40 per depth decoder: the step was host-bound).
-        ``depth`` takes the encoder features (+ the LiDAR encoder's) as a flat argument list."""
-        net = self.models[name]
-        if name == "depth":
-            n = len(net.num_ch_enc)
-            call = lambda *f: net(list(f[:n]), beam_features=list(f[n:])) if len(f) > n else net(list(f))
-        else:
-            call = lambda x: list(net(x))
-        if name == "refine2d_decoder" or torch.is_grad_enabled() or net.training:
-            return call(*tensors)
-        rp = self._replays.get(name)
-        if rp is None:
-            from .replay import Replayable
-            rp = self._replays[name] = Replayable(call, lambda: list(net.parameters()) + list(net.buffers()), name="Refiner." + name)
-        return rp(*tensors)
+        """A stage-1 network through the shared frozen-network runner (predict.FrozenRunner); the refine decoder runs eagerly."""
+        return self.frozen.run(name, *tensors)
 
     def generate_images_pred(self, inputs, outputs, frame_ids):
         """refiner.py:487-541 fused with the per-pixel part of compute_losses; the SI term is the GDC loss (compute_losses)."""
         fids = [f for f in frame_ids[1:]]
         if not fids:
-            for scale in self.opt.scales:
-                disp = FD.bilinear_upsample(outputs[("disp", scale)], (self.opt.height, self.opt.width))
-                outputs[("depth", 0, scale)] = disp_to_depth(disp, self.opt.min_depth, self.opt.max_depth)[1]
-            return
+            return super().generate_images_pred(inputs, outputs, frame_ids)      # validation: depth only
         automask = not self.opt.disable_automasking
         ident = self.identity_losses(inputs, 0) if automask else None
         noise_in = inputs.get("_noise")

@@ -4,9 +4,10 @@ compute_losses, compute_depth_losses, save_model/load_model), driven by ``option
 
 What differs, by design:
   * every op is a libfdhip kernel; per pyramid scale, generate_images_pred + the photometric/SI part of
-    compute_losses are ONE fused kernel (csrc/photometric.hip) — the reference's ("depth",0,s), ("sample",f,s),
-    ("color",f,s) tensors are only materialised when ``materialize_outputs`` is set (logging / tests);
-  * all trainable tensors live in one flat buffer: Adam is one fused launch, and data-parallel training
+    compute_losses are fused - in the default configuration ALL scales in one kernel (csrc/photometric_ms.hip), in the flag
+    variants one kernel per scale (csrc/photometric.hip) — the reference's ("depth",0,s), ("sample",f,s), ("color",f,s)
+    tensors are only materialised when ``materialize_outputs`` is set (logging / tests);
+  * all trainable tensors live in one flat buffer: Adam is one fused launch (optim.py), and data-parallel training
     (one process per GPU, RCCL all-reduce over xGMI, see dp.py) is added — the reference is single-GPU;
   * the data loader / wandb / tensorboard shell of the reference is out of scope (SURVEY.md §2 rows 11,12):
     batches are dicts with the reference's schema, e.g. from ``synthetic.make_batch``.
@@ -17,7 +18,6 @@ import contextlib
 import os
 import time
 
-import numpy as np
 import torch
 
 from . import dp
@@ -25,6 +25,8 @@ from . import functional as FD
 from . import networks
 from . import tuning
 from . import weight_layouts
+from .checkpoint import load_state_by_key
+from .optim import FlatAdam
 from .layers import SSIM, BackprojectDepth, Project3D, disp_to_depth, transformation_from_parameters
 
 MODEL_ORDER = ["encoder", "beam_encoder", "beam_encoder_pose", "depth", "pose_encoder", "pose", "predictive_mask"]
@@ -99,12 +101,11 @@ def derived_hparams(opt, vram_gib):
 
 
 class Trainer:
-    _pose_on_main = False      # True only inside train_step_graphed: the captured step keeps every fork on the capture stream
-
     def __init__(self, options, device=None, rank=0, world_size=1, materialize_outputs=False, verbose=True):
         self.opt = options
         if self.opt.no_cuda or not torch.cuda.is_available():
-            raise RuntimeError("fusiondepth_amd.Trainer needs an MI355X: there is no CPU path (use oracle/ for CPU checks)")
+            raise RuntimeError("fusiondepth_amd.%s needs an MI355X: there is no CPU path (use oracle/ for CPU checks)"
+                               % type(self).__name__)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.index is not None:
             torch.cuda.set_device(self.device)           # libfdhip launches on the CURRENT device's streams (see _lib.stream)
@@ -117,19 +118,83 @@ class Trainer:
         self.opt.num_epochs = hp["num_epochs"]                                                # trainer.py:28
         self.accumulate_step = hp["accumulate_step"]
         self.learning_rate = hp["learning_rate"]
-        self.scheduler_step_size = hp["scheduler_step_size"]
         self.batch_size = hp["micro_batch"]                                                   # per-process micro-batch
         self.log_path = os.path.join(self.opt.log_dir, self.opt.model_name)
 
-        assert self.opt.height % 32 == 0, "'height' must be a multiple of 32"                 # trainer.py:47-48
-        assert self.opt.width % 32 == 0, "'width' must be a multiple of 32"
         assert self.opt.frame_ids[0] == 0, "frame_ids must start with 0"
         self.num_scales = len(self.opt.scales)
         self.num_input_frames = len(self.opt.frame_ids)
         self.num_pose_frames = 2 if self.opt.pose_model_input == "pairs" else self.num_input_frames
         self.use_pose_net = not (self.opt.use_stereo and self.opt.frame_ids == [0])          # trainer.py:61
+        self._check_options()
         if self.opt.use_stereo:
             self.opt.frame_ids = list(self.opt.frame_ids) + ["s"]                            # trainer.py:63-64
+
+        m, order, trained = self._build_networks()
+        self.models = {k: m[k].to(self.device) for k in order if k in m}
+        if world_size > 1:
+            dp.broadcast_module_state(self.models.values())
+        self.trained = trained                       # the networks whose parameters are trained; the others are frozen
+        self.parameters_to_train = [p for k in trained for p in self.models[k].parameters()]
+        frozen = [p for k, net in self.models.items() if k not in trained for p in net.parameters()]
+        for p in frozen:
+            p.requires_grad_(False)                  # no data gradient is propagated into them either
+
+        # ---- optimiser (trainer.py:129-131): Adam + StepLR(gamma 0.1), on one flat buffer ----------------
+        self.flat = dp.FlatParameters(self.parameters_to_train)
+        FD.evict_dead_weight_layouts()         # cached layouts / re-layout plan of trainers that no longer exist
+        FD.enable_weight_cache(self.parameters_to_train)
+        FD.enable_direct_grad(self.parameters_to_train)
+        # a decoder is the serial section of its step: its weight gradients leave the main stream (pass_state.enable_side_wgrad)
+        for k in tuning.host.side_wgrad:
+            if k in trained:
+                FD.enable_side_wgrad(self.models[k].parameters())
+        FD.enable_weight_cache(frozen, frozen=True)      # kernel-side weight layouts derived once, not on every call
+        self.optim = FlatAdam(self.flat, self.learning_rate, hp["scheduler_step_size"])
+        self._graphed = None                   # graph_step.GraphedStep, from the first train_step_graphed on
+        self._streams = []
+        self.parallel_streams = True
+        # the accumulated micro-batches run as one stacked pass where the step has the default shape (see train_step);
+        # the flag variants without a separate pose encoder per frame pair run them one after the other like the reference
+        self.stack_microbatches = (self.use_pose_net and self.opt.pose_model_type == "separate_resnet"
+                                   and self.num_pose_frames == 2)
+        # opt-in (tuning.host.interleave): the four encoders issued block by block in turns instead of one after the other
+        # (networks.interleaved_forward).  Throughput-neutral on this host (the GPU is saturated either way), so the
+        # longer-tested sequential issue order stays the default.
+        self.interleave_encoders = bool(tuning.host.interleave)
+        # one bucket boundary per trained network: each network's backward runs on its own HIP stream
+        unused = [p for k in trained for n, p in self.models[k].named_parameters() if n.startswith("encoder.fc.")]
+        self.grad_sync = dp.GradientSynchronizer(self.flat, world_size, never_used=unused,
+                                                 segments=[len(list(self.models[k].parameters())) for k in trained])
+        self._load_weights()
+
+        # API-parity members (trainer.py:180-194); the fused kernel does not need baked pixel grids
+        if not self.opt.no_ssim:
+            self.ssim = SSIM()
+        self.backproject_depth, self.project_3d = {}, {}
+        for scale in self.opt.scales:
+            h, w = self.opt.height // (2 ** scale), self.opt.width // (2 ** scale)
+            self.backproject_depth[scale] = BackprojectDepth(self.batch_size, h, w)
+            self.project_3d[scale] = Project3D(self.batch_size, h, w)
+        self.photo_options = FD.PhotoOptions(self.opt.min_depth, self.opt.max_depth, self.opt.no_ssim,
+                                             self.opt.avg_reprojection, self.opt.gdc_loss_threshold, self.opt.si_var,
+                                             si_mode=self._lidar_term()[1], **self._SI_CONSTANTS)
+        self.depth_metric_names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
+        self.epoch, self.step, self.batch_idx = 0, 0, 0
+        self.best = 10.0
+        self.start_time = time.time()
+        self.set_train()
+        self.flat.zero_grad()
+        if verbose and rank == 0:
+            self._announce()
+
+    # ---- the steps of __init__ that the sibling drivers of the reference (completor.py, refiner.py) take differently ----
+    _SI_CONSTANTS = {}         # FD.PhotoOptions' si_* keywords where they are not the trainer's
+
+    def _check_options(self):
+        """The option combinations that are refused, with the reference's own reason."""
+        assert self.opt.height % 32 == 0, "'height' must be a multiple of 32"                 # trainer.py:47-48
+        assert self.opt.width % 32 == 0, "'width' must be a multiple of 32"
         shared = self.opt.pose_model_type == "shared"
         if shared and self.use_pose_net and self.opt.beam_encoder and self.num_pose_frames == 2:
             raise NotImplementedError(
@@ -146,8 +211,10 @@ class Trainer:
             assert self.opt.disable_automasking, \
                 "When using predictive_mask, please disable automasking with --disable_automasking"     # trainer.py:118-119
 
-        # ---- networks (trainer.py:66-127) --------------------------------------------------------------
-        pre = self.opt.weights_init == "pretrained"
+    def _build_networks(self, pretrained=None):
+        """trainer.py:66-127 -> (networks by name, their order in ``self.models``, the names of those that are trained; parameters
+        of the others are frozen)."""
+        pre = self.opt.weights_init == "pretrained" if pretrained is None else pretrained
         depth_layers, pose_layers = self._encoder_layers()
         m = {}
         m["encoder"] = networks.ResnetEncoder(depth_layers, pre, cat4beam_to_color=self.opt.cat_4beam_to_color,
@@ -170,67 +237,17 @@ class Trainer:
         for k in ("pose_encoder", "beam_encoder_pose"):           # PoseDecoder reads features[-1] only: their features[0] has no reader
             if k in m:
                 m[k].stem_feature_needed = False
-        self.models = {k: m[k].to(self.device) for k in MODEL_ORDER if k in m}
-        if world_size > 1:
-            dp.broadcast_module_state(self.models.values())
-        self.parameters_to_train = []
-        for k in self.models:
-            self.parameters_to_train += list(self.models[k].parameters())
+        return m, MODEL_ORDER, [k for k in MODEL_ORDER if k in m]
 
-        # ---- optimiser (trainer.py:129-131): Adam + StepLR(gamma 0.1), on one flat buffer ----------------
-        self.flat = dp.FlatParameters(self.parameters_to_train)
-        FD.evict_dead_weight_layouts()         # cached layouts / re-layout plan of trainers that no longer exist
-        FD.enable_weight_cache(self.parameters_to_train)
-        FD.enable_direct_grad(self.parameters_to_train)
-        # the depth decoder is the serial section of the step: its weight gradients leave the main stream (pass_state.enable_side_wgrad)
-        for k in tuning.host.side_wgrad:
-            if k in self.models:
-                FD.enable_side_wgrad(self.models[k].parameters())
-        self.exp_avg = torch.zeros_like(self.flat.flat_param)
-        self.exp_avg_sq = torch.zeros_like(self.flat.flat_param)
-        self.adam_step_count = 0
-        self.lr = self.learning_rate
-        self.adam_state = torch.tensor([0.0, self.lr], device=self.device)      # [step, lr] on the device (graph-safe)
-        self._graph = None
-        self._streams = []
-        self.parallel_streams = True
-        # the accumulated micro-batches run as one stacked pass where the step has the default shape (see train_step);
-        # the flag variants without a separate pose encoder per frame pair run them one after the other like the reference
-        self.stack_microbatches = (self.use_pose_net and self.opt.pose_model_type == "separate_resnet"
-                                   and self.num_pose_frames == 2)
-        # opt-in (tuning.host.interleave): the four encoders issued block by block in turns instead of one after the other
-        # (networks.interleaved_forward).  Throughput-neutral on this host (the GPU is saturated either way), so the
-        # longer-tested sequential issue order stays the default.
-        self.interleave_encoders = bool(tuning.host.interleave)
-        unused = [p for m in self.models.values() for n, p in m.named_parameters() if n.startswith("encoder.fc.")]
-        self.grad_sync = dp.GradientSynchronizer(self.flat, world_size, never_used=unused,
-                                                 segments=[len(list(m.parameters())) for m in self.models.values()])
+    def _load_weights(self):
         if self.opt.train_load_weights_folder is not None:
             self.load_model()
 
-        # API-parity members (trainer.py:180-194); the fused kernel does not need baked pixel grids
-        if not self.opt.no_ssim:
-            self.ssim = SSIM()
-        self.backproject_depth, self.project_3d = {}, {}
-        for scale in self.opt.scales:
-            h, w = self.opt.height // (2 ** scale), self.opt.width // (2 ** scale)
-            self.backproject_depth[scale] = BackprojectDepth(self.batch_size, h, w)
-            self.project_3d[scale] = Project3D(self.batch_size, h, w)
-        self.photo_options = FD.PhotoOptions(self.opt.min_depth, self.opt.max_depth, self.opt.no_ssim,
-                                             self.opt.avg_reprojection, self.opt.gdc_loss_threshold, self.opt.si_var,
-                                             si_mode=self._lidar_term()[1])
-        self.depth_metric_names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
-        self.epoch, self.step, self.batch_idx = 0, 0, 0
-        self.best = 10.0
-        self.start_time = time.time()
-        self.set_train()
-        self.flat.zero_grad()
-        if verbose and rank == 0:
-            n = sum(p.numel() for p in self.parameters_to_train)
-            print("fusiondepth_amd.Trainer: %d parameters (%.1f MB fp32), accumulating %d steps, single batch size = %d, "
-                  "lr %.3g, %d rank(s)" % (n, n * 4 / 1e6, self.accumulate_step, self.batch_size, self.lr, world_size))
+    def _announce(self):
+        n = sum(p.numel() for p in self.parameters_to_train)
+        print("fusiondepth_amd.Trainer: %d parameters (%.1f MB fp32), accumulating %d steps, single batch size = %d, "
+              "lr %.3g, %d rank(s)" % (n, n * 4 / 1e6, self.accumulate_step, self.batch_size, self.lr, self.world_size))
 
-    # ---- what the sibling drivers of the reference (completor.py) configure differently -----------------
     def _derived_hparams(self, vram_gib):
         return derived_hparams(self.opt, vram_gib)
 
@@ -247,9 +264,9 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------------------
     def set_train(self):
-        """trainer.py:207-211"""
-        for m in self.models.values():
-            m.train()
+        """trainer.py:207-211; frozen networks (refiner.py:80-160: its depth / pose networks) stay in eval mode"""
+        for k, m in self.models.items():
+            m.train() if k in self.trained else m.eval()
 
     def set_eval(self):
         """trainer.py:213-217"""
@@ -282,31 +299,39 @@ class Trainer:
         Returns the loss dict (device tensors; nothing is synchronised here)."""
         prestacked = isinstance(micro_batches, dict)       # a loader that already delivers the step's images as one batch
         assert prestacked or len(micro_batches) == self.accumulate_step
-        if self.stack_microbatches:
-            self.grad_sync.arm()
-            stacked = micro_batches if prestacked else self.stack_micro_batches(micro_batches)
-            outputs, losses = self.process_batch(stacked, groups=self.accumulate_step)
-            losses["loss"].backward()
-            self._join_side_streams()
-            self.batch_idx += self.accumulate_step
-        else:
-            assert not prestacked, "pre-stacked input needs stack_microbatches"
-            losses = None
-            for i, inputs in enumerate(micro_batches):
-                last = i == self.accumulate_step - 1
-                outputs, losses = self.process_batch(inputs)
-                loss = losses["loss"] / self.accumulate_step
-                if last:
-                    self.grad_sync.arm()
-                loss.backward()
-                self._join_side_streams()
-                self.batch_idx += 1
+        assert self.stack_microbatches or not prestacked, "pre-stacked input needs stack_microbatches"
+        if self.stack_microbatches and not prestacked:
+            micro_batches = self.stack_micro_batches(micro_batches)
+        inputs, outputs, losses = self._forward_backward(micro_batches, eager=True)
         scale = self.grad_sync.finish() if self.world_size > 1 else 1.0
         self.optimizer_step(scale)
         self._ensure_weight_plan()
         self.step += self.accumulate_step            # the reference counts batches (trainer.py:264), not optimiser steps
-        self._last_io = (stacked if self.stack_microbatches else inputs, outputs)
+        self._last_io = (inputs, outputs)
         return losses
+
+    def _forward_backward(self, batches, eager):
+        """Forward + backward of one optimiser step -> (inputs, outputs, losses) of its last pass.  ``batches``: the stacked batch
+        (``stack_microbatches``: one pass) or the list of micro-batches (one pass each, loss / accumulate_step).  ``eager``: arm the
+        gradient exchange for the window's last pass and count the batches; the captured step (graph_step.py) does neither."""
+        stacked = self.stack_microbatches
+        passes = [batches] if stacked else batches
+        if eager and stacked:
+            self.grad_sync.arm()
+        for i, inputs in enumerate(passes):
+            if stacked:
+                outputs, losses = self.process_batch(inputs, groups=self.accumulate_step)
+                loss = losses["loss"]
+            else:
+                outputs, losses = self.process_batch(inputs)
+                loss = losses["loss"] / self.accumulate_step
+                if eager and i == len(passes) - 1:
+                    self.grad_sync.arm()
+            loss.backward()
+            self._join_side_streams()
+            if eager:
+                self.batch_idx += self.accumulate_step if stacked else 1
+        return inputs, outputs, losses
 
     def _ensure_weight_plan(self):
         """After the first full forward + backward every conv weight has its cached kernel-side layouts: collect their
@@ -316,21 +341,20 @@ class Trainer:
             weight_layouts.rebuild_weight_plan()
 
     def optimizer_step(self, grad_scale=1.0):
-        """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel.  The step
-        counter and lr are read from device memory so the launch can live inside a captured hipGraph."""
-        self.adam_step_count += 1
-        FD.adam_step_dev(self.flat.flat_param, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.adam_state,
-                         grad_scale=grad_scale)
+        """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel (optim.FlatAdam)."""
+        self.optim.step(grad_scale)
         self.flat.zero_grad()
 
     def lr_scheduler_step(self):
-        """StepLR(step_size, 0.1).step()  (trainer.py:266): the learning rate drops by 10x every ``scheduler_step_size`` calls."""
-        self.scheduler_epochs = getattr(self, "scheduler_epochs", 0) + 1
-        if self._graph is None:                 # no captured graph can hold a raw pointer into a retired layout buffer: free them
+        """StepLR(step_size, 0.1).step()  (trainer.py:266)."""
+        if not self._graph_started:             # no captured graph can hold a raw pointer into a retired layout buffer: free them
             FD.release_retired_layouts()
-        if self.scheduler_step_size > 0 and self.scheduler_epochs % self.scheduler_step_size == 0:
-            self.lr *= 0.1
-            self.adam_state[1] = self.lr
+        self.optim.scheduler_step()
+
+    # the optimiser's numbers under the names the reference's drivers, the logs and bench.py read
+    adam_step_count = property(lambda self: self.optim.step_count)
+    lr = property(lambda self: self.optim.lr)
+    scheduler_step_size = property(lambda self: self.optim.scheduler_step_size)
 
     def end_epoch(self):
         """For callers that drive ``train_step`` themselves: advance the epoch counter and the StepLR schedule."""
@@ -349,7 +373,7 @@ class Trainer:
             raise RuntimeError("Trainer.train: no train_loader (pass one, or set self.train_loader: datasets.KITTIRAWBatches for "
                                "KITTI raw, or any iterable of reference-schema batches)")
         self.epoch, self.step = 0, 0
-        self.scheduler_epochs = 0              # a second train() on the same object starts its StepLR count afresh
+        self.optim.scheduler_epochs = 0        # a second train() on the same object starts its StepLR count afresh
         self.start_time = time.time()
         try:
             self.num_total_steps = len(self.train_loader) * self.opt.num_epochs
@@ -422,100 +446,15 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------------------
     def train_step_graphed(self, micro_batches):
-        """``train_step`` replayed from a captured hipGraph (HIP graphs instead of a tracing compiler): the ~4500
-        kernel launches of one optimiser step cost one graph launch on the host.  The first call runs eagerly
-        (allocator warm-up), the second captures, later calls copy the new batch into the captured input buffers
-        and replay.  With several ranks the forward/backward micro-steps are replayed and the gradient all-reduce +
-        Adam run after the graph."""
-        self._pose_on_main = True              # the captured step keeps the pose decoder on the capture stream (see predict_poses)
-        try:
-            return self._train_step_graphed(micro_batches)
-        finally:
-            self._pose_on_main = False         # direct process_batch / train_step calls afterwards fork their side streams again
+        """``train_step`` replayed from a captured hipGraph (graph_step.py)."""
+        if self._graphed is None:
+            from .graph_step import GraphedStep
+            self._graphed = GraphedStep()
+        return self._graphed.step(self, micro_batches)
 
-    def _train_step_graphed(self, micro_batches):
-        if self._graph is None:
-            if self.stack_microbatches:
-                self._static_in = self.stack_micro_batches(micro_batches)
-                if len(micro_batches) == 1:
-                    self._static_in = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self._static_in.items()}
-            else:
-                self._static_in = [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in mb.items()} for mb in micro_batches]
-            self._last_mbs = micro_batches
-            self._graph = "warm"
-            # warm up on the stream the capture will use, so that autograd's AccumulateGrad nodes are bound to it
-            self._side = torch.cuda.Stream()
-            self._side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._side):
-                losses = self._graph_body(self._static_in)
-                if self.world_size > 1:
-                    self._sync_and_step()
-            torch.cuda.current_stream().wait_stream(self._side)
-            self.step += self.accumulate_step
-            self.batch_idx += self.accumulate_step
-            return losses
-        if micro_batches is not self._last_mbs:
-            self._copy_into_static(micro_batches)
-            self._last_mbs = micro_batches
-        if self._graph == "warm":
-            with torch.cuda.stream(self._side):
-                self._ensure_weight_plan()     # layouts valid now; inside the graph Adam is followed by the batched refresh
-            if not weight_layouts.has_plan():
-                FD.bump_weights_epoch()        # no plan: the captured step must re-derive every weight layout at first use
-            FD.sync_late_layouts()             # no event from outside the capture may be waited on inside it
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._side):
-                self._static_losses = self._graph_body(self._static_in)
-            self._graph = g
-        # A refresh of the cached weight layouts issued eagerly since the last replay - the optimiser step that follows the graph when
-        # world_size > 1, load_model() - puts the large layouts on a side stream behind an event (weight_layouts.refresh_weight_layouts).
-        # The captured kernels were recorded with "layout ready" and never look at that event: the replay stream waits for it here.
-        FD.sync_late_layouts()
-        self._graph.replay()
-        if self.world_size > 1:
-            self._sync_and_step()
-        self.step += self.accumulate_step
-        self.batch_idx += self.accumulate_step
-        return self._static_losses
-
-    def _copy_into_static(self, micro_batches):
-        if not self.stack_microbatches:
-            for dst, src in zip(self._static_in, micro_batches):
-                for k, v in src.items():
-                    if torch.is_tensor(v):
-                        dst[k].copy_(v)
-            return
-        for i, mb in enumerate(micro_batches):
-            for k, v in mb.items():
-                if torch.is_tensor(v):
-                    n = v.shape[0]
-                    self._static_in[k][i * n:(i + 1) * n].copy_(v)
-                elif k == "_noise":
-                    for s_, t in enumerate(v):
-                        self._static_in[k][s_][i * t.shape[0]:(i + 1) * t.shape[0]].copy_(t)
-
-    def _graph_body(self, static_in):
-        if self.stack_microbatches:
-            outputs, losses = self.process_batch(static_in, groups=self.accumulate_step)
-            losses["loss"].backward()
-            self._join_side_streams()
-        else:
-            losses = None
-            for inputs in static_in:
-                outputs, losses = self.process_batch(inputs)
-                (losses["loss"] / self.accumulate_step).backward()
-                self._join_side_streams()
-        if self.world_size == 1:
-            self.adam_step_count += 1
-            FD.adam_step_dev(self.flat.flat_param, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.adam_state)
-            self.flat.flat_grad.zero_()
-        return {k: v.detach() for k, v in losses.items()}
-
-    def _sync_and_step(self):
-        import torch.distributed as dist
-        dist.all_reduce(self.flat.flat_grad, op=dist.ReduceOp.SUM)
-        self.optimizer_step(1.0 / self.world_size)
+    # a graph of the step is captured or warming up / inside train_step_graphed every fork stays on the capture stream
+    _graph_started = property(lambda self: self._graphed is not None and self._graphed.graph is not None)
+    _in_graphed_step = property(lambda self: self._graphed is not None and self._graphed.active)
 
     # ------------------------------------------------------------------------------------------------
     def _join_side_streams(self):
@@ -552,9 +491,7 @@ class Trainer:
         720 output pixels), so the four encoder modules are issued on separate HIP streams — inside the captured hipGraph they become
         parallel branches — and joined before the decoders.  Autograd replays each backward on its forward stream,
         so the backward passes overlap the same way."""
-        for key, ipt in inputs.items():
-            if key != "date" and key != "path" and torch.is_tensor(ipt) and ipt.device != self.device:
-                inputs[key] = ipt.to(self.device)
+        self._to_device(inputs)
         par = (self.parallel_streams and not val and self.use_pose_net and self.opt.pose_model_type == "separate_resnet"
                and self.num_pose_frames == 2 and len(self._pose_fids()) > 0)
         if self.opt.cat_4beam_to_color:
@@ -567,6 +504,11 @@ class Trainer:
         FD.begin_forward_pass()
         with FD.defer_bn_counters():
             return self._process_batch(inputs, val, groups, par, enc_in)
+
+    def _to_device(self, inputs):
+        for key, ipt in inputs.items():
+            if key != "date" and key != "path" and torch.is_tensor(ipt) and ipt.device != self.device:
+                inputs[key] = ipt.to(self.device)
 
     def _pose_fids(self):
         """The source frames whose pose comes from the pose network: all but the stereo partner "s" (trainer.py:337, 382)."""
@@ -631,7 +573,7 @@ class Trainer:
         if val:
             self.generate_images_pred(inputs, outputs, [0])
         else:
-            if par and tuning.host.smooth_stream and not self._pose_on_main and not torch.cuda.is_current_stream_capturing():
+            if par and tuning.host.smooth_stream and not self._in_graphed_step and not torch.cuda.is_current_stream_capturing():
                 # the smoothness terms (3 small launches per scale, forward and backward) beside the photometric kernel instead of
                 # behind it on the main stream; the beam encoder's stream is idle between its forward and its backward
                 st = self._fork(0)
@@ -763,7 +705,7 @@ class Trainer:
                 # The pose decoder (a dozen small launches forward, ~60 backward incl. autograd's slicing glue) stays on the pose
                 # encoder's stream: autograd replays a node on its forward stream, so the decoder's backward - created last, hence
                 # replayed first - no longer sits on the main stream in front of the depth decoder's backward (tuning.host.pose_stream).
-                if (tuning.host.pose_stream and self.parallel_streams and not self._pose_on_main
+                if (tuning.host.pose_stream and self.parallel_streams and not self._in_graphed_step
                         and not torch.cuda.is_current_stream_capturing()):
                     pose_stream = st
                     if bf is not None:
@@ -1066,56 +1008,11 @@ class Trainer:
         return folder
 
     def optimizer_state_dict(self):
-        """``torch.optim.Adam.state_dict()`` layout (what trainer.py:714-715 writes), so that ``adam.pth`` interchanges with the
-        reference: per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` in ``parameters_to_train`` order (the reference builds
-        that list in the same network order, trainer.py:66-129), one parameter group carrying the current learning rate."""
-        state = {}
-        step = torch.tensor(float(self.adam_step_count))
-        if self.adam_step_count > 0:
-            avg, sq = self.exp_avg.detach().cpu(), self.exp_avg_sq.detach().cpu()
-            for i, p in enumerate(self.flat.params):
-                o, n = self.flat.offsets[i], p.numel()
-                state[i] = {"step": step.clone(), "exp_avg": avg[o:o + n].view(p.shape).clone(),
-                            "exp_avg_sq": sq[o:o + n].view(p.shape).clone()}
-        group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "initial_lr": self.learning_rate,
-                 "params": list(range(len(self.flat.params)))}
-        return {"state": state, "param_groups": [group]}
+        """``adam.pth`` in ``torch.optim.Adam.state_dict()`` layout (optim.FlatAdam.state_dict)."""
+        return self.optim.state_dict()
 
     def load_optimizer_state_dict(self, st):
-        """Inverse of ``optimizer_state_dict``; also reads the flat layout round 1 of this package wrote.  Restores the moments,
-        the step count (bias correction) and the learning rate (StepLR decays already taken) on the host AND in the device-side
-        ``adam_state`` the Adam kernel reads."""
-        if "state" in st and "param_groups" in st:
-            n_params = len(self.flat.params)
-            groups = st["param_groups"]
-            listed = sum(len(g["params"]) for g in groups)
-            if listed != n_params:
-                raise RuntimeError("adam.pth holds %d parameters, this trainer has %d (different network set?)" % (listed, n_params))
-            steps = []
-            self.exp_avg.zero_(); self.exp_avg_sq.zero_()
-            for i, entry in st["state"].items():
-                i = int(i)
-                p, o = self.flat.params[i], self.flat.offsets[i]
-                if tuple(entry["exp_avg"].shape) != tuple(p.shape):
-                    raise RuntimeError("adam.pth: moment %d has shape %s, parameter has %s" % (i, tuple(entry["exp_avg"].shape), tuple(p.shape)))
-                self.exp_avg[o:o + p.numel()].copy_(entry["exp_avg"].reshape(-1))
-                self.exp_avg_sq[o:o + p.numel()].copy_(entry["exp_avg_sq"].reshape(-1))
-                steps.append(int(float(entry["step"])))
-            if steps and min(steps) != max(steps):
-                raise RuntimeError("adam.pth: per-parameter step counts differ (%d..%d); the flat Adam kernel keeps one" % (min(steps), max(steps)))
-            self.adam_step_count = steps[0] if steps else 0
-            self.lr = float(groups[0]["lr"])
-        elif "exp_avg" in st:
-            if st["exp_avg"].numel() != self.exp_avg.numel():
-                raise RuntimeError("adam.pth: %d moments for %d parameters" % (st["exp_avg"].numel(), self.exp_avg.numel()))
-            self.exp_avg.copy_(st["exp_avg"]); self.exp_avg_sq.copy_(st["exp_avg_sq"])
-            self.adam_step_count = int(st["step"])
-            self.lr = float(st.get("lr", self.lr))
-        else:
-            raise RuntimeError("adam.pth: unknown layout (keys %s)" % sorted(st))
-        self.adam_state[0] = float(self.adam_step_count)
-        self.adam_state[1] = self.lr
+        return self.optim.load_state_dict(st)
 
     def load_model(self):
         """trainer.py:717-746: weights of ``models_to_load`` (+ the two LiDAR encoders when ``--beam_encoder``, :726-728) copied in
@@ -1131,12 +1028,7 @@ class Trainer:
             path = os.path.join(folder, "{}.pth".format(n))
             if not os.path.isfile(path):
                 raise FileNotFoundError("models_to_load: %s is missing" % path)
-            model_dict = self.models[n].state_dict()
-            pretrained = torch.load(path, map_location="cpu")
-            with torch.no_grad():
-                for k, v in pretrained.items():
-                    if k in model_dict:
-                        model_dict[k].copy_(v)              # in place: parameters stay views of the flat buffer
+            load_state_by_key(self.models[n], path, allow_missing=True)      # in place: parameters stay views of the flat buffer
         weight_layouts.weights_replaced()
         FD.refresh_weight_layouts()       # a captured step holds no per-conv re-layout launches: refresh the cached copies now
         adam = os.path.join(folder, "adam.pth")

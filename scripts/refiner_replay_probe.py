@@ -39,4 +39,4 @@ for rnd in range(3):
         tuning.host.replay_frozen = mode
         h, s = run()
         print("replay_frozen=%-5s host issue %.2f ms / step, step %.2f ms = %.1f images/s" % (mode, h, s, B / s * 1e3), flush=True)
-print({k: (r.disabled, len(r.plans), [p[0].n_recs for p in r.plans.values()]) for k, r in rf._replays.items()})
+print({k: (r.disabled, len(r.plans), [p[0].n_recs for p in r.plans.values()]) for k, r in rf.frozen.replays.items()})

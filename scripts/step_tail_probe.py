@@ -16,7 +16,7 @@ for _ in range(6): tr.train_step(inp)
 a = run(20)
 orig = tr.optimizer_step
 def no_opt(scale=1.0):
-    tr.adam_step_count += 1
+    tr.optim.step_count += 1
 tr.optimizer_step = no_opt
 for _ in range(3): tr.train_step(inp)
 b = run(20)

@@ -72,7 +72,7 @@ def _patch(monkeypatch, fake):
     import torch.distributed as dist
     from fusiondepth_amd import dp
     monkeypatch.setattr(dp.dist, "all_reduce", fake.all_reduce)
-    assert dist.all_reduce == fake.all_reduce                   # trainer._sync_and_step imports torch.distributed itself
+    assert dist.all_reduce == fake.all_reduce                   # graph_step._sync_and_step imports torch.distributed itself
 
 
 def _opts(B=2, H=64, W=96, extra=()):

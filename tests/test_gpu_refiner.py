@@ -49,6 +49,27 @@ def test_refiner_needs_its_stage1_folder(tmp_path):
         Refiner(o, verbose=False)
 
 
+def test_refiner_is_built_by_the_trainers_constructor():
+    """``Refiner.__init__`` goes through ``Trainer.__init__``: every attribute the Trainer sets - and the methods the Refiner inherits
+    read - exists on a Refiner, and what is trained is the refine decoder alone, in a flat buffer of exactly its size."""
+    import copy
+    from fusiondepth_amd.trainer import Trainer
+    rf, _, _ = _make(2, 64, 96)
+    tr = Trainer(copy.deepcopy(rf.opt), verbose=False)
+    only_trainer = {}                                   # attribute -> why a Refiner does not have it (none)
+    assert vars(tr).keys() - vars(rf).keys() == only_trainer.keys()
+    decoder = list(rf.models["refine2d_decoder"].parameters())
+    assert len(rf.parameters_to_train) == len(decoder) and all(a is b for a, b in zip(rf.parameters_to_train, decoder))
+    assert all(p.requires_grad for p in decoder)
+    for k, net in rf.models.items():
+        if k != "refine2d_decoder":
+            assert not any(p.requires_grad for p in net.parameters()), k
+            assert not net.training, k
+    assert list(rf.models) == ["encoder", "beam_encoder", "beam_encoder_pose", "depth", "pose_encoder", "pose", "refine2d_decoder"]
+    assert rf.flat.numel() == sum(p.numel() for p in decoder) == rf.optim.exp_avg.numel()
+    assert rf.models["refine2d_decoder"].training
+
+
 def test_refiner_step_vs_reference_golden(golden):
     g = golden("refiner_b1_192x640")
     B, H, W = 1, 192, 640

@@ -96,7 +96,7 @@ def test_refiner_steps_with_replayed_frozen_networks_are_bit_identical():
                 losses.append(float(lg["loss"]))
             torch.cuda.synchronize()
             res[mode] = (losses, torch.cat([p.detach().reshape(-1) for p in rf.models["refine2d_decoder"].parameters()]).clone(),
-                         {k: (r.disabled, len(r.plans)) for k, r in rf._replays.items()})
+                         {k: (r.disabled, len(r.plans)) for k, r in rf.frozen.replays.items()})
         finally:
             tuning.host.replay_frozen = True
     assert res[False][0] == res[True][0], (res[False][0], res[True][0])

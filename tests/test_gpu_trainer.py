@@ -641,7 +641,7 @@ def test_graph_replay_matches_eager():
         for _ in range(4):
             losses = fn([mb])
         torch.cuda.synchronize()
-        outs.append((tr.flat.flat_param.clone(), float(losses["loss"]), float(tr.adam_state[0])))
+        outs.append((tr.flat.flat_param.clone(), float(losses["loss"]), float(tr.optim.state[0])))
     assert outs[0][2] == outs[1][2] == 4.0
     assert_close(outs[1][1], outs[0][1], rtol=1e-5, atol=0, what="loss after 4 steps, graph vs eager")
     assert_close(outs[1][0].cpu().numpy(), outs[0][0].cpu().numpy(), rtol=1e-4, atol=1e-6, what="parameters, graph vs eager")
@@ -1081,7 +1081,7 @@ def test_train_loop_schedule(tmp_path):
     opt = _opts(height=64, width=96, batch_size=2, log_dir=str(tmp_path), num_epochs=2, save_frequency=1, log_frequency=2)
     tr = Trainer(opt, verbose=False)
     tr.opt.num_epochs = 2                                   # (derived: (8 * 17) // batch_size = 68 epochs, trainer.py:28)
-    tr.scheduler_step_size = 1                              # StepLR drops after every epoch
+    tr.optim.scheduler_step_size = 1                              # StepLR drops after every epoch
     acc = tr.accumulate_step
     batches = [synthetic.make_batch(tr.batch_size, 64, 96, seed=20 + i) for i in range(3 * acc)]
     for i, b in enumerate(batches):          # KITTI-sized sparse ground truth (the Garg crop is hard-wired to 375x1242)
@@ -1097,7 +1097,7 @@ def test_train_loop_schedule(tmp_path):
     tr.val = counting_val
     tr.train(batches, [batches[0]])
     assert tr.adam_step_count == 2 * 3 and tr.step == 2 * 3 * acc
-    assert abs(tr.lr - lr0 * 1e-2) < 1e-12 * lr0 and abs(float(tr.adam_state[1]) - tr.lr) < 1e-9
+    assert abs(tr.lr - lr0 * 1e-2) < 1e-12 * lr0 and abs(float(tr.optim.state[1]) - tr.lr) < 1e-9
     models = tmp_path / "mdp" / "models"
     assert sorted(p.name for p in models.iterdir() if p.name.startswith("weights_")) >= ["weights_0", "weights_1"]
     import json
@@ -1109,8 +1109,8 @@ def test_train_loop_schedule(tmp_path):
     # resume: moments, step count and the decayed learning rate come back, and the next step is the one the first run would take
     opt2 = _opts(height=64, width=96, batch_size=2, log_dir=str(tmp_path / "resume"), train_load_weights_folder=str(models / "weights_1"))
     tr2 = Trainer(opt2, verbose=False)
-    assert tr2.adam_step_count == tr.adam_step_count and abs(tr2.lr - tr.lr) < 1e-15 and float(tr2.adam_state[0]) == float(tr.adam_step_count)
-    assert torch.equal(tr2.flat.flat_param, tr.flat.flat_param) and torch.equal(tr2.exp_avg, tr.exp_avg)
+    assert tr2.adam_step_count == tr.adam_step_count and abs(tr2.lr - tr.lr) < 1e-15 and float(tr2.optim.state[0]) == float(tr.adam_step_count)
+    assert torch.equal(tr2.flat.flat_param, tr.flat.flat_param) and torch.equal(tr2.optim.exp_avg, tr.optim.exp_avg)
     mb = batches[:acc]
     for b in mb:
         b["_noise"] = [torch.zeros(tr.batch_size, 2, 64, 96, device="cuda") for _ in range(4)]
@@ -1133,11 +1133,11 @@ def test_adam_checkpoint_is_the_reference_optimizer_layout(tmp_path):
     back = ref_opt.state_dict()
     i = max(back["state"])
     assert float(back["state"][i]["step"]) == 1.0 and back["param_groups"][0]["lr"] == tr.lr
-    tr.exp_avg.zero_(); tr.adam_step_count = 0; tr.adam_state[0] = 0.0
+    tr.optim.exp_avg.zero_(); tr.optim.step_count = 0; tr.optim.state[0] = 0.0
     tr.load_optimizer_state_dict(back)
-    assert tr.adam_step_count == 1 and float(tr.adam_state[0]) == 1.0
+    assert tr.adam_step_count == 1 and float(tr.optim.state[0]) == 1.0
     o = tr.flat.offsets[i]
-    assert torch.equal(tr.exp_avg[o:o + tr.flat.params[i].numel()].cpu(), back["state"][i]["exp_avg"].reshape(-1).cpu())
+    assert torch.equal(tr.optim.exp_avg[o:o + tr.flat.params[i].numel()].cpu(), back["state"][i]["exp_avg"].reshape(-1).cpu())
 
 
 @pytest.mark.parametrize("H,W,B,groups", [(128, 192, 2, 1), (192, 640, 6, 2)])
