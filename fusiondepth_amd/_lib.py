@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FD_LIBFDHIP") or os.path.join(_HERE, "libfdhip.so")   # FD_LIBFDHIP: another build of the library, for a same-box A/B
-ABI_VERSION = 6
+ABI_VERSION = 7
 PHOTO_OUT_FLOATS = 96        # FD_PHOTO_OUT_FLOATS
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -66,6 +66,11 @@ class RasterDesc(ctypes.Structure):
 class ResizeDesc(ctypes.Structure):
     """Mirror of ``fd_resize_desc``."""
     _fields_ = [("offset", _L), ("h_in", _I), ("w_in", _I), ("mirror", _I), ("reserved", _I)]
+
+
+class DepthPngDesc(ctypes.Structure):
+    """Mirror of ``fd_depth_png_desc``."""
+    _fields_ = [("offset", _L)] + [(n, _I) for n in ("h", "w", "mirror", "src_y", "src_x", "win_y", "win_x", "win_h", "win_w", "reserved")]
 
 
 class RelayoutJob(ctypes.Structure):
@@ -191,6 +196,10 @@ SIGNATURES = {
     "fd_velo_rasterize_batch_ws_bytes": ("iii", "l"),
     "fd_velo_rasterize_batch": ("pp" "ii" "p" "iiiiii" "ppp" "p", "i"),
     "fd_resize_bilinear_batch": ("pl" "p" "iii" "p" "p", "i"),
+    "fd_depth_png_keys": ("pl" "p" "iiiii" "ff" "p" "p", "i"),
+    "fd_completion_ws_bytes": ("iii", "l"),
+    "fd_completion_medians": ("pp" "iii" "ff" "p" "pp", "i"),
+    "fd_completion_errors": ("ppp" "iii" "ffff" "p" "pp", "i"),
 }
 
 _lock = threading.Lock()

@@ -239,6 +239,52 @@ def resize_bilinear_batch(packed, descs, size, desc_table=None):
     return out
 
 
+def depth_png_desc_table(descs):
+    """Host image of the ``fd_depth_png_desc`` table for ``descs`` = [(offset in uint16 elements, h, w, mirror, src_y, src_x, win_y,
+    win_x, win_h, win_w)]: a ctypes array."""
+    table = (_lib.DepthPngDesc * len(descs))()
+    for d, (offset, h, w, mirror, src_y, src_x, win_y, win_x, win_h, win_w) in zip(table, descs):
+        d.offset, d.h, d.w, d.mirror = int(offset), int(h), int(w), 1 if mirror else 0
+        d.src_y, d.src_x, d.win_y, d.win_x, d.win_h, d.win_w = int(src_y), int(src_x), int(win_y), int(win_x), int(win_h), int(win_w)
+    return table
+
+
+def depth_png_keys(packed_u16, descs, canvas, pool=1, channels=1, div0=256.0, div1=1.0, desc_table=None):
+    """``get_depth`` of datasets/kitti_completion.py:51-80 for S decoded 16-bit depth PNGs of different sizes in one call
+    (fd_depth_png_keys): ``/ div0``, mirror, crop and / or zero pad, ``F.max_pool2d(2, ceil_mode=True)`` with ``pool`` = 2, ``/ div1``.
+    ``packed_u16``: a 1-D CUDA tensor holding the planes as uint16 (dtype uint16, or int16 carrying the same bits); ``descs``:
+    [(offset, h, w, mirror, src_y, src_x, win_y, win_x, win_h, win_w)] per plane - the window of the ``canvas`` = (H, W) that the
+    plane fills, everything outside it is 0, and the source pixel (in mirrored coordinates) of the window's first pixel;
+    ``desc_table``: the same table already on the device (a uint8 CUDA tensor holding ``depth_png_desc_table(descs)``), else it is
+    uploaded here.  Returns [S, channels, ceil(H / pool), ceil(W / pool)] float32, the map written ``channels`` times."""
+    _need_cuda(packed_u16)
+    if packed_u16.dtype not in (torch.uint16, torch.int16) or packed_u16.dim() != 1 or not packed_u16.is_contiguous() or not packed_u16.numel() \
+            or packed_u16.data_ptr() % 8:
+        raise ValueError("depth_png_keys: packed must be a non-empty contiguous 8-byte aligned 1-D uint16 (or int16) CUDA tensor")
+    S = len(descs)
+    ch, cw = int(canvas[0]), int(canvas[1])
+    pool, channels = int(pool), int(channels)
+    if S < 1 or ch < 1 or cw < 1 or pool not in (1, 2) or channels not in (1, 2):
+        raise ValueError("depth_png_keys: nothing to do (%d planes -> %d x %d, pool %d, %d channels)" % (S, ch, cw, pool, channels))
+    for offset, h, w, _, src_y, src_x, win_y, win_x, win_h, win_w in descs:
+        if h < 1 or w < 1 or offset < 0 or offset + h * w > packed_u16.numel():
+            raise ValueError("depth_png_keys: a %d x %d plane at element %d leaves the packed buffer of %d elements"
+                             % (h, w, offset, packed_u16.numel()))
+        if min(win_y, win_x, win_h, win_w, src_y, src_x) < 0 or win_y + win_h > ch or win_x + win_w > cw or src_y + win_h > h or src_x + win_w > w:
+            raise ValueError("depth_png_keys: window (%d, %d, %d, %d) from source (%d, %d) does not fit a %d x %d plane and a %d x %d canvas"
+                             % (win_y, win_x, win_h, win_w, src_y, src_x, h, w, ch, cw))
+    nbytes = S * ctypes.sizeof(_lib.DepthPngDesc)
+    if desc_table is None:
+        desc_table = torch.frombuffer(bytearray(bytes(depth_png_desc_table(descs))), dtype=torch.uint8).to(packed_u16.device)
+    elif desc_table.dtype != torch.uint8 or not desc_table.is_cuda or desc_table.numel() != nbytes or not desc_table.is_contiguous() \
+            or desc_table.data_ptr() % 8:
+        raise ValueError("depth_png_keys: desc_table must be an 8-byte aligned contiguous uint8 CUDA tensor of %d bytes" % nbytes)
+    out = torch.empty((S, channels, (ch + pool - 1) // pool, (cw + pool - 1) // pool), device=packed_u16.device, dtype=torch.float32)
+    call("fd_depth_png_keys", packed_u16.data_ptr(), packed_u16.numel(), desc_table.data_ptr(), S, ch, cw, pool, channels, float(div0),
+         float(div1), out.data_ptr(), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------ training images (uint8) ---
 # datasets/mono_dataset.py:85-104 on the device: Pillow's antialiased Lanczos resample, ColorJitter and ToTensor, bit for bit
 # (csrc/augment.hip; the arithmetic is restated in tests/augment_ref.py).  uint8 images are [N,H,W,3].

@@ -37,8 +37,10 @@ extern "C" {
  * 5: additions only: graph-based depth correction (fd_gdc_prepare_ws_bytes, fd_gdc_prepare, fd_gdc_ws_bytes, fd_gdc_build,
  *    fd_gdc_cg_iters, fd_gdc_finish, struct fd_gdc_state).  Nothing removed, no signature changed.
  * 6: additions only: the image half of the KITTI loader (fd_resize_lanczos_u8_ws_bytes, fd_resize_lanczos_u8, fd_color_jitter_u8_ws_bytes,
- *    fd_color_jitter_u8_means_offset, fd_color_jitter_u8, fd_u8_to_planes, struct fd_jitter_desc).  Nothing removed, no signature changed. */
-#define FD_ABI_VERSION 6
+ *    fd_color_jitter_u8_means_offset, fd_color_jitter_u8, fd_u8_to_planes, struct fd_jitter_desc).  Nothing removed, no signature changed.
+ * 7: additions only: KITTI depth completion (fd_depth_png_keys + struct fd_depth_png_desc, fd_completion_ws_bytes, fd_completion_medians,
+ *    fd_completion_errors).  Nothing removed, no signature changed. */
+#define FD_ABI_VERSION 7
 
 int fd_abi_version(void);
 const char* fd_supported_arch(void); /* "gfx950" */
@@ -735,6 +737,46 @@ typedef struct fd_resize_desc {
 } fd_resize_desc;
 int fd_resize_bilinear_batch(const float* packed, long packed_floats, const fd_resize_desc* desc, int B, int out_h, int out_w,
                              float* out, void* stream);
+
+/* ------------------------------------------------------------------ KITTI depth completion ----
+ * Depth keys (datasets/kitti_completion.py:51-80 get_depth, completion_dataset.py:314-367): S 16-bit depth PNGs of different sizes,
+ * decoded into one packed uint16 buffer, become [S][channels][ceil(canvas_h / pool)][ceil(canvas_w / pool)] float32 in ONE launch.
+ * Per plane the descriptor names a window of the canvas and the source pixel (in left-right mirrored coordinates where `mirror`
+ * is set: mirrored column x is source column w - 1 - x) that lands on the window's first pixel; canvas pixels outside the window
+ * are 0.  bottom_crop is a window that covers the canvas with (src_y, src_x) = (h - 352, j); the zero pad is (src_y, src_x) =
+ * (0, 0) with the window at (384 - h, (1280 - w) / 2); crop-then-pad is both.  Each output is
+ *   max over its pool x pool block, clipped at the canvas edge (ceil_mode), of ((float)v / div0), then / div1
+ * - two correctly rounded float32 divisions in that order, no reciprocal - written `channels` times.  A descriptor whose plane
+ * does not lie inside `packed`, whose window leaves the canvas or whose source rectangle leaves the plane yields a NaN plane;
+ * nothing outside the buffer is read.  packed and desc 8-byte aligned, out 16-byte aligned. */
+typedef struct fd_depth_png_desc {
+    long offset;                  /* first uint16 of the plane in `packed` */
+    int h, w;                     /* the decoded PNG */
+    int mirror;                   /* fliplr before crop / pad */
+    int src_y, src_x;             /* source pixel (after mirroring) of canvas pixel (win_y, win_x) */
+    int win_y, win_x, win_h, win_w;   /* the filled window of the canvas */
+    int reserved;
+} fd_depth_png_desc;
+int fd_depth_png_keys(const uint16_t* packed, long packed_elems, const fd_depth_png_desc* desc, int S, int canvas_h, int canvas_w,
+                      int pool /*1|2*/, int channels /*1|2*/, float div0, float div1, float* out, void* stream);
+
+/* Scoring (evaluate_completion.py:31-48 compute_errors, :297-355), per image n of pred / gt [N][H][W], mask m = gt > gt_min.
+ * Two entry points because --eval_gdc corrects the scaled prediction between them.
+ * fd_completion_medians: out[n] = { ratio, median(gt[m]), median((pred * pred_scale)[m]), count }, the medians numpy's (for an
+ *   even count the float32 mean of the two middle order statistics: (a + b) rounded to float32, then halved - not torch's lower
+ *   median), ratio = median(gt) / median(pred) in float32; NaN for all three when nothing is selected or a selected prediction is
+ *   NaN.  Radix select over keys formed from the planes in every pass: no list, no sort.  The ws argument is IGNORED by this entry point
+ *   (pass NULL); it is there so that the two calls take the same arguments.
+ * fd_completion_errors: p = pred * pred_scale (* ratio[n] when ratio != NULL), p < lo -> lo, p > hi -> hi, then in float32 as numpy
+ *   evaluates it: gt * 1000 - p * 1000, its square and abs; 1 / (gt * 0.001) - 1 / (p * 0.001), its square and abs.  The four sums
+ *   over m run in float64 (a fixed grid of partial sums, added in index order: bitwise reproducible, no float atomics);
+ *   out[n] = { sqrt(mean sq) = rmse [mm], mae [mm], irmse [1/km], imae [1/km], count } as float64, NaN where the count is 0.
+ *   ws: fd_completion_ws_bytes(N, H, W) bytes, 8-byte aligned. */
+long fd_completion_ws_bytes(int N, int H, int W);
+int fd_completion_medians(const float* pred, const float* gt, int N, int H, int W, float gt_min, float pred_scale,
+                          float* out /*[N][4]*/, void* ws, void* stream);
+int fd_completion_errors(const float* pred, const float* gt, const float* ratio /*[N] or NULL*/, int N, int H, int W,
+                         float gt_min, float pred_scale, float lo, float hi, double* out /*[N][5]*/, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,15 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
                           fed synthetic batches, alternating windows; and the condition: colour path (step 1 at batch 6) + the key <=
                           10 % of the synthetic-fed Refiner step (file mode's LiDAR keys are not in that sum, as in step 4).
 
+``--step completion [--out profiles/completion_time.log]`` measures the depth-completion loader and scorer (``KITTICompletionBatches``,
+``evaluate_completion``):
+
+ 11. ``completion_keys``  batch 4 x 3 frames of 375x1242 sources in full-res mode: upload of the pinned staging buffer, each
+                          ``fd_depth_png_keys`` call (beam planes, depth_gt, full_res_4beam) against its compulsory traffic (uint16 read once,
+                          float32 written once) at 6.3 TB/s (achievable HBM), the colour path at 352x1216, and the two scoring kernels at N = 8 and N = 1 beside the
+                          ``torch.sort``-based median recipe of evaluate_depth.py on the same tensors (device events); then the kernels' own
+                          times under ``rocprofv3 --kernel-trace --stats`` (a run of its own).
+
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
 import argparse
@@ -722,6 +731,141 @@ def step_refiner_trainer(args):
                 "of its device work" % (args.colour_ms, args.gdc_ms, B, dev_ms, 100 * share, 1e3 * syn, "within" if share <= 0.10 else "ABOVE"))
 
 
+# ---------------------------------------------------------------------------------------------------- 11. depth completion
+COMPLETION_BATCH = 4
+
+
+def step_completion_keys(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import completion_data as CD, data_ops, evaluate_completion as EC
+    from fusiondepth_amd.evaluate_depth import _median
+    B, F = COMPLETION_BATCH, FRAMES
+    rng = np.random.default_rng(5)
+    n_planes = F * B + B                                         # sparse planes frame-major, then ground truth
+    plane = (H0 * W0 + 3) // 4 * 4
+    beam = [CD.depth_desc(k * plane, H0, W0, bool(k % 2), True, False) for k in range(F * B)]
+    gt = [CD.depth_desc((F * B + k) * plane, H0, W0, bool(k % 2), True, False) for k in range(B)]
+    full = [CD.depth_desc(k * plane, H0, W0, bool(k % 2), True, True) for k in range(B)]
+    tables = [np.frombuffer(data_ops.depth_png_desc_table([d for d, _ in t]), dtype=np.uint8) for t in (beam, gt, full)]
+    at, pos = [], 0
+    for t in tables:
+        at.append((pos, pos + t.size))
+        pos = (pos + t.size + 15) // 16 * 16
+    staging = torch.empty((pos + 2 * n_planes * plane,), dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    for t, (a, b) in zip(tables, at):
+        host[a:b] = t
+    codes = rng.integers(256, 80 * 256, n_planes * plane).astype(np.uint16)
+    codes[rng.random(codes.size) >= 0.05] = 0
+    host[pos:].view(np.uint16)[:] = codes
+    dev = staging.cuda()
+    packed = dev[pos:].view(torch.int16)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times.append(a.elapsed_time(b))
+        return float(np.median(times)), min(times), max(times)
+
+    say("[11] depth-completion keys, batch %d x %d frames, %dx%d sources, full-res mode; device events, median of %d (min, max)" % (B, F, W0, H0, args.iters))
+    up = timed(lambda: staging.to("cuda", non_blocking=True))
+    say("    upload of the batch's pinned staging buffer (%.1f MB, one copy): %.3f ms (%.3f, %.3f) = %.1f GB/s"
+        % (staging.numel() / 1e6, up[0], up[1], up[2], staging.numel() / (up[0] * 1e-3) / 1e9))
+    total = up[0]
+    for name, descs, k, channels, div1 in (("beam planes -> (2channel, f, 0), 4beam", beam, 0, 2, 100.0), ("depth_gt", gt, 1, 1, 1.0),
+                                           ("full_res_4beam", full, 2, 1, 1.0)):
+        canvas = descs[0][1]
+        ms = timed(lambda: data_ops.depth_png_keys(packed, [d for d, _ in descs], canvas, 1, channels, 256.0, div1,
+                                                   desc_table=dev[at[k][0]:at[k][1]]))
+        read = 2 * len(descs) * 352 * 1216                       # the cropped rectangle of every plane
+        write = 4 * len(descs) * channels * canvas[0] * canvas[1]
+        comp = read + write
+        total += ms[0]
+        say("    fd_depth_png_keys, %s (%d planes, 1 launch; the output allocation included): %.3f ms (%.3f, %.3f); compulsory traffic read "
+            "%.1f MB + write %.1f MB = %.2f us at 6.3 TB/s (achievable HBM) -> %.1fx the bound, %.2f TB/s"
+            % (name, len(descs), ms[0], ms[1], ms[2], read / 1e6, write / 1e6, 1e6 * comp / HBM_BPS, ms[0] * 1e-3 / (comp / HBM_BPS),
+               comp / (ms[0] * 1e-3) / 1e12))
+    frames = torch.from_numpy(np.stack([frame(i % 6)[H0 - 352:, 13:13 + 1216] for i in range(F * B)])).cuda()
+    flip = [bool((i // 2) % 2) for i in range(F * B)]
+    jitter = [JITTER if i % 2 else None for i in range(F * B)]
+    ms = timed(lambda: data_ops.image_pyramid(frames, 352, 1216, SCALES, flip, jitter))
+    total += ms[0]
+    say("    colour path at 352x1216 (%d cropped frames, %d scales, half jittered, 10 launches): %.3f ms (%.3f, %.3f)" % (F * B, SCALES, ms[0], ms[1], ms[2]))
+    say("    the batch's device work (upload + three key calls + colour): %.3f ms" % total)
+    # the scorer, per image, beside the torch.sort-based median recipe of evaluate_depth.py on the same tensors
+    N = 8
+    v, u = np.meshgrid(np.arange(352, dtype=np.float32), np.arange(1216, dtype=np.float32), indexing="ij")
+    truth = np.stack([5.0 + n + 40.0 * (1.0 - v / 352) + 3.0 * np.sin(u / 80.0) for n in range(N)]).astype(np.float32)
+    g = torch.from_numpy(np.where(rng.random(truth.shape) < 0.15, truth, 0.0).astype(np.float32)).cuda()
+    p = torch.from_numpy((truth * 0.5 + rng.normal(0, 0.1, truth.shape)).astype(np.float32)).cuda()
+    med = timed(lambda: EC.completion_medians(p, g))
+    ratio = EC.completion_medians(p, g)[:, 0].contiguous()
+    err = timed(lambda: EC.completion_errors(p, g, ratio))
+
+    def recipe():
+        out = []
+        for n in range(N):
+            m = g[n] > 0.1
+            gs, ps = g[n][m], p[n][m]
+            ps = torch.clamp(ps * (_median(gs) / _median(ps)), 1e-3, 80)
+            d, di = gs * 1000.0 - ps * 1000.0, 1.0 / (gs * 0.001) - 1.0 / (ps * 0.001)
+            out.append(torch.stack([(d * d).double().mean().sqrt(), d.abs().double().mean(), (di * di).double().mean().sqrt(), di.abs().double().mean()]))
+        return torch.stack(out)
+
+    rec = timed(recipe)
+    p1, g1, r1 = p[:1].contiguous(), g[:1].contiguous(), ratio[:1].contiguous()
+    med1, err1 = timed(lambda: EC.completion_medians(p1, g1)), timed(lambda: EC.completion_errors(p1, g1, r1))
+    N_all, N = N, 1
+    rec1 = timed(recipe)
+    N = N_all
+    assert np.allclose(recipe().cpu().numpy(), EC.completion_errors(p, g, ratio)[:, :4].cpu().numpy(), rtol=1e-6)
+    say("    scorer, %d images of 352x1216, 15 %% ground truth: fd_completion_medians %.3f ms (%.3f, %.3f) = %.1f us / image; "
+        "fd_completion_errors %.3f ms (%.3f, %.3f) = %.1f us / image" % (N, med[0], med[1], med[2], 1e3 * med[0] / N, err[0], err[1], err[2], 1e3 * err[0] / N))
+    say("    the same scores with boolean selection + torch.sort medians (evaluate_depth._median), ATen: %.3f ms (%.3f, %.3f) = %.1f us / image "
+        "-> %.1fx the two kernels" % (rec[0], rec[1], rec[2], 1e3 * rec[0] / N, rec[0] / (med[0] + err[0])))
+    say("    ONE image (latency: the medians run two workgroups, nothing beside them): fd_completion_medians %.3f ms (%.3f, %.3f), "
+        "fd_completion_errors %.3f ms (%.3f, %.3f); the ATen recipe %.3f ms (%.3f, %.3f) -> %.2fx the two kernels"
+        % (med1[0], med1[1], med1[2], err1[0], err1[1], err1[2], rec1[0], rec1[1], rec1[2], rec1[0] / (med1[0] + err1[0])))
+
+
+def step_completion_trace_report(args):
+    """The kernels' own times from the rocprofv3 results database of a traced ``completion_keys`` run."""
+    import sqlite3
+    files = sorted(glob.glob(os.path.join(args.trace_dir, "**", "*_results.db"), recursive=True))
+    if not files:
+        sys.exit("no rocprofv3 results database under %s" % args.trace_dir)
+    db = sqlite3.connect(files[-1])
+    say("    rocprofv3 --kernel-trace --stats (a run of its own), kernel times:")
+    for name in ("k_depth_png_keys", "k_completion_median", "k_completion_ratio", "k_completion_errors", "k_completion_finish"):
+        n, avg, lo, hi = list(db.execute("select count(*), avg(end-start)/1e3, min(end-start)/1e3, max(end-start)/1e3 from kernels where name like "
+                                         "'%%%s%%'" % name))[0]
+        if not n:
+            sys.exit("%s is not in the trace" % name)
+        say("      %-22s %4d launches: avg %8.2f us (min %.2f, max %.2f)" % (name, n, avg, lo, hi))
+
+
+def drive_completion(args):
+    out = os.path.abspath(args.out)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    scratch = tempfile.mkdtemp(prefix="bench_loader_")
+    me = "%s %s" % (sys.executable, os.path.abspath(__file__))
+    trace_dir = os.path.join(scratch, "trace")
+    steps = ["timeout -k 10 240 %s --step completion_keys --iters 30" % me,
+             "timeout -k 10 300 rocprofv3 --kernel-trace --stats -d %s -- %s --step completion_keys --iters 10 > /dev/null 2>&1" % (trace_dir, me),
+             "%s --step completion_trace_report --trace_dir %s" % (me, trace_dir)]
+    cmd = "set -o pipefail; (" + " && ".join(steps) + ") 2>&1 | tee -a %s" % out
+    sys.exit(subprocess.call(["bash", "-c", cmd], cwd=ROOT))
+
+
 def drive_refiner(args):
     out = os.path.abspath(args.out)
     os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -776,7 +920,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
                                                       "raw_builder", "raw_trainer", "offline", "offline_worker", "refiner", "inf_gdc_key", "gdc_trace_report",
-                                                      "refiner_trainer"])
+                                                      "refiner_trainer", "completion", "completion_keys", "completion_trace_report"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default="")
     ap.add_argument("--split_file", default="")
@@ -790,8 +934,9 @@ def main():
     ap.add_argument("--trace_dir", default="")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "sparsify_time.log" if args.step == "raw" else "loader_time.log")
-    {"refiner": drive_refiner, "inf_gdc_key": step_inf_gdc_key, "gdc_trace_report": step_gdc_trace_report,
+        args.out = os.path.join(ROOT, "profiles", {"raw": "sparsify_time.log", "completion": "completion_time.log"}.get(args.step, "loader_time.log"))
+    {"completion": drive_completion, "completion_keys": step_completion_keys, "completion_trace_report": step_completion_trace_report,
+     "refiner": drive_refiner, "inf_gdc_key": step_inf_gdc_key, "gdc_trace_report": step_gdc_trace_report,
      "refiner_trainer": step_refiner_trainer, "raw": drive_raw, "sparsify": step_sparsify, "raw_builder": step_raw_builder,
      "raw_trainer": step_raw_trainer, "offline": step_offline, "offline_worker": step_offline_worker, "all": drive, "colour": step_colour,
      "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker, "builder": step_builder,
