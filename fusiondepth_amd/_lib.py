@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FD_LIBFDHIP") or os.path.join(_HERE, "libfdhip.so")   # FD_LIBFDHIP: another build of the library, for a same-box A/B
-ABI_VERSION = 7
+ABI_VERSION = 8
 PHOTO_OUT_FLOATS = 96        # FD_PHOTO_OUT_FLOATS
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -71,6 +71,11 @@ class ResizeDesc(ctypes.Structure):
 class DepthPngDesc(ctypes.Structure):
     """Mirror of ``fd_depth_png_desc``."""
     _fields_ = [("offset", _L)] + [(n, _I) for n in ("h", "w", "mirror", "src_y", "src_x", "win_y", "win_x", "win_h", "win_w", "reserved")]
+
+
+class EigenDesc(ctypes.Structure):
+    """Mirror of ``fd_eigen_desc``."""
+    _fields_ = [("offset", _L)] + [(n, _I) for n in ("H", "W", "pred", "y0", "y1", "x0", "x1", "reserved")]
 
 
 class RelayoutJob(ctypes.Structure):
@@ -200,6 +205,8 @@ SIGNATURES = {
     "fd_completion_ws_bytes": ("iii", "l"),
     "fd_completion_medians": ("pp" "iii" "ff" "p" "pp", "i"),
     "fd_completion_errors": ("ppp" "iii" "ffff" "p" "pp", "i"),
+    "fd_eigen_scores_ws_bytes": ("iil", "l"),
+    "fd_eigen_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "p" "pp", "i"),
 }
 
 _lock = threading.Lock()

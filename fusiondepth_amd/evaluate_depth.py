@@ -1,21 +1,48 @@
-"""Device-side mirror of the metric core of the reference ``evaluate_depth.py``.
+"""The reference's ``evaluate_depth.py`` on the device: the Eigen-split metrics of a saved model.
 
   * ``compute_errors(gt, pred)``                      evaluate_depth.py:42-60   (fd_depth_errors)
   * ``batch_post_process_disparity(l_disp, r_disp)``  evaluate_depth.py:62-70   (fd_post_process_disparity, float64 like numpy)
-  * ``evaluate_predictions(pred_disps, gt_depths, ...)``  the per-image loop of ``evaluate`` (evaluate_depth.py:344-478):
-    resize the predicted disparity to the ground-truth size, invert, Eigen mask + Garg crop, ``pred_depth_scale_factor``,
-    median scaling, optional GDC (--eval_gdc, gdc.py), clamp to [1e-3, 80], metrics, mean over images.
-Model loading, the dataset walk, colour-mapped PNG dumps and the per-semantic-class breakdown of the reference script are
-outside the hot path.  No CPU fallback: tensors must live on the GPU.
+  * ``evaluate_predictions(pred_disps, gt_depths, ...)``  the per-image loop of ``evaluate`` (evaluate_depth.py:344-478), one image
+    at a time: resize the predicted disparity to the ground-truth size, invert, Eigen mask + Garg crop, ``pred_depth_scale_factor``,
+    median scaling, optional GDC (--eval_gdc, gdc.py), clamp to [1e-3, 80], metrics, mean over images.  The path of ``--eval_gdc``,
+    which needs the dense map between median scaling and scoring.
+  * ``pack_gt_depths`` / ``eigen_scores(pred_disps, gt_depths, ...)``  the same loop without GDC as one library call per chunk of
+    images (fd_eigen_scores, csrc/eigen_eval.hip): the resize is evaluated at the selected ground-truth pixels only, numpy's medians
+    come from a radix select over the compacted pairs, float32 terms, float64 sums in a fixed order (bitwise reproducible).
+  * ``evaluate(opt, splits_dir)`` / ``python -m fusiondepth_amd.evaluate_depth``: the script (:74-489), on ``Predictor`` (with
+    ``--refine_2d``: the stage-2 refine decoder) and ``KITTIRAWBatches``.
+
+Deviations from the reference, on purpose
+  * disparities are scored as float32.  ``--post_process`` yields float64 (numpy's promotion in ``batch_post_process_disparity``), which
+    the reference hands to ``cv2.resize`` as float64; here they are rounded to float32 once, as ``evaluate_predictions`` always did.
+  * ``--post_process`` feeds the mirrored colour image next to the UNMIRRORED LiDAR maps (and a batch of B maps next to 2 B images,
+    which fails for B > 1); here the second pass gets the mirrored ``2channel`` / ``4beam`` maps, as ``evaluate_completion`` does.
+  * the splits folder is an argument (``--splits_dir``, taken off the command line before ``MonodepthOptions`` parses the rest; default
+    ``splits``) instead of a folder beside the script; ``--eval_gdc`` reads the calibration under ``--data_path`` instead of ``kitti_data/``,
+    and the beam file is read only then (the reference loads it always and uses it only with ``--eval_gdc``).
+  * ``--no_eval`` and ``--eval_split benchmark`` return ``None`` instead of ending the interpreter; the benchmark PNGs are written with
+    PIL; no wandb run, no ``visualization/dates.npy``, no input statistics printout.
+  * not covered, refused with the reason: ``--visualize``, ``--per_semantic``, ``--save_sample``, ``--demo``, the odometry splits, a model
+    without the beam encoder, ``--cat2end`` with ``--refine_2d`` (the reference's refine branch reads ``beam_features``, which ``--cat2end``
+    never computes), ``--eval_gdc`` with ``--ext_disp_to_eval`` (the reference's ``dates`` are undefined there).
+No CPU fallback: tensors must live on the GPU.
 """
+import os
+import sys
+
 import numpy as np
 import torch
 
 from . import functional as FD
-from ._lib import _need_cuda, call, stream
+from ._lib import _need_cuda, call, query, stream
 
 MIN_DEPTH = 1e-3          # evaluate_depth.py:28-29
 MAX_DEPTH = 80
+STEREO_SCALE_FACTOR = 5.4 # :32
+METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+# numpy mirror of ``fd_eigen_desc`` (40 bytes, as ``_lib.EigenDesc``)
+EIGEN_DESC = np.dtype([("offset", np.int64), ("H", np.int32), ("W", np.int32), ("pred", np.int32), ("y0", np.int32), ("y1", np.int32),
+                       ("x0", np.int32), ("x1", np.int32), ("reserved", np.int32)])
 
 
 def compute_errors(gt, pred):
@@ -96,3 +123,264 @@ def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_s
         pred, g = torch.clamp(pred_depth[mask], MIN_DEPTH, MAX_DEPTH), gt[mask]
         errors.append(compute_errors(g, pred))
     return np.array(errors).mean(0), np.array(ratios)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the batched scorer
+def split_window(eval_split, gt_height, gt_width):
+    """The mask window (y0, y1, x0, x1) of one ground-truth map: the Garg crop for ``eigen`` / ``demo`` (evaluate_depth.py:358-365),
+    the whole map for every other split (:367-368)."""
+    if eval_split in ("eigen", "demo"):
+        return tuple(int(v) for v in garg_crop(gt_height, gt_width))
+    return 0, int(gt_height), 0, int(gt_width)
+
+
+def split_bounds(eval_split):
+    """(gt_lo, gt_hi) of the strict comparisons that select ground truth: (1e-3, 80) for ``eigen`` / ``demo``, (0, inf) otherwise."""
+    return (MIN_DEPTH, float(MAX_DEPTH)) if eval_split in ("eigen", "demo") else (0.0, float("inf"))
+
+
+def pack_gt_depths(gt_depths, eval_split):
+    """Ground-truth maps of different sizes -> (flat float32 tensor holding them back to back, ``EIGEN_DESC`` array with one
+    descriptor per map: plane offset, size, the index of its prediction (its position in ``gt_depths``) and the split's mask window,
+    computed as the reference does: float64 products, ``astype(np.int32)``, clamped to the map like the slice they feed).  Pure host
+    code; the tensor is pinned where a GPU is present, so that its upload can overlap."""
+    maps = [np.ascontiguousarray(np.asarray(g), dtype=np.float32) for g in gt_depths]
+    desc = np.zeros(len(maps), dtype=EIGEN_DESC)
+    at = 0
+    for i, g in enumerate(maps):
+        if g.ndim != 2 or not g.size:
+            raise ValueError("pack_gt_depths: ground truth %d has shape %s, expected a non-empty [H,W] map" % (i, g.shape))
+        H, W = g.shape
+        y0, y1, x0, x1 = split_window(eval_split, H, W)
+        y1, x1 = min(max(y1, 0), H), min(max(x1, 0), W)
+        y0, x0 = min(max(y0, 0), y1), min(max(x0, 0), x1)
+        desc[i] = (at, H, W, i, y0, y1, x0, x1, 0)
+        at += H * W
+    packed = torch.empty((max(at, 1),), dtype=torch.float32, pin_memory=torch.cuda.is_available())
+    flat = packed.numpy()
+    for d, g in zip(desc, maps):
+        flat[d["offset"]:d["offset"] + g.size] = g.reshape(-1)
+    return packed[:at] if at else packed[:0], desc
+
+
+def eigen_scores(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False, chunk=64):
+    """evaluate_depth.py:344-478 without GDC, ``chunk`` images per ``fd_eigen_scores`` call (so that pinned and device memory stay
+    bounded).  ``pred_disps``: [N,h,w] device tensor or host array (float64 is rounded to float32 once); ``gt_depths``: N [H_i,W_i]
+    maps.  Returns ``(per_image[N,7] float64, ratios[N] float32 - empty without median scaling -, counts[N] int64)``."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("fusiondepth_amd.evaluate_depth.eigen_scores needs an MI355X: there is no CPU path (use oracle/ for CPU checks)")
+    N = len(gt_depths)
+    if len(pred_disps) != N:
+        raise ValueError("eigen_scores: %d predictions for %d ground-truth maps" % (len(pred_disps), N))
+    if chunk < 1 or chunk > 4096:
+        raise ValueError("eigen_scores: chunk must be 1 .. 4096")
+    gt_lo, gt_hi = split_bounds(eval_split)
+    rows = []
+    for a in range(0, N, chunk):
+        b = min(a + chunk, N)
+        disp = pred_disps[a:b]
+        disp = disp if torch.is_tensor(disp) else torch.as_tensor(np.asarray(disp))
+        disp = FD.f32(disp).cuda()
+        if disp.dim() != 3:
+            raise ValueError("eigen_scores: pred_disps must be [N,h,w], got %s" % (tuple(disp.shape),))
+        packed, desc = pack_gt_depths(gt_depths[a:b], eval_split)
+        dev = disp.device
+        packed_d = packed.to(dev, non_blocking=True)
+        desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+        max_rows = int((desc["y1"] - desc["y0"]).max())
+        cap = int(((desc["y1"] - desc["y0"]).astype(np.int64) * (desc["x1"] - desc["x0"])).sum())
+        ws = torch.empty((max(query("fd_eigen_scores_ws_bytes", b - a, max_rows, cap), 8),), device=dev, dtype=torch.uint8)
+        out = torch.empty((b - a, 9), device=dev, dtype=torch.float64)
+        call("fd_eigen_scores", disp.data_ptr(), disp.shape[0], disp.shape[1], disp.shape[2], packed_d.data_ptr(), packed_d.numel(),
+             desc_d.data_ptr(), b - a, max_rows, cap, float(gt_lo), float(gt_hi), float(pred_depth_scale_factor),
+             0 if disable_median_scaling else 1, MIN_DEPTH, float(MAX_DEPTH), out.data_ptr(), ws.data_ptr(), stream())
+        rows.append(out.cpu().numpy())                           # synchronises: the pinned buffer is free to go afterwards
+    out = np.concatenate(rows) if rows else np.zeros((0, 9))
+    ratios = np.zeros((0,), np.float32) if disable_median_scaling else out[:, 7].astype(np.float32)
+    return out[:, :7].copy(), ratios, out[:, 8].astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the script
+def benchmark_depth_png(disp_resized):
+    """evaluate_depth.py:299-301 on disparities already resized to 352x1216: ``5.4 / disp``, clip to 0 .. 80, ``uint16(depth * 256)``."""
+    depth = STEREO_SCALE_FACTOR / np.asarray(disp_resized, dtype=np.float32)
+    depth = np.clip(depth, 0, 80)
+    return np.uint16(depth * 256)
+
+
+def split_off_splits_dir(argv, default="splits"):
+    """``--splits_dir X`` / ``--splits_dir=X`` is not one of the reference's options (tests/golden/options_surface.json pins that
+    surface): take it off the command line -> (splits_dir, the remaining arguments)."""
+    rest, splits_dir, i = [], default, 0
+    argv = list(argv)
+    while i < len(argv):
+        if argv[i] == "--splits_dir":
+            if i + 1 >= len(argv):
+                raise ValueError("--splits_dir needs a value")
+            splits_dir = argv[i + 1]
+            i += 2
+        elif argv[i].startswith("--splits_dir="):
+            splits_dir = argv[i].split("=", 1)[1]
+            i += 1
+        else:
+            rest.append(argv[i])
+            i += 1
+    return splits_dir, rest
+
+
+def _refuse_uncovered(opt):
+    """Everything ``evaluate`` does not cover, before anything touches the GPU."""
+    if sum((bool(opt.eval_mono), bool(opt.eval_stereo))) != 1:
+        raise ValueError("Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo")
+    for flag, why in (("visualize", "it writes OpenCV colour maps and .npy dumps to fixed relative folders"),
+                      ("per_semantic", "it reads masks of an external segmentation run from a fixed relative folder"),
+                      ("demo", "the demo split and its visualisation folders are not part of this package")):
+        if getattr(opt, flag):
+            raise NotImplementedError("evaluate_depth: --%s is not covered (%s)" % (flag, why))
+    if opt.save_sample != -1:
+        raise NotImplementedError("evaluate_depth: --save_sample is not covered (a matplotlib plot saved to a path on the author's machine)")
+    if opt.eval_split in ("odom_9", "odom_10"):
+        raise NotImplementedError("evaluate_depth: the odometry splits are not covered (the reference's script has no ground truth for them)")
+    if opt.ext_disp_to_eval is None:
+        if not opt.beam_encoder:
+            raise NotImplementedError("evaluate_depth: a model without the beam encoder is not covered (Predictor always runs it)")
+        if opt.cat2end and opt.refine_2d:
+            raise NotImplementedError("evaluate_depth: --cat2end with --refine_2d is not covered (the reference's refine branch reads "
+                                      "beam_features, which its --cat2end branch never computes)")
+    elif opt.eval_gdc:
+        raise NotImplementedError("evaluate_depth: --eval_gdc with --ext_disp_to_eval is not covered (the reference's dates are undefined there)")
+
+
+def _read_lines(path):
+    with open(path) as fh:
+        return [ln for ln in fh.read().splitlines() if ln.strip()]
+
+
+def predict_disps(predictor, batch, opt):
+    """evaluate_depth.py:166-242 for one batch -> [B,192,640] host array of scaled disparities (float32; float64 with --post_process)."""
+    keys = ["2channel", "4beam"] + [("inv_K", s) for s in opt.scales]
+    color = batch["color", 0, 0]
+    B = color.shape[0]
+    if opt.post_process:                                         # two passes per image, the second mirrored (LiDAR maps included)
+        inputs = {("color_aug", 0, 0): torch.cat((color, torch.flip(color, [3])), 0)}
+        for k in keys:
+            if k in batch:
+                second = torch.flip(batch[k], [3]) if isinstance(k, str) else batch[k]
+                inputs[k] = torch.cat((batch[k], second), 0)
+    else:
+        inputs = {("color_aug", 0, 0): color}
+        inputs.update({k: batch[k] for k in keys if k in batch})
+    disp = predictor.predict(inputs)[("disp", 0)]
+    if tuple(disp.shape[2:]) != (192, 640):                      # :235-236, the reference's fixed size
+        disp = FD.bilinear_upsample(disp, (192, 640)) if disp.shape[2] <= 192 and disp.shape[3] <= 640 else \
+            torch.nn.functional.interpolate(disp, [192, 640], mode="bilinear", align_corners=False)
+    pred_disp = FD.disp_to_depth(disp, opt.min_depth, opt.max_depth)[0][:, 0]
+    if opt.post_process:
+        pred_disp = batch_post_process_disparity(pred_disp[:B].contiguous(), torch.flip(pred_disp[B:], [2]).contiguous())
+    return pred_disp.cpu().numpy()
+
+
+def evaluate(opt, splits_dir="splits"):
+    """evaluate_depth.py:74-489: the disparities of a saved model over ``<splits_dir>/<eval_split>/test_files.txt`` (or those of
+    ``--ext_disp_to_eval``), scored against ``gt_depths.npz`` of the split.  Returns ``(mean[7], ratios, per_image[N,7])``
+    (``per_image`` is None with ``--eval_gdc``, which scores through ``evaluate_predictions``); None after ``--no_eval`` and for the
+    ``benchmark`` split, which has no ground truth."""
+    _refuse_uncovered(opt)
+    dates = []
+    if opt.ext_disp_to_eval is None:
+        from .datasets import KITTIRAWBatches
+        from .predict import Predictor
+        if opt.load_weights_folder is None:
+            raise ValueError("evaluate_depth: --load_weights_folder is required")
+        opt.load_weights_folder = folder = os.path.expanduser(opt.load_weights_folder)
+        if not os.path.isdir(folder):
+            raise FileNotFoundError("Cannot find a folder at {}".format(folder))
+        print("-> Loading weights from {}".format(folder))
+        filenames = _read_lines(os.path.join(splits_dir, opt.eval_split, "test_files.txt"))
+        enc = torch.load(os.path.join(folder, "encoder.pth"), map_location="cpu")
+        height, width = int(enc.get("height", opt.height)), int(enc.get("width", opt.width))
+        del enc
+        if opt.eval_gdc:
+            opt.eval_batch_size = 1
+        predictor = Predictor(folder, num_layers=opt.num_layers, scales=tuple(opt.scales), cat_4beam_to_color=opt.cat_4beam_to_color,
+                              cat2start=opt.cat2start, cat2end=opt.cat2end, refine_2d=opt.refine_2d, catxy=(opt.catxy == "true"),
+                              refine2d_deep=(opt.refine2d_deep == "true"), refine_a0=(opt.refine_a0 == "true"),
+                              refine_iter=opt.refine_iter, refine_offset=opt.refine_offset,
+                              refine_depthnet_with_beam=(opt.refine_depthnet_with_beam == "true"), height=height, width=width,
+                              min_depth=opt.min_depth, max_depth=opt.max_depth)
+        loader = KITTIRAWBatches(opt.data_path, filenames, height, width, [0], 4, is_train=False, img_ext=".png" if opt.png else ".jpg",
+                                 opt=opt, batch_size=opt.eval_batch_size, drop_last=False)
+        print("-> Computing predictions with size {}x{}".format(width, height))
+        pred_disps = []
+        for batch in loader:
+            dates += batch["date"]
+            pred_disps.append(predict_disps(predictor, batch, opt))
+        loader.close()
+        pred_disps = np.concatenate(pred_disps)
+    else:
+        print("-> Loading predictions from {}".format(opt.ext_disp_to_eval))
+        pred_disps = np.load(opt.ext_disp_to_eval)
+        if opt.eval_eigen_to_benchmark:
+            pred_disps = pred_disps[np.load(os.path.join(splits_dir, "benchmark", "eigen_to_benchmark_ids.npy"))]
+
+    if opt.save_pred_disps:
+        output_path = os.path.join(opt.load_weights_folder, "disps_{}_split.npy".format(opt.eval_split))
+        print("-> Saving predicted disparities to ", output_path)
+        np.save(output_path, pred_disps)
+
+    if opt.no_eval:
+        print("-> Evaluation disabled. Done.")
+        return None
+    if opt.eval_split == "benchmark":
+        from PIL import Image
+        save_dir = os.path.join(opt.load_weights_folder, "benchmark_predictions")
+        print("-> Saving out benchmark predictions to {}".format(save_dir))
+        os.makedirs(save_dir, exist_ok=True)
+        for a in range(0, len(pred_disps), 64):
+            resized = FD.resize_linear_cv(FD.f32(torch.as_tensor(pred_disps[a:a + 64])).cuda(), (352, 1216)).cpu().numpy()
+            for k, depth in enumerate(benchmark_depth_png(resized)):
+                Image.fromarray(depth).save(os.path.join(save_dir, "{:010d}.png".format(a + k)))
+        print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
+        return None
+
+    gt_depths = np.load(os.path.join(splits_dir, opt.eval_split, "gt_depths.npz"), fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
+    print("-> Evaluating")
+    if opt.eval_stereo:
+        print("   Stereo evaluation - disabling median scaling, scaling by {}".format(STEREO_SCALE_FACTOR))
+        opt.disable_median_scaling = True
+        opt.pred_depth_scale_factor = STEREO_SCALE_FACTOR
+    else:
+        print("   Mono evaluation - using median scaling")
+    if opt.eval_gdc:
+        from . import kitti_utils
+        if opt.random_sample == -1:
+            print("using {} beams LiDAR".format(opt.nbeams))
+            beam_path = os.path.join(splits_dir, opt.eval_split, "{}beam.npz".format(opt.nbeams))
+        else:
+            beam_path = os.path.join(splits_dir, opt.eval_split, "r{}.npz".format(opt.random_sample))
+        beam_depths = np.load(beam_path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
+        calibs = [kitti_utils.Calibration(os.path.join(opt.data_path, d, "calib_cam_to_cam.txt")) for d in dates]
+        mean_errors, ratios = evaluate_predictions(pred_disps, gt_depths, opt.eval_split, opt.pred_depth_scale_factor,
+                                                   opt.disable_median_scaling, True, beam_depths, calibs, opt.random_sample, opt.nbeams)
+        per_image = None
+    else:
+        per_image, ratios, _ = eigen_scores(pred_disps, list(gt_depths), opt.eval_split, opt.pred_depth_scale_factor,
+                                            opt.disable_median_scaling)
+        mean_errors = per_image.mean(0)
+    if not opt.disable_median_scaling:
+        med = np.median(ratios)
+        print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
+    print("\n  " + ("{:>8} | " * 7).format(*METRICS))
+    print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
+    print("\n-> Done!")
+    return mean_errors, ratios, per_image
+
+
+def main(argv=None):
+    from .options import MonodepthOptions
+    splits_dir, rest = split_off_splits_dir(sys.argv[1:] if argv is None else argv)
+    return evaluate(MonodepthOptions().parse(rest), splits_dir)
+
+
+if __name__ == "__main__":
+    main()

@@ -39,8 +39,10 @@ extern "C" {
  * 6: additions only: the image half of the KITTI loader (fd_resize_lanczos_u8_ws_bytes, fd_resize_lanczos_u8, fd_color_jitter_u8_ws_bytes,
  *    fd_color_jitter_u8_means_offset, fd_color_jitter_u8, fd_u8_to_planes, struct fd_jitter_desc).  Nothing removed, no signature changed.
  * 7: additions only: KITTI depth completion (fd_depth_png_keys + struct fd_depth_png_desc, fd_completion_ws_bytes, fd_completion_medians,
- *    fd_completion_errors).  Nothing removed, no signature changed. */
-#define FD_ABI_VERSION 7
+ *    fd_completion_errors).  Nothing removed, no signature changed.
+ * 8: additions only: the batched Eigen-split scorer (fd_eigen_scores_ws_bytes, fd_eigen_scores, struct fd_eigen_desc).  Nothing
+ *    removed, no signature changed. */
+#define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
 const char* fd_supported_arch(void); /* "gfx950" */
@@ -777,6 +779,38 @@ int fd_completion_medians(const float* pred, const float* gt, int N, int H, int 
                           float* out /*[N][4]*/, void* ws, void* stream);
 int fd_completion_errors(const float* pred, const float* gt, const float* ratio /*[N] or NULL*/, int N, int H, int W,
                          float gt_min, float pred_scale, float lo, float hi, double* out /*[N][5]*/, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ Eigen-split scoring --------
+ * The per-image loop of evaluate_depth.py:344-478 (without GDC) for N images whose ground-truth maps differ in size, in ONE call of
+ * 6 launches (5 without median scaling), whatever N is (csrc/eigen_eval.hip).
+ *   disp     [M][h][w] predicted disparities;  packed: the ground-truth planes, image n at `offset`, H x W, row-major.
+ *   desc     DEVICE array of N descriptors.  The mask of image n is  gt > gt_lo && gt < gt_hi  inside rows [y0, y1), columns [x0, x1)
+ *            (gt_hi = +inf: no upper bound).  A descriptor whose plane leaves `packed`, whose window leaves the plane or whose `pred`
+ *            is not in [0, M) gives a NaN row with count -1; nothing outside the buffers is read.
+ * At every selected pixel, and only there: OpenCV's float32 INTER_LINEAR resize of disp[pred] to H x W from its four taps (the
+ * arithmetic of fd_resize_linear_cv: horizontal pass first, separate multiplies and adds), 1 / that (IEEE division), * pred_scale.
+ * The (gt, pred) pairs are compacted in row-major order (counts per window row, a scan, then the writes: every position is a function
+ * of the data alone).  median_scaling != 0: ratio = median(gt) / median(pred) with numpy's medians (radix select over the compact
+ * lists; an even count takes the float32 mean of the two middle values) and pred *= ratio.  Then p = pred < lo ? lo : pred > hi ? hi : pred
+ * (a NaN stays) and the terms of compute_errors (evaluate_depth.py:42-60) in float32, one rounding per numpy operation; the log term
+ * is (float)(log((double)gt) - log((double)p)) squared in float32 (numpy's float32 log is not correctly rounded and cannot be
+ * restated bit for bit).  The sums run in float64 over a fixed grid of partials, added in index order: no float atomics, bitwise
+ * reproducible.
+ *   out[n] = { abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio, count } as float64; ratio is NaN without median scaling; an
+ *   empty selection gives NaN metrics and count 0, a NaN prediction what numpy gives (NaN for the first four and the ratio, a1-a3 = 0).
+ *   ws: fd_eigen_scores_ws_bytes(N, max_rows, list_cap) bytes, 8-byte aligned, where max_rows >= y1 - y0 of every image and
+ *   list_cap >= the sum of (y1 - y0) * (x1 - x0) over the images.  N <= 4096.  packed, desc 8-byte aligned. */
+typedef struct fd_eigen_desc {
+    long offset;                  /* first float of the ground-truth plane in `packed` */
+    int H, W;                     /* its size */
+    int pred;                     /* index of the disparity plane */
+    int y0, y1, x0, x1;           /* the mask window: rows [y0, y1), columns [x0, x1) */
+    int reserved;
+} fd_eigen_desc;
+long fd_eigen_scores_ws_bytes(int N, int max_rows, long list_cap);
+int fd_eigen_scores(const float* disp, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
+                    int max_rows, long list_cap, float gt_lo, float gt_hi, float pred_scale, int median_scaling, float lo, float hi,
+                    double* out /*[N][9]*/, void* ws, void* stream);
 
 #ifdef __cplusplus
 }
