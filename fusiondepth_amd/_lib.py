@@ -78,6 +78,11 @@ class EigenDesc(ctypes.Structure):
     _fields_ = [("offset", _L)] + [(n, _I) for n in ("H", "W", "pred", "y0", "y1", "x0", "x1", "reserved")]
 
 
+class ExportDesc(ctypes.Structure):
+    """Mirror of ``fd_export_desc``."""
+    _fields_ = [("offset", _L), ("H", _I), ("W", _I), ("pred", _I), ("reserved", _I)]
+
+
 class RelayoutJob(ctypes.Structure):
     """Mirror of ``fd_relayout_job``."""
     _fields_ = ([("w", ctypes.c_void_p), ("dst", ctypes.c_void_p)] +
@@ -207,6 +212,8 @@ SIGNATURES = {
     "fd_completion_errors": ("ppp" "iii" "ffff" "p" "pp", "i"),
     "fd_eigen_scores_ws_bytes": ("iil", "l"),
     "fd_eigen_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "p" "pp", "i"),
+    "fd_depth_export": ("piii" "pi" "lii" "f" "ppp" "p", "i"),
+    "fd_depth_quantize_u16": ("pplp", "i"),
 }
 
 _lock = threading.Lock()

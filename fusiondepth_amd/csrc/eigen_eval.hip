@@ -18,6 +18,7 @@
 // Every float32 step below is one rounding, as numpy does it: contraction is off for the whole file.
 #include "../../include/fdhip.h"
 #include "fd_common.h"
+#include "cv_resize.h"                                          // OpenCV's INTER_LINEAR coefficients (cv_linear_coeff)
 
 #pragma clang fp contract(off)
 
@@ -53,17 +54,6 @@ __device__ __forceinline__ long window_area(const fd_eigen_desc& d, const Args& 
 }
 __device__ __forceinline__ bool selected(float g, float gt_lo, float gt_hi, bool no_hi) { return g > gt_lo && (no_hi || g < gt_hi); }
 
-// OpenCV's INTER_LINEAR coefficients, as geometry.hip's cv_linear_coeff
-__device__ __forceinline__ void cv_coeff(int d, double scale, int n_in, int& s0, int& s1, float& w0, float& w1) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n_in - 1) { s = n_in - 1; f = 0.f; }
-    s0 = s; s1 = s + 1 < n_in ? s + 1 : n_in - 1;
-    w0 = 1.0f - f; w1 = f;
-}
-
 // ---------------------------------------------------------------------------------------------- 1, 3: count and compact
 template <bool WRITE>
 __global__ void __launch_bounds__(ROW_WAVES * 64) k_eigen_rows(Args a) {
@@ -84,7 +74,7 @@ __global__ void __launch_bounds__(ROW_WAVES * 64) k_eigen_rows(Args a) {
     if (WRITE) {
         at = a.info[n].base + a.rows[(long)n * a.max_rows + r];
         dp = a.disp + (long)d.pred * a.h * a.w;
-        cv_coeff(y, (double)a.h / (double)d.H, a.h, ya, yb, b0, b1);
+        cv_linear_coeff(y, (double)a.h / (double)d.H, a.h, ya, yb, b0, b1);
         sx = (double)a.w / (double)d.W;
     }
     int count = 0;
@@ -96,7 +86,7 @@ __global__ void __launch_bounds__(ROW_WAVES * 64) k_eigen_rows(Args a) {
         if (WRITE && sel) {
             int xa, xb;
             float a0, a1;
-            cv_coeff(x, sx, a.w, xa, xb, a0, a1);
+            cv_linear_coeff(x, sx, a.w, xa, xb, a0, a1);
             const float r0 = dp[ya * a.w + xa] * a0 + dp[ya * a.w + xb] * a1;
             const float r1 = dp[yb * a.w + xa] * a0 + dp[yb * a.w + xb] * a1;
             const float dv = r0 * b0 + r1 * b1;

@@ -5,6 +5,7 @@
 
 #include "../../include/fdhip.h"
 #include "fd_common.h"
+#include "cv_resize.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -469,16 +470,7 @@ extern "C" int fd_cat_xy_fwd(const float* depth, const float* inv_K, float* out,
 // cv2.resize(img, (Wout, Hout)) with INTER_LINEAR on a float32 image (evaluate_depth.py:349): OpenCV's coefficient rule
 // (resize.cpp: scale in double, source coordinate rounded to float, floor, edge rule) and its two float32 passes, horizontal first.
 // Not ATen's rule (k_bilinear_fwd computes the coordinate in float32 throughout): at x ~ 600 the two differ by ~6e-5 in the weight.
-__device__ __forceinline__ void cv_linear_coeff(int d, double scale, int n_in, int& s0, int& s1, float& w0, float& w1) {
-#pragma clang fp contract(off)     // no FMA contraction (HIP's __fmul_rn / __dmul_rn are plain operators): OpenCV's scalar arithmetic
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n_in - 1) { s = n_in - 1; f = 0.f; }
-    s0 = s; s1 = s + 1 < n_in ? s + 1 : n_in - 1;
-    w0 = 1.0f - f; w1 = f;
-}
+// The coefficient rule is cv_linear_coeff (cv_resize.h), shared with the scorer and the exporter.
 __global__ void k_resize_linear_cv(const float* __restrict__ x, float* __restrict__ y, int Hin, int Win, int Hout, int Wout) {
     const int pl = blockIdx.y;
     const long Po = (long)Hout * Wout;

@@ -83,12 +83,14 @@ def gdc_range(random_sample=-1, nbeams=4):
 
 
 def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False,
-                         eval_gdc=False, beam_depths=None, calibs=None, random_sample=-1, nbeams=4):
+                         eval_gdc=False, beam_depths=None, calibs=None, random_sample=-1, nbeams=4, on_depth=None):
     """evaluate_depth.py:344-478.  ``pred_disps``: [N,h,w] device tensor (or list); ``gt_depths``: list of [H_i,W_i] arrays /
     tensors (KITTI ground truth has per-drive sizes).  Returns (mean of the 7 metrics over the images, per-image scaling ratios).
     ``eval_gdc`` (--eval_gdc, evaluate_depth.py:387-405): after median scaling, correct each prediction with GDC against
     ``beam_depths[i]`` (the sparse LiDAR map at ground-truth size, 0 = no point) and ``calibs[i]`` (``kitti_utils.Calibration``),
-    with the reference's settings and pitch range (``gdc_range(random_sample, nbeams)``)."""
+    with the reference's settings and pitch range (``gdc_range(random_sample, nbeams)``).  ``on_depth``: an optional callback
+    ``(i, depth)`` that sees image i's dense [H_i,W_i] device map after scaling and GDC, before the clamp (export_detection.py:388
+    saves it there); the default changes nothing."""
     if eval_gdc:
         from .gdc import GDC
         if beam_depths is None or calibs is None:
@@ -120,6 +122,8 @@ def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_s
             gtd[gtd == 0] = -1
             pred_depth = GDC(pred_depth, gtd, calibs[i], W_tol=3e-5, recon_tol=5e-4, k=10, method="cg",
                              consider_range=gdc_range(random_sample, nbeams), idx=i)
+        if on_depth is not None:
+            on_depth(i, pred_depth)
         pred, g = torch.clamp(pred_depth[mask], MIN_DEPTH, MAX_DEPTH), gt[mask]
         errors.append(compute_errors(g, pred))
     return np.array(errors).mean(0), np.array(ratios)
@@ -280,6 +284,20 @@ def predict_disps(predictor, batch, opt):
     return pred_disp.cpu().numpy()
 
 
+def save_benchmark_predictions(opt, pred_disps):
+    """evaluate_depth.py:291-311: the ``benchmark`` split has no ground truth; its predictions go to 352x1216 16-bit PNGs under
+    ``<load_weights_folder>/benchmark_predictions``."""
+    from PIL import Image
+    save_dir = os.path.join(opt.load_weights_folder, "benchmark_predictions")
+    print("-> Saving out benchmark predictions to {}".format(save_dir))
+    os.makedirs(save_dir, exist_ok=True)
+    for a in range(0, len(pred_disps), 64):
+        resized = FD.resize_linear_cv(FD.f32(torch.as_tensor(pred_disps[a:a + 64])).cuda(), (352, 1216)).cpu().numpy()
+        for k, depth in enumerate(benchmark_depth_png(resized)):
+            Image.fromarray(depth).save(os.path.join(save_dir, "{:010d}.png".format(a + k)))
+    print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
+
+
 def evaluate(opt, splits_dir="splits"):
     """evaluate_depth.py:74-489: the disparities of a saved model over ``<splits_dir>/<eval_split>/test_files.txt`` (or those of
     ``--ext_disp_to_eval``), scored against ``gt_depths.npz`` of the split.  Returns ``(mean[7], ratios, per_image[N,7])``
@@ -332,15 +350,7 @@ def evaluate(opt, splits_dir="splits"):
         print("-> Evaluation disabled. Done.")
         return None
     if opt.eval_split == "benchmark":
-        from PIL import Image
-        save_dir = os.path.join(opt.load_weights_folder, "benchmark_predictions")
-        print("-> Saving out benchmark predictions to {}".format(save_dir))
-        os.makedirs(save_dir, exist_ok=True)
-        for a in range(0, len(pred_disps), 64):
-            resized = FD.resize_linear_cv(FD.f32(torch.as_tensor(pred_disps[a:a + 64])).cuda(), (352, 1216)).cpu().numpy()
-            for k, depth in enumerate(benchmark_depth_png(resized)):
-                Image.fromarray(depth).save(os.path.join(save_dir, "{:010d}.png".format(a + k)))
-        print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
+        save_benchmark_predictions(opt, pred_disps)
         return None
 
     gt_depths = np.load(os.path.join(splits_dir, opt.eval_split, "gt_depths.npz"), fix_imports=True, encoding="latin1", allow_pickle=True)["data"]

@@ -41,7 +41,10 @@ extern "C" {
  * 7: additions only: KITTI depth completion (fd_depth_png_keys + struct fd_depth_png_desc, fd_completion_ws_bytes, fd_completion_medians,
  *    fd_completion_errors).  Nothing removed, no signature changed.
  * 8: additions only: the batched Eigen-split scorer (fd_eigen_scores_ws_bytes, fd_eigen_scores, struct fd_eigen_desc).  Nothing
- *    removed, no signature changed. */
+ *    removed, no signature changed.
+ *    Added later WITHOUT raising the number: the KITTI 3-D detection depth export (fd_depth_export + struct fd_export_desc,
+ *    fd_depth_quantize_u16).  Nothing removed, no signature changed: a client built against 8 runs unchanged, and one that wants the
+ *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8. */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -811,6 +814,35 @@ long fd_eigen_scores_ws_bytes(int N, int max_rows, long list_cap);
 int fd_eigen_scores(const float* disp, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
                     int max_rows, long list_cap, float gt_lo, float gt_hi, float pred_scale, int median_scaling, float lo, float hi,
                     double* out /*[N][9]*/, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ detection depth export -----
+ * The dense part of export_detection.py:317-392 for N maps of different sizes in ONE launch (csrc/detection.hip): the whole predicted
+ * depth map at each image's own size, scaled and quantised to the 16-bit PNG payload.
+ *   disp     [M][h][w] predicted disparities.
+ *   desc     DEVICE array of N descriptors: map n is H x W, row-major, at element `offset` of the packed outputs, computed from
+ *            disp[pred].  Planes lie back to back at arbitrary (odd included) element offsets; nothing is assumed about alignment.
+ *            A descriptor whose plane leaves [0, packed_elems), whose size is not positive or whose `pred` is not in [0, M) writes
+ *            nothing.  max_H / max_W >= every H / W (they size the grid; a larger map is written only up to them).
+ * For every output pixel, each step ONE float32 rounding, no contraction:
+ *   d = OpenCV's float32 INTER_LINEAR resize of disp[pred] to H x W (the arithmetic of fd_resize_linear_cv / fd_eigen_scores:
+ *       coefficients in double -> float, horizontal pass first, separate multiplies and adds);
+ *   p = 1 / d (IEEE division);  p *= pred_scale;  p *= ratio[n] when ratio != NULL;  q = p * 256.
+ * depth_out (float32, packed_elems, or NULL) receives p, u16_out (uint16, packed_elems, or NULL) the quantised q; at least one of
+ * them is given.  The quantiser is truncation toward zero - numpy's astype(np.uint16) in range.  Out of range numpy's cast is
+ * undefined; here it is DEFINED: NaN and negative q -> 0, q >= 65535 (+inf included) -> 65535.
+ * No workspace, no atomics; every store is a plain vector store, 16 bytes per lane wherever the row segment is 16-byte aligned
+ * (the address decides, not the descriptor), narrower at a row's head and tail.  N <= 65535.
+ * fd_depth_quantize_u16: the same quantiser on a contiguous float64 plane of n values (the map GDC returns); q = x * 256 is a float64
+ * product there, as numpy computes it for the reference's float64 map. */
+typedef struct fd_export_desc {
+    long offset;                  /* first element of the map in the packed outputs */
+    int H, W;                     /* its size */
+    int pred;                     /* index of the disparity plane */
+    int reserved;
+} fd_export_desc;
+int fd_depth_export(const float* disp, int M, int h, int w, const fd_export_desc* desc, int N, long packed_elems, int max_H, int max_W,
+                    float pred_scale, const float* ratio /*[N] or NULL*/, float* depth_out, uint16_t* u16_out, void* stream);
+int fd_depth_quantize_u16(const double* x, uint16_t* out, long n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,11 +3,19 @@ against the per-image ATen loop ``evaluate_depth.evaluate_predictions`` on the s
 disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct maps, cycled), the ``eigen`` split with median scaling.
 
     python scripts/bench_eval.py [--reps 10] [--out profiles/eigen_eval_time.log]
+    python scripts/bench_eval.py --step detection [--reps 10] [--out profiles/detection_export_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
 around a synchronise.  The call's traffic bound: the ground truth inside the windows once, four taps per selected pixel, the compact
-(gt, pred) lists written once and read once; at 6.3 TB/s (achievable HBM, as elsewhere in profiles/)."""
+(gt, pred) lists written once and read once; at 6.3 TB/s (achievable HBM, as elsewhere in profiles/).
+
+``--step detection``: the dense part of the detection export, ``detection.depth_export`` (fd_depth_export, csrc/detection.hip), at N = 1 and
+64 maps of 375x1242 from 192x640 disparities with per-image ratios, against the recipe that was available before it: one
+``FD.resize_linear_cv`` per image, the reciprocal and two multiplies in torch, ``.cpu()``, ``(x * 256).astype(np.uint16)``.  Both on the
+same box in the same run, alternating, after the two were compared bit for bit.  Per N: the library call alone between device events
+(uint16 output only, as the script calls it) with its traffic bound - the bytes written plus the source read once, at 6.3 TB/s -, the
+recipe's device part between events, and both end to end (uploads of descriptors and ratios, the download) as wall time."""
 import argparse
 import os
 import sys
@@ -84,11 +92,97 @@ def library_call(disps, gts):
     return run, packed, bound, selected
 
 
+def alternate(fns, reps, timer):
+    """The callables in turn, ``reps`` rounds after one warm-up round -> per callable (median, min, max) of ``timer(fn)`` [ms]."""
+    ts = [[] for _ in fns]
+    for _ in range(reps + 1):
+        for k, fn in enumerate(fns):
+            ts[k].append(timer(fn))
+    return [(float(np.median(t[1:])), float(min(t[1:])), float(max(t[1:]))) for t in ts]
+
+
+def _event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def _wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0)
+
+
+def detection_step(a):
+    from fusiondepth_amd import detection as D
+    from fusiondepth_amd import functional as FD
+    H, W, h, w = 375, 1242, 192, 640
+    rng = np.random.RandomState(5)
+    lines = ["Detection depth export, %dx%d disparities -> %dx%d uint16 maps with per-image ratios; median of %d (min, max) after one "
+             "warm-up round, exporter and recipe alternating" % (h, w, H, W, a.reps)]
+    for n in (1, 64):
+        disps = torch.from_numpy(rng.uniform(0.02, 0.6, (n, h, w)).astype(np.float32)).cuda()
+        ratios = rng.uniform(1.2, 1.4, n).astype(np.float32)
+        ratios_t = [torch.tensor(r, dtype=torch.float32, device="cuda") for r in ratios]
+        sizes = [(H, W)] * n
+        desc, total = D.pack_export_sizes(sizes)
+        desc_d = torch.from_numpy(desc.view(np.uint8).copy()).cuda()
+        ratio_d = torch.from_numpy(ratios).cuda()
+        out = torch.empty((total,), device="cuda", dtype=torch.int16)
+
+        def kernel():
+            call("fd_depth_export", disps.data_ptr(), n, h, w, desc_d.data_ptr(), n, total, H, W, 1.0, ratio_d.data_ptr(), None, out.data_ptr(),
+                 stream())
+
+        def recipe_device():
+            return [(1.0 / FD.resize_linear_cv(disps[i][None, None], (H, W))[0, 0]) * 1.0 * ratios_t[i] for i in range(n)]
+
+        def recipe():
+            return [((1.0 / FD.resize_linear_cv(disps[i][None, None], (H, W))[0, 0]) * 1.0 * ratios_t[i]).cpu().numpy() * 256 for i in range(n)]
+
+        def recipe_all():
+            return [x.astype(np.uint16) for x in recipe()]
+
+        def exporter_all():
+            return D.depth_export(disps, sizes, ratios=ratios)
+
+        got, want = exporter_all(), recipe_all()                 # in range the recipe's cast is defined: the two agree bit for bit
+        assert all(np.array_equal(g, x) for g, x in zip(got, want)), "exporter and recipe disagree"
+        t_k, t_rd = alternate([kernel, recipe_device], a.reps, _event_ms)
+        t_e, t_r = alternate([exporter_all, recipe_all], a.reps, _wall_ms)
+        bound = 2 * total + 4 * n * h * w
+        t_bound = 1e3 * bound / HBM
+        lines.append("  N = %2d: fd_depth_export, resident, uint16 only: %.3f ms (%.3f, %.3f) = %.1f us / image; traffic bound %.2f MB = %.2f us "
+                     "at 6.3 TB/s -> %.1fx the bound; the recipe's device part (%d launches): %.3f ms (%.3f, %.3f) -> %.2fx"
+                     % (n, t_k[0], t_k[1], t_k[2], 1e3 * t_k[0] / n, bound / 1e6, 1e3 * t_bound, t_k[0] / t_bound, 4 * n, t_rd[0], t_rd[1], t_rd[2],
+                        t_rd[0] / t_k[0]))
+        lines.append("          depth_export end to end (descriptor and ratio uploads, 1 call, pinned download of %.1f MB): %.3f ms (%.3f, %.3f) "
+                     "= %.3f ms / image; recipe end to end (float32 download, host * 256 and cast): %.3f ms (%.3f, %.3f) = %.3f ms / image -> %.2fx"
+                     % (2 * total / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, t_r[0], t_r[1], t_r[2], t_r[0] / n, t_r[0] / t_e[0]))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eigen_eval_time.log"))
+    ap.add_argument("--step", choices=("eigen", "detection"), default="eigen")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "eigen_eval_time.log" if a.step == "eigen" else "detection_export_time.log")
+    if a.step == "detection":
+        text = "\n".join(detection_step(a))
+        print(text)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+        return
     rng = np.random.RandomState(5)
     lines = ["Eigen-split scorer, 192x640 disparities, 375x1242 ground truth with 5 %% valid pixels, eigen split, median scaling; "
              "median of %d (min, max) after one warm-up" % a.reps]
