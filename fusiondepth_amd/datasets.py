@@ -49,8 +49,14 @@ them straight into one pinned staging buffer that also carries the descriptor ta
 ONE library call (``fd_resize_bilinear_batch``) per batch.  Shape ``[B, height, width]``, the reference's squeezed shape (it
 hardcodes ``[192, 640]``: the same deviation as ``4beam``, identical at the default size).  Every other key is the parent's.
 
-Not covered (each raises): the stereo frame ``"s"``, ``need_full_res_4beam`` (needs cv2; ``4beam_full`` / ``2channel_full`` are read by
-nothing in the reference); in ``KITTIRAWBatches`` itself also ``need_inf_gdc`` / ``clone_gdc`` - those are ``KITTIRefinerBatches``'.
+The stereo loader.  ``KITTIStereoBatches`` is ``KITTIRAWBatches`` plus the stereo partner ``"s"`` of ``--use_stereo``
+(mono_dataset.py:156-163, 216-222): ``("color" | "color_aug", "s", scale)`` = the other camera's image at the item's own frame index,
+with the item's flip and jitter draw, and ``"stereo_T"`` [B,4,4], built on the host for the batch and sent with one upload.  ``"s"``
+has no LiDAR scan and no ``("2channel", "s", 0)``.  Every other key is the parent's.
+
+Not covered (each raises): ``need_full_res_4beam`` (needs cv2; ``4beam_full`` / ``2channel_full`` are read by nothing in the
+reference); the stereo frame ``"s"`` everywhere but in ``KITTIStereoBatches``; in ``KITTIRAWBatches`` itself also ``need_inf_gdc`` /
+``clone_gdc`` - those are ``KITTIRefinerBatches``'.
 """
 import concurrent.futures
 import ctypes
@@ -171,6 +177,14 @@ class KITTIRAWBatches:
     def get_velo_path(self, folder, frame_index):
         return os.path.join(self.data_path, folder, "velodyne_points/data/{:010d}.bin".format(int(frame_index)))
 
+    def frame_image_path(self, folder, frame_index, side, f):
+        """The image of frame slot ``f`` of an item (mono_dataset.py:156-161)."""
+        return self.get_image_path(folder, frame_index + f, side)
+
+    def lidar_frames(self):
+        """The frame slots that have a LiDAR scan of their own, in the order of the per-frame LiDAR keys."""
+        return self.frame_idxs
+
     def beam_folder(self):
         random_sample = self._opt("random_sample", -1)
         return "random{}".format(random_sample) if random_sample > 0 else "{}beam".format(self._opt("nbeams", 4))
@@ -240,10 +254,10 @@ class KITTIRAWBatches:
             d = self.item_draws(epoch, index)
             item = {"index": index, "folder": folder, "frame_index": frame_index, "side": side, "date": folder.split("/")[0],
                     "do_flip": bool(d["do_flip"]), "jitter": d["jitter"] if d["do_color_aug"] else None,
-                    "images": [self.get_image_path(folder, frame_index + f, side) for f in self.frame_idxs],
+                    "images": [self.frame_image_path(folder, frame_index, side, f) for f in self.frame_idxs],
                     "beams": [], "velo": None}
             if self.need_4beam or self.need_2_channel:
-                frames = self.frame_idxs if self.need_2_channel else [0]
+                frames = self.lidar_frames() if self.need_2_channel else [0]
                 item["beams"] = [self.get_beam_path(folder, frame_index + f) for f in frames]
             if self.load_depth:
                 item["velo"] = self.get_velo_path(folder, frame_index)
@@ -371,10 +385,10 @@ class KITTIRAWBatches:
             slab, _ = data_ops.sparsify_scans(points, H, W, None if self.random_sample else self.line_spec, 1, self.random_sample, None,
                                         self.seed, keys, offsets=offsets)
             beams = data_ops.velo_rasterize_batch(slab, descs, (2 * self.height, 2 * self.width), desc_table=table).unsqueeze(1)
-            zero = self.frame_idxs.index(0) if self.need_2_channel else 0
+            zero = self.lidar_frames().index(0) if self.need_2_channel else 0
             if self.need_2_channel:
                 two = data_ops.scatter_2channel(beams, data_ops.scaled_roi(self.height, self.width))
-                for fi, f in enumerate(self.frame_idxs):
+                for fi, f in enumerate(self.lidar_frames()):
                     batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
             if self.need_4beam:
                 batch["4beam"] = beams[zero * B:(zero + 1) * B]
@@ -401,10 +415,10 @@ class KITTIRAWBatches:
                     beams.append(torch.flip(beam, dims=[1]) if it["do_flip"] else beam)
             beams = torch.stack(beams).unsqueeze(1).contiguous()
             B = len(items)
-            zero = self.frame_idxs.index(0) if self.need_2_channel else 0
+            zero = self.lidar_frames().index(0) if self.need_2_channel else 0
             if self.need_2_channel:                              # mono_dataset.py:162-163: one per frame, with or without need_4beam
                 two = data_ops.scatter_2channel(beams, data_ops.scaled_roi(self.height, self.width))
-                for fi, f in enumerate(self.frame_idxs):
+                for fi, f in enumerate(self.lidar_frames()):
                     batch[("2channel", f, 0)] = two[fi * B:(fi + 1) * B]
             if self.need_4beam:                                  # mono_dataset.py:193-206
                 batch["4beam"] = beams[zero * B:(zero + 1) * B]
@@ -479,6 +493,60 @@ class KITTIRAWBatches:
                 for t in self._tensors(batch):
                     t.record_stream(cur)
                 yield batch
+
+
+OTHER_SIDE = {"l": "r", "r": "l"}                             # mono_dataset.py:157
+
+
+def stereo_T(side, do_flip):
+    """mono_dataset.py:216-222: the pose of the stereo partner, a 0.1 baseline along x whose sign depends on the side and the flip."""
+    T = np.eye(4, dtype=np.float32)
+    T[0, 3] = (-1 if side == "l" else 1) * (-1 if do_flip else 1) * 0.1
+    return T
+
+
+class KITTIStereoBatches(KITTIRAWBatches):
+    """``KITTIRAWBatches`` for ``--use_stereo``: accepts the stereo partner ``"s"`` in ``frame_idxs`` (``[0, "s"]``, ``[0, -1, 1,
+    "s"]``) and adds ``("color" | "color_aug", "s", scale)`` and ``"stereo_T"``; see the module docstring.  Same arguments; every
+    other key is the parent's, and both ``lidar_source`` modes work.  With ``jitter_per_image`` the slot of ``"s"`` has its own
+    ``[scale]`` list of draws like every other frame slot.
+
+    ``"s"`` gets no ``("2channel", "s", 0)``: the dataset makes none (mono_dataset.py:156-163), and ``Trainer.predict_poses`` reads
+    that key for the temporal frames only.  The reference itself reads it for every frame id, so with stereo + temporal frames and
+    its default pose network it dies with a ``KeyError`` at trainer.py:334; this port does not."""
+
+    def _check_covered(self):
+        if self._opt("need_full_res_4beam"):
+            raise NotImplementedError("KITTIStereoBatches: need_full_res_4beam is not covered (the reference resizes with cv2)")
+        if self._opt("need_inf_gdc") or self._opt("clone_gdc"):
+            raise NotImplementedError("KITTIStereoBatches: need_inf_gdc / clone_gdc are not covered (no inf_gdc maps are loaded); "
+                                      "KITTIRefinerBatches loads them")
+        for f in self.frame_idxs:
+            if f != "s" and not isinstance(f, (int, np.integer)):
+                raise ValueError("KITTIStereoBatches: frame id %r is neither an integer nor 's'" % (f,))
+
+    def frame_image_path(self, folder, frame_index, side, f):
+        if f == "s":
+            return self.get_image_path(folder, frame_index, OTHER_SIDE[side])
+        return super().frame_image_path(folder, frame_index, side, f)
+
+    def lidar_frames(self):
+        return [f for f in self.frame_idxs if f != "s"]
+
+    def plan_batch(self, epoch, indices):
+        if "s" in self.frame_idxs:
+            for index in indices:
+                if parse_line(self.filenames[index])[2] not in OTHER_SIDE:
+                    raise ValueError("KITTIStereoBatches: the split line %r names no side ('l' or 'r'), so it has no stereo partner"
+                                     % (self.filenames[index],))
+        return super().plan_batch(epoch, indices)
+
+    def _finish_batch(self, items):
+        batch = super()._finish_batch(items)
+        if "s" in self.frame_idxs:
+            host = np.stack([stereo_T(it["side"], it["do_flip"]) for it in items])
+            batch["stereo_T"] = torch.from_numpy(host).to(self.device, non_blocking=True)
+        return batch
 
 
 def _load_map_into(path, dst):

@@ -146,6 +146,9 @@ def render_frame(image0, depth_units, K, inv_K, T_0_to_f, iterations=5):
     return sample(image0, p)
 
 
+STEREO_BASELINE_M = 0.54      # KITTI's stereo baseline
+
+
 def make_scene_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -1, 1), seed=1234, device="cuda", scatter=None,
                      gt_size=(375, 1242), clutter=0.0):
     """One minibatch of the consistent scene (see the module docstring), reference schema, float32 on ``device``.
@@ -170,6 +173,15 @@ def make_scene_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -
     for f in frame_ids:
         if f == 0:
             img = image0
+        elif f == "s":
+            # the stereo partner of an "l" item that is not flipped (mono_dataset.py:216-222): a pure sideways translation, rendered
+            # through the depth field like the temporal frames.  KITTI's 54 cm baseline in this scene's units (metres / 26, the
+            # LiDAR term's scale) is 0.0208, not the dataset's 0.1, which belongs to a depth scale of 5.4 m per unit: with 0.1 the
+            # near rows would shift by a quarter of the image.  The larger shift needs more fixed-point iterations than a frame step.
+            T = torch.eye(4, device=device).repeat(batch, 1, 1)
+            T[:, 0, 3] = -STEREO_BASELINE_M / 26.0
+            inputs["stereo_T"] = T
+            img = render_frame(image0, depth_m / 26.0, inputs[("K", 0)], inputs[("inv_K", 0)], T, iterations=16)
         else:
             T = scene_motion(batch, f, gen, device)
             inputs[("T_gt", f)] = T
@@ -181,7 +193,7 @@ def make_scene_batch(batch, height=192, width=640, num_scales=4, frame_ids=(0, -
             inputs[("color_aug", f, s)] = inputs[("color", f, s)]
     roi = data_ops.scaled_roi(height, width)
     rows = [int(height * q) for q in (0.52, 0.625, 0.73, 0.835)]
-    for i, f in enumerate(frame_ids):
+    for i, f in enumerate(f for f in frame_ids if f != "s"):    # the stereo partner has no scan of its own
         beam = torch.zeros(batch, 1, height, width, device=device)
         for r in rows:
             cols = torch.arange(2 + (r + i) % 3, width - 2, 3, device=device)

@@ -813,9 +813,12 @@ class Trainer:
             ident0 = self.identity_losses(inputs, 0) if (automask and not self.opt.v1_multiscale) else None
         noise_in = inputs.get("_noise")               # injected tie-break noise (tests); else drawn like trainer.py:551-552
         if self._multiscale_loss_ok(fids):
-            # default configuration: ALL scales in one launch that also produces the gradients (csrc/photometric_ms.hip)
+            # default configuration: ALL scales in one launch that also produces the gradients (csrc/photometric_ms.hip; with
+            # --use_stereo the one- / three-frame kernel of csrc/photometric_msn.hip, "s" posed by stereo_T: trainer.py:444-447)
             scales = list(self.opt.scales)
             B, _, H, W = inputs[("color", 0, 0)].shape
+            Ts = [inputs["stereo_T"] if f == "s" else outputs[("cam_T_cam", 0, f)] for f in fids]
+            Ts = [T if T.shape[0] == B else T.expand(B, 4, 4).contiguous() for T in Ts]
             noise = None
             if ident0 is not None:
                 if noise_in is not None:
@@ -825,7 +828,7 @@ class Trainer:
                                  torch.randn((len(scales), B, ident0.shape[1], H, W), device=ident0.device))
             lidar = [i for i, s in enumerate(scales) if s in si_scales]
             photo, si, sel = FD.photo_loss_ms(
-                [outputs[("disp", s)] for s in scales], [outputs[("cam_T_cam", 0, f)] for f in fids], inputs[("K", 0)],
+                [outputs[("disp", s)] for s in scales], Ts, inputs[("K", 0)],
                 inputs[("inv_K", 0)], [inputs[("color", f, 0)] for f in fids], inputs[("color", 0, 0)], ident0, noise,
                 inputs["4beam"] if lidar else None, lidar, self.photo_options, getattr(self, "_groups", 1))
             for i, scale in enumerate(scales):
@@ -893,13 +896,14 @@ class Trainer:
                         outputs[("color_identity", f, scale)] = inputs[("color", f, src_s)]
 
     def _multiscale_loss_ok(self, fids):
-        """The fused all-scales kernel covers the default loss configuration (two source frames, SSIM, per-frame minimum, one
-        pose per frame shared by the scales, no materialised warps); every flag variant keeps the per-scale kernels."""
+        """The fused all-scales kernels cover the default loss configuration (one to three source frames, the stereo partner "s"
+        among them or not, SSIM, per-frame minimum, one pose per frame shared by the scales, no materialised warps); every flag
+        variant keeps the per-scale kernels."""
         if not tuning.host.photo_ms:
             return False
         o = self.opt
         return (FD.photo_ms_supported(self.photo_options, len(fids), self.materialize_outputs) and not o.v1_multiscale
-                and o.pose_model_type != "posecnn" and not o.predictive_mask and "s" not in fids and 1 <= len(o.scales) <= 4
+                and o.pose_model_type != "posecnn" and not o.predictive_mask and 1 <= len(o.scales) <= 4
                 and all(o.height % (2 ** s) == 0 and o.width % (2 ** s) == 0 for s in o.scales))
 
     def compute_reprojection_loss(self, pred, target):

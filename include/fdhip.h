@@ -44,7 +44,8 @@ extern "C" {
  *    removed, no signature changed.
  *    Added later WITHOUT raising the number: the KITTI 3-D detection depth export (fd_depth_export + struct fd_export_desc,
  *    fd_depth_quantize_u16).  Nothing removed, no signature changed: a client built against 8 runs unchanged, and one that wants the
- *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8. */
+ *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8.
+ *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -276,6 +277,18 @@ int fd_photo_ms_fwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const 
 int fd_photo_ms_bwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* beam, const float* stats,
                     const float* const* g_photo, const float* const* g_si, float* d1, const float* ws,
                     float* const* d_disp, float* gP, void* stream);
+/* The same three entry points for ONE or THREE source frames (--use_stereo: frame_ids [0, "s"] and [0, -1, 1, "s"]; the stereo
+ * partner's pose is just one more P).  Semantics, layouts and `out` exactly as above with cfg.base.NF in {1, 3}: src[NF],
+ * P [B,NF,3,4], noise[s] / ident [B,NF,H,W], sel = index into cat(ident_0.., reproj_0..) (0 .. 2 NF - 1; 0 .. NF - 1 without
+ * ident), gP [B,NF,3,4].  One wave per source frame and strip (csrc/photometric_msn.hip); NF == 2 is refused here as NF != 2
+ * is above. */
+long fd_photo_msn_ws_floats(const fd_photo_ms_cfg* cfg);
+int fd_photo_msn_fwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* inv_K, const float* P,
+                     const float* const* src, const float* target, const float* ident, const float* const* noise,
+                     const float* beam, uint8_t* sel, float* d1, float* ws, float* out, void* stream);
+int fd_photo_msn_bwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* beam, const float* stats,
+                     const float* const* g_photo, const float* const* g_si, float* d1, const float* ws,
+                     float* const* d_disp, float* gP, void* stream);
 
 /* layers.py:235-248 get_smooth_loss on the mean-normalised disparity (trainer.py:569-571):
  * out[0] = get_smooth_loss(disp/(mean_hw(disp)+1e-7), img).  ws: fd_smooth_ws_floats(B,H,W). */
