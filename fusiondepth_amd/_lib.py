@@ -215,6 +215,8 @@ SIGNATURES = {
     "fd_completion_errors": ("ppp" "iii" "ffff" "p" "pp", "i"),
     "fd_eigen_scores_ws_bytes": ("iil", "l"),
     "fd_eigen_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "p" "pp", "i"),
+    "fd_val_scores_ws_bytes": ("iil", "l"),
+    "fd_val_scores": ("piii" "pl" "pi" "il" "ff" "p" "pp", "i"),
     "fd_depth_export": ("piii" "pi" "lii" "f" "ppp" "p", "i"),
     "fd_depth_quantize_u16": ("pplp", "i"),
 }

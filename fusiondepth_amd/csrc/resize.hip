@@ -9,21 +9,11 @@
 // gather bound by those rows: no LDS.
 #include "../../include/fdhip.h"
 #include "fd_common.h"
+#include "aten_resize.h"                                        // ATen's source-index rule (aten_src)
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// area_pixel_compute_source_index(align_corners=False) + the index / weight step of upsample_bilinear2d, float32
-__device__ __forceinline__ void aten_src(int dst, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-    float src = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);      // ONE rounding
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src;
-    i0 = i0 > n_in - 1 ? n_in - 1 : i0;                               // never taken for a valid size; keeps the loads in the plane
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.0f - l1;
-}
 
 __global__ void __launch_bounds__(256) k_resize_bilinear_batch(const float* __restrict__ packed, long packed_floats,
                                                                const fd_resize_desc* __restrict__ desc, int out_h, int out_w,

@@ -54,6 +54,14 @@ The stereo loader.  ``KITTIStereoBatches`` is ``KITTIRAWBatches`` plus the stere
 with the item's flip and jitter draw, and ``"stereo_T"`` [B,4,4], built on the host for the batch and sent with one upload.  ``"s"``
 has no LiDAR scan and no ``("2channel", "s", 0)``.  Every other key is the parent's.
 
+Rank sharding.  ``rank`` / ``world_size`` (inherited by every builder below and by the completion and detection loaders) give each
+process of a data-parallel job its own batches.  The global order of an epoch stays ``default_rng([seed, epoch]).permutation(n)``, the
+same on every rank; it is cut into global batches of ``batch_size``, of which only the first ``(n // (batch_size * world_size)) *
+world_size`` are used, and global batch k goes to rank ``k % world_size``.  Every rank therefore yields the same number of batches
+(``len(loader)``) - an unequal count would leave a rank alone in the gradient all-reduce - which is also why ``world_size > 1`` with
+``drop_last=False`` raises.  ``item_draws`` stays keyed by (seed, epoch, index): an item gets the same flip and jitter on whichever
+rank it lands.  With the defaults (rank 0 of 1) the order and every batch are what they were.
+
 Not covered (each raises): ``need_full_res_4beam`` (needs cv2; ``4beam_full`` / ``2channel_full`` are read by nothing in the
 reference); the stereo frame ``"s"`` everywhere but in ``KITTIStereoBatches``; in ``KITTIRAWBatches`` itself also ``need_inf_gdc`` /
 ``clone_gdc`` - those are ``KITTIRefinerBatches``'.
@@ -117,11 +125,12 @@ class KITTIRAWBatches:
     uint8`` instead of the PIL decoder (pre-decoded frames), ``prefetch`` = issue the next batch on a side stream before handing
     out the current one, ``lidar_source`` = ``"files"`` (sparse scans written offline) or ``"raw"`` (sparsified here from
     ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default: the reference's list for ``opt.nbeams``),
-    ``sparsify_grid`` = (H, W) of its angular grid."""
+    ``sparsify_grid`` = (H, W) of its angular grid, ``rank`` / ``world_size`` = this process's shard of every epoch (data-parallel
+    training; the defaults give the whole epoch, exactly as before)."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
                  batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
-                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True):
+                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True, rank=0, world_size=1):
         self.data_path, self.filenames = data_path, list(filenames)
         self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
         self.frame_idxs = list(frame_idxs)
@@ -134,6 +143,13 @@ class KITTIRAWBatches:
         self.draws, self.loader, self.prefetch = draws, loader or pil_loader, bool(prefetch)
         if self.batch_size < 1:
             raise ValueError("KITTIRAWBatches: batch_size must be positive")
+        self.rank, self.world_size = int(rank), int(world_size)
+        if self.world_size < 1 or not 0 <= self.rank < self.world_size:
+            raise ValueError("KITTIRAWBatches: rank %d is not in [0, world_size = %d)" % (self.rank, self.world_size))
+        if self.world_size > 1 and not self.drop_last:
+            raise ValueError("KITTIRAWBatches: world_size > 1 needs drop_last=True (a trailing partial batch would leave one rank "
+                             "alone in the gradient all-reduce)")
+        self.served = []                                         # (epoch, item indices) of every epoch handed out, in order
         self._check_covered()
         if 0 not in self.frame_idxs:
             raise ValueError("KITTIRAWBatches: frame_idxs must contain 0 (the frame every network and the LiDAR keys refer to)")
@@ -212,13 +228,21 @@ class KITTIRAWBatches:
 
     # ---- order and draws --------------------------------------------------------------------------------------------------------
     def __len__(self):
+        """Batches per epoch on THIS rank (the same number on every rank)."""
         n, B = len(self.filenames), self.batch_size
+        if self.world_size > 1:
+            return n // (B * self.world_size)
         return n // B if self.drop_last else (n + B - 1) // B
 
     def epoch_order(self, epoch):
-        """Item indices of one epoch, in batch order (with ``drop_last`` the trailing partial batch is dropped)."""
+        """Item indices of one epoch on this rank, in batch order (with ``drop_last`` the trailing partial batch is dropped).  The
+        global order is the same on every rank; it is cut into global batches of ``batch_size``, the first ``len(self) * world_size``
+        of them are used and global batch k goes to rank ``k % world_size`` (module docstring, "Rank sharding")."""
         n = len(self.filenames)
         order = np.random.default_rng([self.seed, int(epoch)]).permutation(n) if self.shuffle else np.arange(n)
+        if self.world_size > 1:
+            B, W = self.batch_size, self.world_size
+            return [int(i) for k in range(self.rank, len(self) * W, W) for i in order[k * B:(k + 1) * B]]
         return [int(i) for i in order[:len(self) * self.batch_size if self.drop_last else n]]
 
     def item_draws(self, epoch, index):
@@ -469,6 +493,7 @@ class KITTIRAWBatches:
         epoch = self._epoch
         self._epoch += 1
         order = self.epoch_order(epoch)
+        self.served.append((epoch, order))
         B = self.batch_size
         chunks = [order[i * B:(i + 1) * B] for i in range(len(self))]
         if not chunks:

@@ -212,24 +212,37 @@ def benchmark_depth_png(disp_resized):
     return np.uint16(depth * 256)
 
 
-def split_off_splits_dir(argv, default="splits"):
-    """``--splits_dir X`` / ``--splits_dir=X`` is not one of the reference's options (tests/golden/options_surface.json pins that
-    surface): take it off the command line -> (splits_dir, the remaining arguments)."""
-    rest, splits_dir, i = [], default, 0
-    argv = list(argv)
+def split_off_flags(argv, valued, switches=()):
+    """Flags that are not among the reference's options (tests/golden/options_surface.json pins that surface) are taken off the
+    command line before ``MonodepthOptions`` parses the rest.  ``valued``: {name: default} of the flags ``--name X`` / ``--name=X``;
+    ``switches``: names of flags without a value.  Returns ({name: value - a string as typed, or the default -, switch: bool}, the
+    remaining arguments); a flag that is in neither list stays in the rest and fails in argparse as before."""
+    found = dict(valued)
+    found.update({name: False for name in switches})
+    rest, i, argv = [], 0, list(argv)
     while i < len(argv):
-        if argv[i] == "--splits_dir":
+        arg = argv[i]
+        name = arg[2:].split("=", 1)[0] if arg.startswith("--") else None
+        if name in valued and "=" in arg:
+            found[name] = arg.split("=", 1)[1]
+        elif name in valued:
             if i + 1 >= len(argv):
-                raise ValueError("--splits_dir needs a value")
-            splits_dir = argv[i + 1]
-            i += 2
-        elif argv[i].startswith("--splits_dir="):
-            splits_dir = argv[i].split("=", 1)[1]
+                raise ValueError("--%s needs a value" % name)
+            found[name] = argv[i + 1]
             i += 1
+        elif name in switches and "=" not in arg:
+            found[name] = True
         else:
-            rest.append(argv[i])
-            i += 1
-    return splits_dir, rest
+            rest.append(arg)
+        i += 1
+    return found, rest
+
+
+def split_off_splits_dir(argv, default="splits"):
+    """``--splits_dir X`` / ``--splits_dir=X`` taken off the command line (``split_off_flags``) -> (splits_dir, the remaining
+    arguments)."""
+    found, rest = split_off_flags(argv, {"splits_dir": default})
+    return found["splits_dir"], rest
 
 
 def _refuse_uncovered(opt):

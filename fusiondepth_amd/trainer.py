@@ -182,6 +182,10 @@ class Trainer:
         self.depth_metric_names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
         self.epoch, self.step, self.batch_idx = 0, 0, 0
         self.best = 10.0
+        # validation.ValGroundTruth of the validation loader's images, in its order: val_metrics then scores every image against its
+        # own map in one fused pass (see val_metrics).  None: depth_gt of the batches, one compute_depth_losses per batch.
+        self.val_gt = None
+        self.last_losses = None                # the loss dict of the latest train_step (device tensors)
         self.start_time = time.time()
         self.set_train()
         self.flat.zero_grad()
@@ -308,6 +312,7 @@ class Trainer:
         self._ensure_weight_plan()
         self.step += self.accumulate_step            # the reference counts batches (trainer.py:264), not optimiser steps
         self._last_io = (inputs, outputs)
+        self.last_losses = losses
         return losses
 
     def _forward_backward(self, batches, eager):
@@ -966,7 +971,19 @@ class Trainer:
             losses[metric] = losses.get(metric, 0.0) + v if accumulate else v
 
     def val_metrics(self, batches):
-        """trainer.py:390-409: mean monitoring metrics over an iterable of batches (depth only, eval-mode BN)."""
+        """trainer.py:390-409: mean monitoring metrics over an iterable of batches (depth only, eval-mode BN).
+
+        With ``self.val_gt`` set (a ``validation.ValGroundTruth``; ``python -m fusiondepth_amd.train`` sets it from the split's
+        ``gt_depths.npz``) the metrics are the reference's against the per-image ground truth of trainer.py:404-405, and nothing is
+        read back inside the loop: every batch's ``("depth", 0, 0)`` is copied into a preallocated ``[N_val, h, w]`` device buffer,
+        the scorer (``fd_val_scores``) runs once over all images, ONE download brings the ``[N_val, 9]`` rows and their float64 mean
+        is the result.  Image k of the loader is scored against map k.  At ``--eval_batch_size 1`` - the reference's default, and the
+        only value at which its ``gt_depths[batch_idx]`` indexing means anything - that mean over images IS the reference's mean over
+        batches; with a larger batch the images are still scored one by one against their own maps and averaged per image (the
+        reference would hold a whole batch against the map of index ``batch_idx``).
+        Data-parallel runs: rank 0 alone validates and saves, as before; the other ranks wait in the next gradient exchange."""
+        if self.val_gt is not None:
+            return self._val_metrics_fused(batches)
         self.set_eval()
         losses = {m: 0.0 for m in self.depth_metric_names}
         n = 0
@@ -980,6 +997,30 @@ class Trainer:
             losses[m] /= max(n, 1)
         self.set_train()
         return losses
+
+    def _val_metrics_fused(self, batches):
+        """``val_metrics`` with ``val_gt``: no ``.cpu()``, ``.item()``, ``float()`` or boolean indexing until the one download."""
+        gt = self.val_gt
+        self.set_eval()
+        at = 0
+        with torch.no_grad():
+            for inputs in batches:
+                outputs, _ = self.process_batch(inputs, val=True)
+                depth = outputs[("depth", 0, 0)]
+                B, shape = depth.shape[0], (len(gt),) + tuple(depth.shape[2:])
+                if getattr(self, "_val_depths", None) is None or tuple(self._val_depths.shape) != shape:
+                    self._val_depths = torch.empty(shape, device=depth.device, dtype=torch.float32)
+                if at + B > len(gt):
+                    raise ValueError("Trainer.val_metrics: the loader yields more images than val_gt has maps (%d)" % len(gt))
+                self._val_depths[at:at + B].copy_(depth[:, 0])
+                at += B
+            if at != len(gt):
+                raise ValueError("Trainer.val_metrics: the loader yielded %d images for the %d maps of val_gt" % (at, len(gt)))
+            rows = gt.score(self._val_depths).cpu().numpy()          # the one download
+        self.last_val_rows = rows                                    # [N_val, 9]: the seven metrics, ratio, count per image
+        mean = rows[:, :7].mean(0)
+        self.set_train()
+        return {m: mean[i] for i, m in enumerate(self.depth_metric_names)}
 
     def val(self, batches, save_best=True):
         """trainer.py:390-423: validation metrics + best-checkpoint bookkeeping - a new best de/abs_rel is remembered and

@@ -45,7 +45,8 @@ extern "C" {
  *    Added later WITHOUT raising the number: the KITTI 3-D detection depth export (fd_depth_export + struct fd_export_desc,
  *    fd_depth_quantize_u16).  Nothing removed, no signature changed: a client built against 8 runs unchanged, and one that wants the
  *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8.
- *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd). */
+ *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd).
+ *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -827,6 +828,29 @@ long fd_eigen_scores_ws_bytes(int N, int max_rows, long list_cap);
 int fd_eigen_scores(const float* disp, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
                     int max_rows, long list_cap, float gt_lo, float gt_hi, float pred_scale, int median_scaling, float lo, float hi,
                     double* out /*[N][9]*/, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ training-time scoring ------
+ * compute_depth_losses (trainer.py:598-630) + compute_depth_errors (layers.py:284-302) per image, for N images whose ground-truth maps
+ * differ in size, in ONE call of 6 launches, whatever N is (csrc/val_scores.hip; the kernels are fd_eigen_scores' under another
+ * compile-time rule, csrc/score_lists.h).  The arguments are fd_eigen_scores':
+ *   depth    [M][h][w] predicted DEPTHS (outputs[("depth", 0, 0)]);  packed, desc, N, max_rows, list_cap, ws as above.
+ *            The mask of image n is  gt > 0  inside rows [y0, y1), columns [x0, x1) (the caller passes the Garg crop 153:371, 44:1197
+ *            clipped to the plane, as slicing clips it).  A descriptor whose plane leaves `packed`, whose window leaves the plane or
+ *            whose `pred` is not in [0, M) gives a NaN row with count -1; nothing outside the buffers is read.
+ * At every selected pixel, and only there: ATen's CPU bilinear rule with align_corners=False resamples depth[pred] to H x W - the
+ * arithmetic of fd_resize_bilinear_batch: scale = (float)n_in / (float)n_out, src = fmaf(scale, d + 0.5f, -0.5f) clamped at 0, the
+ * blend width first, top = fmaf(hx, a, lx * b), out = fmaf(hy, top, ly * bot) - then p = p < lo ? lo : p > hi ? hi : p (a NaN stays).
+ * The (gt, p) pairs are compacted in row-major order.  The medians are torch's: the LOWER order statistic, rank (n - 1) / 2, NaN
+ * when the list holds one.  ratio = median(gt) / median(p) (IEEE float32 division), p = p * ratio, the clamp again, then the terms of
+ * compute_depth_errors in float32, one rounding per operation (IEEE divisions for gt / p and p / gt; 1.25, 1.5625 and 1.953125 are
+ * exact); the log term is (float)(log((double)gt) - log((double)p)) squared in float32, as in fd_eigen_scores and for its reason.
+ * The sums run in float64 over a fixed grid of partials, added in index order: no float atomics, bitwise reproducible.
+ *   out[n] = { abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio, count } as float64; an empty selection gives NaN metrics and
+ *   count 0, a NaN prediction what torch gives (NaN for the first four and the ratio, a1-a3 = 0).
+ *   ws: fd_val_scores_ws_bytes(N, max_rows, list_cap) bytes, 8-byte aligned.  N <= 4096.  packed, desc, out 8-byte aligned. */
+long fd_val_scores_ws_bytes(int N, int max_rows, long list_cap);
+int fd_val_scores(const float* depth, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
+                  int max_rows, long list_cap, float lo, float hi, double* out /*[N][9]*/, void* ws, void* stream);
 
 /* ------------------------------------------------------------------ detection depth export -----
  * The dense part of export_detection.py:317-392 for N maps of different sizes in ONE launch (csrc/detection.hip): the whole predicted

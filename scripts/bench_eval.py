@@ -4,6 +4,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
 
     python scripts/bench_eval.py [--reps 10] [--out profiles/eigen_eval_time.log]
     python scripts/bench_eval.py --step detection [--reps 10] [--out profiles/detection_export_time.log]
+    python scripts/bench_eval.py --step val [--reps 5] [--out profiles/val_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -15,10 +16,18 @@ around a synchronise.  The call's traffic bound: the ground truth inside the win
 ``FD.resize_linear_cv`` per image, the reciprocal and two multiplies in torch, ``.cpu()``, ``(x * 256).astype(np.uint16)``.  Both on the
 same box in the same run, alternating, after the two were compared bit for bit.  Per N: the library call alone between device events
 (uint16 output only, as the script calls it) with its traffic bound - the bytes written plus the source read once, at 6.3 TB/s -, the
-recipe's device part between events, and both end to end (uploads of descriptors and ratios, the download) as wall time."""
+recipe's device part between events, and both end to end (uploads of descriptors and ratios, the download) as wall time.
+
+``--step val``: one in-training validation, ``Trainer.val`` (ResNet-18 at 192x640, batch 1, eval mode), over 64 and over 697 synthetic
+batches (``synthetic.make_batch``; 8 distinct ones, cycled) with 375x1242 ground truth of which 5 % is valid: the fused route
+(``trainer.val_gt`` = a resident ``validation.ValGroundTruth``: depths gathered on the device, ``fd_val_scores`` once per 64 images, one
+download) against the route without it (``compute_depth_losses`` per batch: a boolean selection, two ``torch.median`` sorts, seven
+``.cpu()`` copies), alternating in one run, wall time around a synchronise; median (min, max) of the rounds after one warm-up round.  Also
+the scorer alone between device events with everything resident.  No loader runs here: the batches are in memory."""
 import argparse
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -168,16 +177,65 @@ def detection_step(a):
     return lines
 
 
+def val_step(a):
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.options import MonodepthOptions
+    from fusiondepth_amd.trainer import Trainer
+    from fusiondepth_amd.validation import ValGroundTruth
+    rng = np.random.RandomState(5)
+    torch.manual_seed(1)
+    opt = MonodepthOptions().parse(["--num_layers", "18", "--weights_init", "scratch", "--log_dir", tempfile.mkdtemp(prefix="fd_bench_val_")])
+    tr = Trainer(opt, verbose=False)
+    distinct = []
+    for k in range(8):
+        b = synthetic.make_batch(1, 192, 640, frame_ids=(0,), seed=40 + k)
+        gt = rng.uniform(1.5, 80.0, (375, 1242)).astype(np.float32)
+        gt[rng.rand(375, 1242) > 0.05] = 0.0
+        b["depth_gt"] = torch.from_numpy(gt).cuda()[None, None]
+        distinct.append((b, gt))
+    lines = ["In-training validation, Trainer.val (ResNet-18 at 192x640, batch 1, eval mode) over N in-memory synthetic batches, 375x1242 "
+             "ground truth with 5 % valid pixels; fused route (val_gt) and compute_depth_losses route alternating in one run, wall time; "
+             "median (min, max) of the rounds after one warm-up round"]
+    for n in (64, 697):
+        reps = a.reps if n <= 64 else max(2, a.reps // 2)
+        batches = [distinct[i % 8][0] for i in range(n)]
+        vg = ValGroundTruth([distinct[i % 8][1] for i in range(n)])
+
+        def fused():
+            tr.val_gt = vg
+            return tr.val(batches, save_best=False)
+
+        def plain():
+            tr.val_gt = None
+            return tr.val(batches, save_best=False)
+
+        f, p = fused(), plain()
+        worst = max(abs(float(f[m]) - float(p[m])) / abs(float(p[m])) for m in tr.depth_metric_names)
+        (t_f, t_p) = alternate([fused, plain], reps, _wall_ms)
+        depths = tr._val_depths
+        t_s = alternate([lambda: vg.score(depths)], reps, _event_ms)[0]
+        selected = int(vg.out[:, 8].sum().item())
+        lines.append("  N = %3d, %d rounds: fused %.1f ms (%.1f, %.1f) = %.3f ms / image; compute_depth_losses route %.1f ms (%.1f, %.1f) = %.3f ms "
+                     "/ image -> %.2fx (medians); the two routes' mean metrics differ by at most %.1e relative"
+                     % (n, reps, t_f[0], t_f[1], t_f[2], t_f[0] / n, t_p[0], t_p[1], t_p[2], t_p[0] / n, t_p[0] / t_f[0], worst))
+        lines.append("           fd_val_scores alone, resident ground truth (%.0f MB), %d call(s), %d selected pixels: %.3f ms (%.3f, %.3f) = "
+                     "%.1f us / image" % (vg.packed.numel() * 4 / 1e6, len(vg.chunks), selected, t_s[0], t_s[1], t_s[2], 1e3 * t_s[0] / n))
+        tr.val_gt = None
+        del vg
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val"), default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "eigen_eval_time.log" if a.step == "eigen" else "detection_export_time.log")
-    if a.step == "detection":
-        text = "\n".join(detection_step(a))
+        a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
+                                                "val": "val_time.log"}[a.step])
+    if a.step in ("detection", "val"):
+        text = "\n".join(detection_step(a) if a.step == "detection" else val_step(a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
