@@ -217,6 +217,8 @@ SIGNATURES = {
     "fd_eigen_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "p" "pp", "i"),
     "fd_val_scores_ws_bytes": ("iil", "l"),
     "fd_val_scores": ("piii" "pl" "pi" "il" "ff" "p" "pp", "i"),
+    "fd_completion_val_scores_ws_bytes": ("iil", "l"),
+    "fd_completion_val_scores": ("piii" "pl" "pi" "il" "fff" "p" "pp", "i"),
     "fd_depth_export": ("piii" "pi" "lii" "f" "ppp" "p", "i"),
     "fd_depth_quantize_u16": ("pplp", "i"),
 }

@@ -13,8 +13,10 @@ with its own hyper-parameters and LiDAR term; what differs from ``Trainer`` (ref
   * monitoring metrics (completor.py:728-762): ground truth valid where > 0.1, Garg crop only with
     ``--completion_eigen_crop``, errors computed on millimetres (x 1000);
   * validation (completor.py:390-426): mean metrics over the validation batches, best-RMSE bookkeeping that names the
-    checkpoint ``rms<N>``.
-The wandb / DataLoader shell (completor.py:131-146, 767-790) is out of scope like the trainer's.
+    checkpoint ``rms<N>``.  With ``val_scorer`` set the metrics come from ``fd_completion_val_scores`` with one download per
+    validation (``val_metrics``); ``Trainer.run_epoch`` logs ``val_losses``, the losses of ``val``'s ``(losses, saved)``.
+The DataLoader shell (completor.py:131-146) is ``python -m fusiondepth_amd.complete`` (complete.py); wandb (:767-790) is out of scope
+like the trainer's.
 """
 import numpy as np
 import torch
@@ -30,6 +32,7 @@ class Completor(Trainer):
         super().__init__(options, device=device, rank=rank, world_size=world_size, materialize_outputs=materialize_outputs,
                          verbose=verbose)
         self.best = 100000.0                                             # completor.py:186
+        self.val_scorer = None                                           # validation.CompletionValScorer: val_metrics' fused route
 
     # ---- configuration hooks of Trainer.__init__ ----------------------------------------------------
     def _derived_hparams(self, vram_gib):
@@ -77,6 +80,35 @@ class Completor(Trainer):
         for i, metric in enumerate(self.depth_metric_names):
             v = errs[i].detach().cpu().numpy()
             losses[metric] = losses.get(metric, 0.0) + v if accumulate else v
+
+    def val_metrics(self, batches):
+        """completor.py:390-409: mean monitoring metrics over an iterable of batches.
+
+        With ``self.val_scorer`` set (a ``validation.CompletionValScorer``; ``python -m fusiondepth_amd.complete`` sets it) nothing is
+        read back inside the loop: every batch's ``("depth", 0, 0)`` and ``depth_gt`` are copied device to device into the scorer's
+        staging pair, ``fd_completion_val_scores`` runs once per full chunk and once for the remainder, ONE download brings the
+        ``[N_val, 9]`` rows and their float64 mean is the result.  At ``--eval_batch_size 1`` - the reference's default - that mean
+        over images IS the reference's mean over batches; with a larger batch the images are still scored one by one and averaged per
+        image (the reference would form one mask and one pair of medians over the whole batch).
+        ``val_scorer = None`` (the default) is the per-batch ``compute_depth_losses`` route of ``Trainer.val_metrics``, unchanged."""
+        scorer = self.val_scorer
+        if scorer is None:
+            return super().val_metrics(batches)
+        self.set_eval()
+        scorer.begin()
+        with torch.no_grad():
+            for inputs in batches:
+                outputs, _ = self.process_batch(inputs, val=True)
+                scorer.add(outputs[("depth", 0, 0)], inputs["depth_gt"])
+            rows = scorer.finish().cpu().numpy()                     # the one download
+        self.last_val_rows = rows                                    # [N_val, 9]: the seven metrics, ratio, count per image
+        mean = rows[:, :7].mean(0)
+        self.set_train()
+        return {m: mean[i] for i, m in enumerate(self.depth_metric_names)}
+
+    def val_losses(self, batches):
+        """``Trainer.run_epoch`` logs the losses of ``val``, not the checkpoint folder beside them."""
+        return self.val(batches)[0]
 
     def val(self, batches, save_best=True):
         """completor.py:390-426: mean metrics over ``batches``; a new best de/rms is remembered and, below 1200 (mm), saved

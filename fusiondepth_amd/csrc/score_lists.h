@@ -1,5 +1,6 @@
-// The device code the two per-image depth scorers share: fd_eigen_scores (eigen_eval.hip: the rules of evaluate_depth.py) and
-// fd_val_scores (val_scores.hip: the rules of the trainer's compute_depth_losses).  Both select ground-truth pixels inside a window,
+// The device code the three per-image depth scorers share: fd_eigen_scores (eigen_eval.hip: the rules of evaluate_depth.py),
+// fd_val_scores (val_scores.hip: the rules of the trainer's compute_depth_losses) and fd_completion_val_scores (completion_val.hip: the
+// rules of the Completor's compute_depth_losses).  All select ground-truth pixels inside a window,
 // evaluate a bilinear resample of the prediction at the selected pixels only, compact the (gt, pred) pairs in row-major order, take
 // a median of each list by radix select and sum the float32 terms of the seven metrics in float64 over a fixed grid of partials.
 // What differs is a compile-time RULE:
@@ -7,6 +8,8 @@
 //               float32 mean of the two middle values).
 //   RULE_VAL    ATen's CPU bilinear rule (align_corners=False, aten_resize.h) on the DEPTH, clamped to [lo, hi] before the median;
 //               torch's median (the lower middle element, rank (n - 1) / 2).
+//   RULE_COMPLETION  RULE_VAL's resample and medians; after the second clamp both sides are scaled to millimetres, g' = g * 1000.0f
+//               and p' = p * 1000.0f (one float32 rounding each), and the seven terms are formed on g' and p' (completor.py:762).
 // Launches, whatever N is:
 //   1 k_score_rows<RULE, false>  one wave per window row of every image: how many pixels of the row are selected.
 //   2 k_score_scan               one workgroup per image: where its compact lists start (the window areas of the images before it)
@@ -17,7 +20,7 @@
 //   4 k_score_median<RULE>       one workgroup per (image, list): completion.hip's radix select (4 passes of 8 bits, LDS histograms
 //                                with integer atomics; RULE_EIGEN adds a fifth pass for the upper middle element of an even count)
 //                                over the compact list, a few times 10^4 values, not over the plane.
-//   5 k_score_errors             ratio = median(gt) / median(pred) in float32, p = clamp(pred * ratio, lo, hi) and the terms of
+//   5 k_score_errors<RULE>       ratio = median(gt) / median(pred) in float32, p = clamp(pred * ratio, lo, hi) and the terms of
 //                                compute_errors / compute_depth_errors in float32, float64 sums: a fixed grid of workgroups per
 //                                image, a fixed shuffle tree inside each, partials to the workspace.
 //   6 k_score_finish             sums an image's partials in index order -> out[n][9].  No float atomics anywhere: run-to-run
@@ -34,7 +37,7 @@
 
 namespace {
 
-enum ScoreRule { RULE_EIGEN = 0, RULE_VAL = 1 };
+enum ScoreRule { RULE_EIGEN = 0, RULE_VAL = 1, RULE_COMPLETION = 2 };
 
 constexpr int ROW_WAVES = 4;                                      // window rows per workgroup of the count / compact kernels
 constexpr int ERR_THREADS = 256;
@@ -254,6 +257,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+template <int RULE>
 __global__ void __launch_bounds__(ERR_THREADS) k_score_errors(Args a) {
     __shared__ double red[ERR_THREADS / 64][ERR_VALUES];
     const int g = blockIdx.x, n_img = blockIdx.y, t = threadIdx.x;
@@ -265,11 +269,15 @@ __global__ void __launch_bounds__(ERR_THREADS) k_score_errors(Args a) {
     const float ratio = scaled ? a.med[2 * n_img] / a.med[2 * n_img + 1] : 1.0f;
     double acc[ERR_VALUES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = g * ERR_THREADS + t; i < n; i += ERR_GROUPS * ERR_THREADS) {
-        const float gv = gl[i];
+        float gv = gl[i];
         float p = pl[i];
         if (scaled) p = p * ratio;                                // pred_depth *= ratio
         p = p < a.lo ? a.lo : p;                                  // pred_depth[pred_depth < MIN_DEPTH] = MIN_DEPTH: a NaN stays
         p = p > a.hi ? a.hi : p;
+        if (RULE == RULE_COMPLETION) {                            // compute_depth_errors(gt * 1000.0, pred * 1000.0): millimetres
+            gv = gv * 1000.0f;
+            p = p * 1000.0f;
+        }
         const float q0 = gv / p, q1 = p / gv;
         float th = q0 > q1 ? q0 : q1;                             // np.maximum / torch.max: a NaN on either side gives NaN
         if (q0 != q0 || q1 != q1) th = __builtin_nanf("");
@@ -356,7 +364,7 @@ inline int launch_scores(const Args& a, hipStream_t st, const char* const names[
         hipLaunchKernelGGL((k_score_median<RULE>), dim3(2, a.N), dim3(1024), 0, st, a);
         FD_LAUNCH_CHECK(names[3]);
     }
-    hipLaunchKernelGGL(k_score_errors, dim3(ERR_GROUPS, a.N), dim3(ERR_THREADS), 0, st, a);
+    hipLaunchKernelGGL((k_score_errors<RULE>), dim3(ERR_GROUPS, a.N), dim3(ERR_THREADS), 0, st, a);
     FD_LAUNCH_CHECK(names[4]);
     hipLaunchKernelGGL(k_score_finish, dim3(fd_cdiv(a.N, 64)), dim3(64), 0, st, a);
     FD_LAUNCH_CHECK(names[5]);

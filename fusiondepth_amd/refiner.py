@@ -315,7 +315,7 @@ class Refiner(Trainer):
                     self.compute_depth_losses(inputs, self._last_outputs, losses)
                 self.log("train", {k: v for k, v in losses.items() if torch.is_tensor(v) or np.ndim(v) == 0})
                 if getattr(self, "val_loader", None) is not None:
-                    self.log("val", self.val(self.val_loader))
+                    self.log("val", self.val_losses(self.val_loader))
                     self.set_train()
         self.lr_scheduler_step()
 
@@ -340,4 +340,5 @@ class Refiner(Trainer):
         self.step += 1
         self.batch_idx += 1
         self._last_outputs = outputs
+        self.last_losses = losses
         return losses

@@ -109,10 +109,12 @@ def param_checksum(trainer):
     return [float(flat64.sum()), float(flat64.abs().sum())]
 
 
-def write_summary(trainer, train_loader, rank):
-    """``<log_path>/train_summary.rank<k>.json``: what this rank did."""
+def write_summary(trainer, train_loader, rank, loss_scale=None):
+    """``<log_path>/train_summary.rank<k>.json``: what this rank did.  ``loss_scale``: what turns the latest step's ``loss`` into the
+    value the log prints (default ``1 / accumulate_step``: ``Trainer.train_step`` sums over its stacked micro-batches)."""
     last = trainer.last_losses
-    loss = float(last["loss"]) / trainer.accumulate_step if last is not None else None
+    scale = 1.0 / trainer.accumulate_step if loss_scale is None else loss_scale
+    loss = float(last["loss"]) * scale if last is not None else None
     res = {"rank": rank, "world_size": trainer.world_size, "steps": trainer.step, "epochs": len(train_loader.served),
            "batches_per_epoch": len(train_loader), "batch_size": train_loader.batch_size, "last_loss": loss,
            "param_checksum": param_checksum(trainer), "best": float(trainer.best),

@@ -424,9 +424,13 @@ class Trainer:
                     self.compute_depth_losses(last_in, last_out, losses)
                 self.log("train", losses)
                 if getattr(self, "val_loader", None) is not None:
-                    self.log("val", self.val(self.val_loader))
+                    self.log("val", self.val_losses(self.val_loader))
                     self.set_train()
         self.lr_scheduler_step()
+
+    def val_losses(self, batches):
+        """What ``run_epoch`` logs under "val": the losses of ``val``.  (``Completor.val`` returns more than the losses.)"""
+        return self.val(batches)
 
     def log_time(self, batch_idx, duration, loss):
         """trainer.py:632-642."""

@@ -46,7 +46,8 @@ extern "C" {
  *    fd_depth_quantize_u16).  Nothing removed, no signature changed: a client built against 8 runs unchanged, and one that wants the
  *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8.
  *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd).
- *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc). */
+ *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc).
+ *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -851,6 +852,25 @@ int fd_eigen_scores(const float* disp, int M, int h, int w, const float* packed,
 long fd_val_scores_ws_bytes(int N, int max_rows, long list_cap);
 int fd_val_scores(const float* depth, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
                   int max_rows, long list_cap, float lo, float hi, double* out /*[N][9]*/, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ the Completor's training-time scoring
+ * compute_depth_losses (completor.py:728-762) + compute_depth_errors (layers.py:284-302) per image, in ONE call of 6 launches, whatever
+ * N is (csrc/completion_val.hip; fd_val_scores' kernels under a third compile-time rule, csrc/score_lists.h).  The arguments are
+ * fd_val_scores' plus gt_min; what differs from its rule:
+ *   the mask of image n is  gt > gt_min  inside rows [y0, y1), columns [x0, x1): a float32 comparison against a float32 (the caller
+ *   passes (float)0.1, as torch compares a float32 tensor with the Python scalar 0.1).  The caller passes the whole plane as the
+ *   window, or with --completion_eigen_crop 153:371, 44:1197 clipped to the plane as slicing clips it.
+ *   after  p = clamp(p * ratio, lo, hi)  both sides are scaled to millimetres, g' = g * 1000.0f and p' = p * 1000.0f, one float32
+ *   rounding each, and the seven terms of compute_depth_errors are formed on g' and p' as fd_val_scores forms them on g and p.
+ * Everything else is fd_val_scores': ATen's CPU bilinear rule on depth[pred] at the selected pixels only (equal sizes included: the
+ * rule is then the identity), the clamp before torch's LOWER medians, ratio = median(gt) / median(p) on the UNSCALED lists, float64 sums
+ * over the fixed grid of partials added in index order (no float atomics, bitwise reproducible), the bad-descriptor row (NaN, count -1).
+ *   out[n] = { abs_rel, sq_rel, rmse [mm], rmse_log, a1, a2, a3, ratio, count } as float64.
+ *   ws: fd_completion_val_scores_ws_bytes(N, max_rows, list_cap) bytes, 8-byte aligned.  N <= 4096.  packed, desc, out 8-byte aligned. */
+long fd_completion_val_scores_ws_bytes(int N, int max_rows, long list_cap);
+int fd_completion_val_scores(const float* depth, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc,
+                             int N, int max_rows, long list_cap, float gt_min, float lo, float hi, double* out /*[N][9]*/, void* ws,
+                             void* stream);
 
 /* ------------------------------------------------------------------ detection depth export -----
  * The dense part of export_detection.py:317-392 for N maps of different sizes in ONE launch (csrc/detection.hip): the whole predicted

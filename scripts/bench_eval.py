@@ -5,6 +5,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py [--reps 10] [--out profiles/eigen_eval_time.log]
     python scripts/bench_eval.py --step detection [--reps 10] [--out profiles/detection_export_time.log]
     python scripts/bench_eval.py --step val [--reps 5] [--out profiles/val_time.log]
+    python scripts/bench_eval.py --step completion_val [--reps 5] [--out profiles/completion_val_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -23,7 +24,12 @@ batches (``synthetic.make_batch``; 8 distinct ones, cycled) with 375x1242 ground
 (``trainer.val_gt`` = a resident ``validation.ValGroundTruth``: depths gathered on the device, ``fd_val_scores`` once per 64 images, one
 download) against the route without it (``compute_depth_losses`` per batch: a boolean selection, two ``torch.median`` sorts, seven
 ``.cpu()`` copies), alternating in one run, wall time around a synchronise; median (min, max) of the rounds after one warm-up round.  Also
-the scorer alone between device events with everything resident.  No loader runs here: the batches are in memory."""
+the scorer alone between device events with everything resident.  No loader runs here: the batches are in memory.
+
+``--step completion_val``: the same for ``Completor.val`` (ResNet-18 at 352x1216, batch 1) over 64 and over 1000 synthetic batches with
+352x1216 ground truth of which 15 % is valid: the fused route (``completor.val_scorer`` = a ``validation.CompletionValScorer``:
+``fd_completion_val_scores`` once per 64 images, one download) against ``Completor.compute_depth_losses`` per batch, alternating; and the
+scorer alone between device events for 1 and for 64 images."""
 import argparse
 import os
 import sys
@@ -225,17 +231,81 @@ def val_step(a):
     return lines
 
 
+def completion_val_step(a):
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.completor import Completor
+    from fusiondepth_amd.options import MonodepthOptions
+    from fusiondepth_amd.validation import CompletionValScorer
+    H, W = 352, 1216
+    rng = np.random.RandomState(5)
+    torch.manual_seed(1)
+    opt = MonodepthOptions().parse(["--num_layers", "18", "--completion_num_layers", "18", "--completion_pose_num_layers", "18",
+                                    "--weights_init", "scratch", "--log_dir", tempfile.mkdtemp(prefix="fd_bench_cval_")])
+    cp = Completor(opt, verbose=False)
+    distinct = []
+    for k in range(8):
+        b = synthetic.make_batch(1, H, W, frame_ids=(0,), seed=40 + k)
+        gt = rng.uniform(1.5, 80.0, (H, W)).astype(np.float32)
+        gt[rng.rand(H, W) > 0.15] = 0.0
+        b["depth_gt"] = torch.from_numpy(gt).cuda()[None, None]
+        distinct.append(b)
+    lines = ["In-training validation, Completor.val (ResNet-18 at %dx%d, batch 1, eval mode) over N in-memory synthetic batches, ground "
+             "truth with 15 %% valid pixels; fused route (val_scorer) and compute_depth_losses route alternating in one run, wall time; "
+             "median (min, max) of the rounds after one warm-up round" % (H, W)]
+    for n in (64, 1000):
+        reps = a.reps if n <= 64 else max(3, a.reps // 3)
+        batches = [distinct[i % 8] for i in range(n)]
+        scorer = CompletionValScorer(n, (H, W), (H, W))
+
+        def fused():
+            cp.val_scorer = scorer
+            return cp.val(batches, save_best=False)[0]
+
+        def plain():
+            cp.val_scorer = None
+            return cp.val(batches, save_best=False)[0]
+
+        f, p = fused(), plain()
+        worst = max(abs(float(f[m]) - float(p[m])) / abs(float(p[m])) for m in cp.depth_metric_names)
+        (t_f, t_p) = alternate([fused, plain], reps, _wall_ms)
+        spread = max(t_f[2] - t_f[1], t_p[2] - t_p[1])
+        lines.append("  N = %4d, %d rounds: fused %.1f ms (%.1f, %.1f) = %.3f ms / image; compute_depth_losses route %.1f ms (%.1f, %.1f) = %.3f ms "
+                     "/ image -> %.2fx (medians); difference of the medians %.1f ms against the larger spread %.1f ms; the two routes' mean "
+                     "metrics differ by at most %.1e relative"
+                     % (n, reps, t_f[0], t_f[1], t_f[2], t_f[0] / n, t_p[0], t_p[1], t_p[2], t_p[0] / n, t_p[0] / t_f[0], t_p[0] - t_f[0], spread,
+                        worst))
+        cp.val_scorer = None
+        del scorer
+    for n in (1, 64):                                            # the scorer alone, everything resident: one library call
+        scorer = CompletionValScorer(n, (H, W), (H, W))
+        depth = torch.from_numpy(rng.uniform(1.0, 80.0, (n, 1, H, W)).astype(np.float32)).cuda()
+        gts = torch.cat([distinct[i % 8]["depth_gt"] for i in range(n)])
+        scorer.begin()
+        scorer.add(depth, gts)
+        scorer.finish()
+        selected = int(scorer.out[:, 8].sum().item())
+
+        def call_only():
+            scorer.filled, scorer.seen = n, n
+            scorer._flush()
+
+        t_s = alternate([call_only], a.reps, _event_ms)[0]
+        lines.append("  fd_completion_val_scores alone, %d image(s) resident, 1 call, %d selected pixels: %.3f ms (%.3f, %.3f) = %.1f us / image"
+                     % (n, selected, t_s[0], t_s[1], t_s[2], 1e3 * t_s[0] / n))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val"), default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
-                                                "val": "val_time.log"}[a.step])
-    if a.step in ("detection", "val"):
-        text = "\n".join(detection_step(a) if a.step == "detection" else val_step(a))
+                                                "val": "val_time.log", "completion_val": "completion_val_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val"):
+        text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
