@@ -215,6 +215,9 @@ SIGNATURES = {
     "fd_completion_errors": ("ppp" "iii" "ffff" "p" "pp", "i"),
     "fd_eigen_scores_ws_bytes": ("iil", "l"),
     "fd_eigen_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "p" "pp", "i"),
+    "fd_eigen_class_scores_ws_bytes": ("iili", "l"),
+    "fd_eigen_class_scores": ("piii" "pl" "pi" "il" "fff" "i" "ff" "pi" "pp" "pp", "i"),
+    "fd_class_errors": ("ppp" "li" "ff" "p" "p", "i"),
     "fd_val_scores_ws_bytes": ("iil", "l"),
     "fd_val_scores": ("piii" "pl" "pi" "il" "ff" "p" "pp", "i"),
     "fd_completion_val_scores_ws_bytes": ("iil", "l"),

@@ -27,6 +27,10 @@
 //                                identical.
 // Every float32 step is one rounding: contraction is off here and in the including files; the fused multiply-adds of ATen's rule
 // are explicit fmaf calls.
+// fd_eigen_class_scores (eigen_class.hip) adds two things to the six launches.  k_score_rows<RULE, true, true> also writes the label of
+// each selected pixel to a uint8 list at the pair's index (the three scorers above leave the flag off: their kernels are unchanged).
+// k_class_errors, one workgroup per (class, image), then walks the image's compact list, keeps the pairs whose label is its class and
+// sums score_terms - the per-pixel arithmetic it shares with k_score_errors - through class_reduce.
 #pragma once
 #include "../../include/fdhip.h"
 #include "fd_common.h"
@@ -57,6 +61,11 @@ struct Args {
     double* part;                                                 // [N][ERR_GROUPS][ERR_VALUES]
     float* gt_list; float* pred_list;                             // [list_cap] each
     double* out;
+    // fd_eigen_class_scores alone (k_score_rows<.., true, true> and k_class_errors; nothing else reads them)
+    const unsigned char* labels = nullptr;                        // label plane of image n at BYTE desc[n].offset, H x W, row-major
+    unsigned char* label_list = nullptr;                          // [list_cap]: the label of the pair at the same index
+    int K = 0;                                                    // classes; a label >= K belongs to none
+    double* class_out = nullptr;                                  // [N][K][CLASS_VALUES]
 };
 
 __device__ __forceinline__ bool desc_ok(const fd_eigen_desc& d, const Args& a) {
@@ -70,8 +79,9 @@ __device__ __forceinline__ long window_area(const fd_eigen_desc& d, const Args& 
 __device__ __forceinline__ bool selected(float g, float gt_lo, float gt_hi, bool no_hi) { return g > gt_lo && (no_hi || g < gt_hi); }
 
 // ---------------------------------------------------------------------------------------------- 1, 3: count and compact
-template <int RULE, bool WRITE>
+template <int RULE, bool WRITE, bool LABELS = false>
 __global__ void __launch_bounds__(ROW_WAVES * 64) k_score_rows(Args a) {
+    static_assert(WRITE || !LABELS, "labels are written beside the pairs");
     const int n = blockIdx.y, lane = threadIdx.x & 63;
     const int r = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);    // wave-uniform
     const fd_eigen_desc d = a.desc[n];
@@ -83,6 +93,7 @@ __global__ void __launch_bounds__(ROW_WAVES * 64) k_score_rows(Args a) {
     const unsigned long long below = (1ull << lane) - 1ull;
     long at = 0;
     const float* dp = nullptr;
+    const unsigned char* lrow = nullptr;                          // byte loads: a plane starts at any address
     int ya = 0, yb = 0;
     float b0 = 0.f, b1 = 0.f;
     double sx = 0.0;                                              // RULE_EIGEN: OpenCV's scale, a double
@@ -90,6 +101,7 @@ __global__ void __launch_bounds__(ROW_WAVES * 64) k_score_rows(Args a) {
     if (WRITE) {
         at = a.info[n].base + a.rows[(long)n * a.max_rows + r];
         dp = a.disp + (long)d.pred * a.h * a.w;
+        if (LABELS) lrow = a.labels + d.offset + (long)y * d.W;
         if (RULE == RULE_EIGEN) {
             cv_linear_coeff(y, (double)a.h / (double)d.H, a.h, ya, yb, b0, b1);
             sx = (double)a.w / (double)d.W;
@@ -125,6 +137,7 @@ __global__ void __launch_bounds__(ROW_WAVES * 64) k_score_rows(Args a) {
             const long i = at + count + __popcll(m & below);
             a.gt_list[i] = g;
             a.pred_list[i] = depth;
+            if (LABELS) a.label_list[i] = lrow[x];
         }
         count += __popcll(m);
     }
@@ -257,6 +270,32 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// The terms of one (gt, pred) pair, added to acc: the per-pixel arithmetic of k_score_errors and k_class_errors.
+template <int RULE>
+__device__ __forceinline__ void score_terms(float gv, float p, bool scaled, float ratio, float lo, float hi, double (&acc)[ERR_VALUES]) {
+    if (scaled) p = p * ratio;                                    // pred_depth *= ratio
+    p = p < lo ? lo : p;                                          // pred_depth[pred_depth < MIN_DEPTH] = MIN_DEPTH: a NaN stays
+    p = p > hi ? hi : p;
+    if (RULE == RULE_COMPLETION) {                                // compute_depth_errors(gt * 1000.0, pred * 1000.0): millimetres
+        gv = gv * 1000.0f;
+        p = p * 1000.0f;
+    }
+    const float q0 = gv / p, q1 = p / gv;
+    float th = q0 > q1 ? q0 : q1;                                 // np.maximum / torch.max: a NaN on either side gives NaN
+    if (q0 != q0 || q1 != q1) th = __builtin_nanf("");
+    const float df = gv - p;
+    const float sq = df * df;
+    // the logarithms in float64, their difference rounded once; numpy's float32 log is not correctly rounded (fdhip.h)
+    const float dl = (float)(log((double)gv) - log((double)p));
+    acc[0] += (double)(__builtin_fabsf(df) / gv);
+    acc[1] += (double)(sq / gv);
+    acc[2] += (double)sq;
+    acc[3] += (double)(dl * dl);
+    acc[4] += th < 1.25f ? 1.0 : 0.0;
+    acc[5] += th < 1.5625f ? 1.0 : 0.0;                           // 1.25 ** 2 and 1.25 ** 3 are exact in float32
+    acc[6] += th < 1.953125f ? 1.0 : 0.0;
+}
+
 template <int RULE>
 __global__ void __launch_bounds__(ERR_THREADS) k_score_errors(Args a) {
     __shared__ double red[ERR_THREADS / 64][ERR_VALUES];
@@ -268,31 +307,7 @@ __global__ void __launch_bounds__(ERR_THREADS) k_score_errors(Args a) {
     const bool scaled = a.median_scaling != 0;
     const float ratio = scaled ? a.med[2 * n_img] / a.med[2 * n_img + 1] : 1.0f;
     double acc[ERR_VALUES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = g * ERR_THREADS + t; i < n; i += ERR_GROUPS * ERR_THREADS) {
-        float gv = gl[i];
-        float p = pl[i];
-        if (scaled) p = p * ratio;                                // pred_depth *= ratio
-        p = p < a.lo ? a.lo : p;                                  // pred_depth[pred_depth < MIN_DEPTH] = MIN_DEPTH: a NaN stays
-        p = p > a.hi ? a.hi : p;
-        if (RULE == RULE_COMPLETION) {                            // compute_depth_errors(gt * 1000.0, pred * 1000.0): millimetres
-            gv = gv * 1000.0f;
-            p = p * 1000.0f;
-        }
-        const float q0 = gv / p, q1 = p / gv;
-        float th = q0 > q1 ? q0 : q1;                             // np.maximum / torch.max: a NaN on either side gives NaN
-        if (q0 != q0 || q1 != q1) th = __builtin_nanf("");
-        const float df = gv - p;
-        const float sq = df * df;
-        // the logarithms in float64, their difference rounded once; numpy's float32 log is not correctly rounded (fdhip.h)
-        const float dl = (float)(log((double)gv) - log((double)p));
-        acc[0] += (double)(__builtin_fabsf(df) / gv);
-        acc[1] += (double)(sq / gv);
-        acc[2] += (double)sq;
-        acc[3] += (double)(dl * dl);
-        acc[4] += th < 1.25f ? 1.0 : 0.0;
-        acc[5] += th < 1.5625f ? 1.0 : 0.0;                       // 1.25 ** 2 and 1.25 ** 3 are exact in float32
-        acc[6] += th < 1.953125f ? 1.0 : 0.0;
-    }
+    for (int i = g * ERR_THREADS + t; i < n; i += ERR_GROUPS * ERR_THREADS) score_terms<RULE>(gl[i], pl[i], scaled, ratio, a.lo, a.hi, acc);
 #pragma unroll
     for (int v = 0; v < ERR_VALUES; ++v) {
         const double s = wave_sum_f64(acc[v]);
@@ -319,6 +334,90 @@ __global__ void k_score_finish(Args a) {
     o[4] = s[4] / n; o[5] = s[5] / n; o[6] = s[6] / n;
     o[7] = a.median_scaling ? (double)(a.med[2 * i] / a.med[2 * i + 1]) : (double)__builtin_nanf("");
     o[8] = info.ok ? n : -1.0;
+}
+
+// ---------------------------------------------------------------------------------------------- 7: per-class errors
+constexpr int CLASS_THREADS = 256;                                // T: thread t takes pairs t, t + T, ...
+constexpr int CLASS_VALUES = 8;                                   // abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count
+constexpr int CLASS_AHEAD = 16;                                   // steps whose loads a thread issues together
+
+// One workgroup sums the pairs of gl / pl [0, n) whose label is c and writes o[0 .. 8).  Each thread adds its pairs in index order,
+// the lanes of a wave add through wave_sum_f64's tree, thread 0 .. 7 adds the waves in wave order: the result is a function of the
+// lists alone, by whichever entry point they arrive.  No pair of class c: eight zeros (the reference's np.zeros(7), count 0).
+template <int RULE>
+__device__ __forceinline__ void class_reduce(const float* gl, const float* pl, const unsigned char* ll, long n, int c, bool scaled,
+                                             float ratio, float lo, float hi, double* o) {
+    __shared__ double red[CLASS_THREADS / 64][CLASS_VALUES];
+    const int t = threadIdx.x;
+    double acc[ERR_VALUES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double cnt = 0.0;
+    // One label in K fits, so in a step some lane of a wave nearly always has a pair and a wave that took the steps one by one would
+    // pay for a memory round trip and for the terms (two float64 logarithms) in almost every step.  Instead the loads of CLASS_AHEAD
+    // steps are issued together - labels, and gt and pred whether or not the label fits: coalesced reads of lists that lie in the
+    // L2 - and then each thread takes ITS fitting pairs in index order, all lanes at once: a wave forms the terms as often as its
+    // busiest lane has pairs among these steps (2 or 3 times in 16), and every thread still adds pairs t, t + T, ... in that order.
+    for (long i = t; i < n; i += CLASS_AHEAD * CLASS_THREADS) {
+        float gv[CLASS_AHEAD], pv[CLASS_AHEAD];
+        unsigned fits = 0;
+#pragma unroll
+        for (int k = 0; k < CLASS_AHEAD; ++k) {
+            const long at = i + (long)k * CLASS_THREADS;
+            const bool in = at < n;
+            if (in && (int)ll[at] == c) fits |= 1u << k;
+            gv[k] = in ? gl[at] : 0.f;
+            pv[k] = in ? pl[at] : 0.f;
+        }
+        while (fits) {
+            const int k = __builtin_ctz(fits);
+            fits &= fits - 1;
+            float g = gv[0], p = pv[0];
+#pragma unroll
+            for (int j = 1; j < CLASS_AHEAD; ++j) {               // selects, not an indexed array: the values stay in registers
+                g = k == j ? gv[j] : g;
+                p = k == j ? pv[j] : p;
+            }
+            score_terms<RULE>(g, p, scaled, ratio, lo, hi, acc);
+            cnt += 1.0;
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < ERR_VALUES; ++v) {
+        const double s = wave_sum_f64(acc[v]);
+        if ((t & 63) == 0) red[t >> 6][v] = s;
+    }
+    const double s = wave_sum_f64(cnt);
+    if ((t & 63) == 0) red[t >> 6][ERR_VALUES] = s;
+    __syncthreads();
+    if (t < CLASS_VALUES) {
+        double v = 0.0, m = 0.0;                                  // m: the class's count, a sum of integers
+        for (int w = 0; w < CLASS_THREADS / 64; ++w) {
+            v += red[w][t];
+            m += red[w][ERR_VALUES];
+        }
+        if (t < ERR_VALUES) {
+            v = m > 0.0 ? v / m : 0.0;
+            if (t == 2 || t == 3) v = sqrt(v);
+        }
+        o[t] = v;
+    }
+}
+
+// blockIdx.x: class; blockIdx.y: image
+template <int RULE>
+__global__ void __launch_bounds__(CLASS_THREADS) k_class_errors(Args a) {
+    const int c = blockIdx.x, n_img = blockIdx.y;
+    const ImageInfo info = a.info[n_img];
+    const int n = info.ok ? info.count : 0;                       // a refused image: zero rows
+    const bool scaled = a.median_scaling != 0;
+    const float ratio = scaled ? a.med[2 * n_img] / a.med[2 * n_img + 1] : 1.0f;
+    class_reduce<RULE>(a.gt_list + info.base, a.pred_list + info.base, a.label_list + info.base, n, c, scaled, ratio, a.lo, a.hi,
+                       a.class_out + ((long)n_img * a.K + c) * CLASS_VALUES);
+}
+
+// The class kernel on lists that are already matched and scaled (fd_class_errors): pred is clamped, nothing else.
+__global__ void __launch_bounds__(CLASS_THREADS) k_class_errors_lists(const float* gt, const float* pred, const unsigned char* labels, long n,
+                                                                      float lo, float hi, double* class_out) {
+    class_reduce<RULE_EIGEN>(gt, pred, labels, n, blockIdx.x, false, 1.0f, lo, hi, class_out + (long)blockIdx.x * CLASS_VALUES);
 }
 
 // ---------------------------------------------------------------------------------------------- host side
@@ -350,15 +449,16 @@ inline void place(Args& a, void* ws) {
     a.rows = (int*)(base + l.rows); a.gt_list = (float*)(base + l.gt_list); a.pred_list = (float*)(base + l.pred_list);
 }
 
-// The launches of one call; `names` = the six texts FD_LAUNCH_CHECK reports (count, scan, compact, medians, errors, finish).
-template <int RULE>
-inline int launch_scores(const Args& a, hipStream_t st, const char* const names[6]) {
+// The launches of one call; `names` = the six texts FD_LAUNCH_CHECK reports (count, scan, compact, medians, errors, finish), and a
+// seventh (classes) with LABELS: the compact launch then writes the label list too, and the class kernel follows the finish.
+template <int RULE, bool LABELS = false>
+inline int launch_scores(const Args& a, hipStream_t st, const char* const* names) {
     const dim3 row_grid(a.max_rows > 0 ? fd_cdiv(a.max_rows, ROW_WAVES) : 1, a.N);
     hipLaunchKernelGGL((k_score_rows<RULE, false>), row_grid, dim3(ROW_WAVES * 64), 0, st, a);
     FD_LAUNCH_CHECK(names[0]);
     hipLaunchKernelGGL(k_score_scan, dim3(a.N), dim3(1024), 0, st, a);
     FD_LAUNCH_CHECK(names[1]);
-    hipLaunchKernelGGL((k_score_rows<RULE, true>), row_grid, dim3(ROW_WAVES * 64), 0, st, a);
+    hipLaunchKernelGGL((k_score_rows<RULE, true, LABELS>), row_grid, dim3(ROW_WAVES * 64), 0, st, a);
     FD_LAUNCH_CHECK(names[2]);
     if (a.median_scaling) {
         hipLaunchKernelGGL((k_score_median<RULE>), dim3(2, a.N), dim3(1024), 0, st, a);
@@ -368,6 +468,10 @@ inline int launch_scores(const Args& a, hipStream_t st, const char* const names[
     FD_LAUNCH_CHECK(names[4]);
     hipLaunchKernelGGL(k_score_finish, dim3(fd_cdiv(a.N, 64)), dim3(64), 0, st, a);
     FD_LAUNCH_CHECK(names[5]);
+    if (LABELS) {
+        hipLaunchKernelGGL((k_class_errors<RULE>), dim3(a.K, a.N), dim3(CLASS_THREADS), 0, st, a);
+        FD_LAUNCH_CHECK(names[6]);
+    }
     return 0;
 }
 

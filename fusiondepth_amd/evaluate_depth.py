@@ -9,8 +9,13 @@
   * ``pack_gt_depths`` / ``eigen_scores(pred_disps, gt_depths, ...)``  the same loop without GDC as one library call per chunk of
     images (fd_eigen_scores, csrc/eigen_eval.hip): the resize is evaluated at the selected ground-truth pixels only, numpy's medians
     come from a radix select over the compacted pairs, float32 terms, float64 sums in a fixed order (bitwise reproducible).
-  * ``evaluate(opt, splits_dir)`` / ``python -m fusiondepth_amd.evaluate_depth``: the script (:74-489), on ``Predictor`` (with
-    ``--refine_2d``: the stage-2 refine decoder) and ``KITTIRAWBatches``.
+  * ``pack_labels`` / ``eigen_class_scores(pred_disps, gt_depths, sem_masks, ...)`` / ``semantic_summary``: ``--per_semantic``
+    (:330-334, :451-467, :491-496), the metrics of every image per semantic class - 34 boolean selections and ``compute_errors`` calls
+    per image in the reference - from the same library call per chunk (fd_eigen_class_scores, csrc/eigen_class.hip): each selected
+    pixel's label rides beside its (gt, pred) pair, one workgroup per (class, image) sums its class over the compact list.  With
+    ``--eval_gdc`` the classes are scored per image from the dense map (``functional.class_errors``, fd_class_errors).
+  * ``evaluate(opt, splits_dir, semantic_dir, semantic_out)`` / ``python -m fusiondepth_amd.evaluate_depth``: the script (:74-496), on
+    ``Predictor`` (with ``--refine_2d``: the stage-2 refine decoder) and ``KITTIRAWBatches``.
 
 Deviations from the reference, on purpose
   * disparities are scored as float32.  ``--post_process`` yields float64 (numpy's promotion in ``batch_post_process_disparity``), which
@@ -20,9 +25,13 @@ Deviations from the reference, on purpose
   * the splits folder is an argument (``--splits_dir``, taken off the command line before ``MonodepthOptions`` parses the rest; default
     ``splits``) instead of a folder beside the script; ``--eval_gdc`` reads the calibration under ``--data_path`` instead of ``kitti_data/``,
     and the beam file is read only then (the reference loads it always and uses it only with ``--eval_gdc``).
+  * ``--per_semantic`` reads ``pred_mask{i}.png`` from ``--semantic_dir`` and writes ``<run_name>.npy`` and ``pixel_count.npy`` under
+    ``--semantic_out`` (default ``.``), both taken off the command line like ``--splits_dir``, instead of
+    ``../semantic-segmentation/kitti/results`` and the working directory; without ``--semantic_dir`` the flag is refused.  The
+    arrays have one column per image of the split, not the reference's fixed 697; ``--run_name`` unset names the file ``per_semantic.npy``.
   * ``--no_eval`` and ``--eval_split benchmark`` return ``None`` instead of ending the interpreter; the benchmark PNGs are written with
     PIL; no wandb run, no ``visualization/dates.npy``, no input statistics printout.
-  * not covered, refused with the reason: ``--visualize``, ``--per_semantic``, ``--save_sample``, ``--demo``, the odometry splits, a model
+  * not covered, refused with the reason: ``--visualize``, ``--per_semantic`` without ``--semantic_dir``, ``--save_sample``, ``--demo``, the odometry splits, a model
     without the beam encoder, ``--cat2end`` with ``--refine_2d`` (the reference's refine branch reads ``beam_features``, which ``--cat2end``
     never computes), ``--eval_gdc`` with ``--ext_disp_to_eval`` (the reference's ``dates`` are undefined there).
 No CPU fallback: tensors must live on the GPU.
@@ -40,6 +49,7 @@ MIN_DEPTH = 1e-3          # evaluate_depth.py:28-29
 MAX_DEPTH = 80
 STEREO_SCALE_FACTOR = 5.4 # :32
 METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+NUM_CLASSES = 34          # :331, :455 - the label ids of the segmentation masks
 # numpy mirror of ``fd_eigen_desc`` (40 bytes, as ``_lib.EigenDesc``)
 EIGEN_DESC = np.dtype([("offset", np.int64), ("H", np.int32), ("W", np.int32), ("pred", np.int32), ("y0", np.int32), ("y1", np.int32),
                        ("x0", np.int32), ("x1", np.int32), ("reserved", np.int32)])
@@ -83,14 +93,20 @@ def gdc_range(random_sample=-1, nbeams=4):
 
 
 def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False,
-                         eval_gdc=False, beam_depths=None, calibs=None, random_sample=-1, nbeams=4, on_depth=None):
+                         eval_gdc=False, beam_depths=None, calibs=None, random_sample=-1, nbeams=4, on_depth=None, sem_masks=None,
+                         num_classes=NUM_CLASSES):
     """evaluate_depth.py:344-478.  ``pred_disps``: [N,h,w] device tensor (or list); ``gt_depths``: list of [H_i,W_i] arrays /
     tensors (KITTI ground truth has per-drive sizes).  Returns (mean of the 7 metrics over the images, per-image scaling ratios).
     ``eval_gdc`` (--eval_gdc, evaluate_depth.py:387-405): after median scaling, correct each prediction with GDC against
     ``beam_depths[i]`` (the sparse LiDAR map at ground-truth size, 0 = no point) and ``calibs[i]`` (``kitti_utils.Calibration``),
     with the reference's settings and pitch range (``gdc_range(random_sample, nbeams)``).  ``on_depth``: an optional callback
     ``(i, depth)`` that sees image i's dense [H_i,W_i] device map after scaling and GDC, before the clamp (export_detection.py:388
-    saves it there); the default changes nothing."""
+    saves it there); the default changes nothing.  ``sem_masks`` (--per_semantic, :451-467): N [H_i,W_i] uint8 label maps; the
+    classes of every image are then scored on ``gt[mask]``, the clamped ``pred[mask]`` and ``sem[mask]`` (``FD.class_errors``) and
+    the result is ``(mean, ratios, class_metrics[N,K,7] float64, class_counts[N,K] int64)``."""
+    if sem_masks is not None and len(sem_masks) != len(gt_depths):
+        raise ValueError("evaluate_predictions: %d label masks for %d ground-truth maps" % (len(sem_masks), len(gt_depths)))
+    classes = []
     if eval_gdc:
         from .gdc import GDC
         if beam_depths is None or calibs is None:
@@ -126,6 +142,12 @@ def evaluate_predictions(pred_disps, gt_depths, eval_split="eigen", pred_depth_s
             on_depth(i, pred_depth)
         pred, g = torch.clamp(pred_depth[mask], MIN_DEPTH, MAX_DEPTH), gt[mask]
         errors.append(compute_errors(g, pred))
+        if sem_masks is not None:
+            sem = torch.from_numpy(_label_plane(sem_masks[i], i, gh, gw, "evaluate_predictions")).cuda()
+            classes.append(FD.class_errors(g, pred, sem[mask], num_classes))
+    if sem_masks is not None:
+        rows = torch.stack(classes).cpu().numpy() if classes else np.zeros((0, num_classes, 8))
+        return np.array(errors).mean(0), np.array(ratios), rows[:, :, :7].copy(), rows[:, :, 7].astype(np.int64)
     return np.array(errors).mean(0), np.array(ratios)
 
 
@@ -167,6 +189,21 @@ def pack_gt_depths(gt_depths, eval_split):
     return packed[:at] if at else packed[:0], desc
 
 
+def _upload_chunk(who, disp, gt_depths, eval_split):
+    """One chunk of ``eigen_scores`` / ``eigen_class_scores`` on its way to the device -> (disparities [n,h,w] on the device, the pinned
+    packed ground truth, its descriptors, both on the device, the tallest window, the sum of the window areas)."""
+    disp = disp if torch.is_tensor(disp) else torch.as_tensor(np.asarray(disp))
+    disp = FD.f32(disp).cuda()
+    if disp.dim() != 3:
+        raise ValueError("%s: pred_disps must be [N,h,w], got %s" % (who, tuple(disp.shape)))
+    packed, desc = pack_gt_depths(gt_depths, eval_split)
+    packed_d = packed.to(disp.device, non_blocking=True)
+    desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(disp.device)
+    max_rows = int((desc["y1"] - desc["y0"]).max())
+    cap = int(((desc["y1"] - desc["y0"]).astype(np.int64) * (desc["x1"] - desc["x0"])).sum())
+    return disp, packed, desc, packed_d, desc_d, max_rows, cap
+
+
 def eigen_scores(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_factor=1.0, disable_median_scaling=False, chunk=64):
     """evaluate_depth.py:344-478 without GDC, ``chunk`` images per ``fd_eigen_scores`` call (so that pinned and device memory stay
     bounded).  ``pred_disps``: [N,h,w] device tensor or host array (float64 is rounded to float32 once); ``gt_depths``: N [H_i,W_i]
@@ -182,17 +219,8 @@ def eigen_scores(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_fac
     rows = []
     for a in range(0, N, chunk):
         b = min(a + chunk, N)
-        disp = pred_disps[a:b]
-        disp = disp if torch.is_tensor(disp) else torch.as_tensor(np.asarray(disp))
-        disp = FD.f32(disp).cuda()
-        if disp.dim() != 3:
-            raise ValueError("eigen_scores: pred_disps must be [N,h,w], got %s" % (tuple(disp.shape),))
-        packed, desc = pack_gt_depths(gt_depths[a:b], eval_split)
+        disp, _, desc, packed_d, desc_d, max_rows, cap = _upload_chunk("eigen_scores", pred_disps[a:b], gt_depths[a:b], eval_split)
         dev = disp.device
-        packed_d = packed.to(dev, non_blocking=True)
-        desc_d = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-        max_rows = int((desc["y1"] - desc["y0"]).max())
-        cap = int(((desc["y1"] - desc["y0"]).astype(np.int64) * (desc["x1"] - desc["x0"])).sum())
         ws = torch.empty((max(query("fd_eigen_scores_ws_bytes", b - a, max_rows, cap), 8),), device=dev, dtype=torch.uint8)
         out = torch.empty((b - a, 9), device=dev, dtype=torch.float64)
         call("fd_eigen_scores", disp.data_ptr(), disp.shape[0], disp.shape[1], disp.shape[2], packed_d.data_ptr(), packed_d.numel(),
@@ -202,6 +230,92 @@ def eigen_scores(pred_disps, gt_depths, eval_split="eigen", pred_depth_scale_fac
     out = np.concatenate(rows) if rows else np.zeros((0, 9))
     ratios = np.zeros((0,), np.float32) if disable_median_scaling else out[:, 7].astype(np.float32)
     return out[:, :7].copy(), ratios, out[:, 8].astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- per semantic class
+def _label_plane(mask, i, H, W, who):
+    """Label mask ``i`` as a contiguous [H,W] uint8 array; ValueError when it is not of its ground truth's size or holds a value that
+    uint8 cannot hold without change."""
+    m = np.asarray(mask)
+    if m.shape != (H, W):
+        raise ValueError("%s: label mask %d has shape %s, its ground truth is %s" % (who, i, m.shape, (H, W)))
+    with np.errstate(invalid="ignore"):
+        u = m.astype(np.uint8)
+    if not np.array_equal(u, m):
+        raise ValueError("%s: label mask %d holds values that are not integers in 0 .. 255" % (who, i))
+    return np.ascontiguousarray(u)
+
+
+def pack_labels(sem_masks, desc):
+    """Label masks beside ``pack_gt_depths``' planes: a uint8 tensor of as many BYTES as the packed ground truth has floats, mask n at
+    byte ``desc[n]["offset"]`` (so a plane starts at any address: a 17x90 one is followed by one at an odd byte).  Pure host code;
+    pinned where a GPU is present.  ValueError, naming the image, when a mask is not [H,W] of its ground truth or cannot be held
+    as uint8 without change."""
+    if len(sem_masks) != len(desc):
+        raise ValueError("pack_labels: %d label masks for %d ground-truth maps" % (len(sem_masks), len(desc)))
+    total = int(sum(int(d["H"]) * int(d["W"]) for d in desc))
+    packed = torch.empty((max(total, 1),), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    flat = packed.numpy()
+    for i, (d, m) in enumerate(zip(desc, sem_masks)):
+        u = _label_plane(m, i, int(d["H"]), int(d["W"]), "pack_labels")
+        flat[d["offset"]:d["offset"] + u.size] = u.reshape(-1)
+    return packed[:total]
+
+
+def eigen_class_scores(pred_disps, gt_depths, sem_masks, num_classes=NUM_CLASSES, eval_split="eigen", pred_depth_scale_factor=1.0,
+                       disable_median_scaling=False, chunk=64):
+    """``eigen_scores`` and, from the same call (fd_eigen_class_scores), evaluate_depth.py:451-467: the metrics of every image per
+    label of ``sem_masks`` (N [H_i,W_i] uint8 maps; a label >= ``num_classes`` belongs to no class).  One upload of the labels and one
+    download per chunk.  Returns ``(per_image[N,7], ratios, counts`` - ``eigen_scores``' own, bit for bit - ``, class_metrics[N,K,7]
+    float64 (zeros where a class has no pixel), class_counts[N,K] int64)``."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("fusiondepth_amd.evaluate_depth.eigen_class_scores needs an MI355X: there is no CPU path (use oracle/ for CPU checks)")
+    N, K = len(gt_depths), int(num_classes)
+    if len(pred_disps) != N or len(sem_masks) != N:
+        raise ValueError("eigen_class_scores: %d predictions and %d label masks for %d ground-truth maps" % (len(pred_disps), len(sem_masks), N))
+    if chunk < 1 or chunk > 4096:
+        raise ValueError("eigen_class_scores: chunk must be 1 .. 4096")
+    gt_lo, gt_hi = split_bounds(eval_split)
+    rows, class_rows = [], []
+    for a in range(0, N, chunk):
+        b = min(a + chunk, N)
+        n = b - a
+        disp, _, desc, packed_d, desc_d, max_rows, cap = _upload_chunk("eigen_class_scores", pred_disps[a:b], gt_depths[a:b], eval_split)
+        dev = disp.device
+        labels = pack_labels(sem_masks[a:b], desc)
+        labels_d = labels.to(dev, non_blocking=True)
+        ws = torch.empty((max(query("fd_eigen_class_scores_ws_bytes", n, max_rows, cap, K), 8),), device=dev, dtype=torch.uint8)
+        both = torch.empty((n * 9 + n * max(K, 0) * 8,), device=dev, dtype=torch.float64)       # out, then class_out: one download
+        call("fd_eigen_class_scores", disp.data_ptr(), disp.shape[0], disp.shape[1], disp.shape[2], packed_d.data_ptr(), packed_d.numel(),
+             desc_d.data_ptr(), n, max_rows, cap, float(gt_lo), float(gt_hi), float(pred_depth_scale_factor),
+             0 if disable_median_scaling else 1, MIN_DEPTH, float(MAX_DEPTH), labels_d.data_ptr(), K, both.data_ptr(),
+             both.data_ptr() + n * 9 * 8, ws.data_ptr(), stream())
+        host = both.cpu().numpy()                                # synchronises: the pinned buffers are free to go afterwards
+        rows.append(host[:n * 9].reshape(n, 9))
+        class_rows.append(host[n * 9:].reshape(n, K, 8))
+    out = np.concatenate(rows) if rows else np.zeros((0, 9))
+    cls = np.concatenate(class_rows) if class_rows else np.zeros((0, max(K, 0), 8))
+    ratios = np.zeros((0,), np.float32) if disable_median_scaling else out[:, 7].astype(np.float32)
+    return out[:, :7].copy(), ratios, out[:, 8].astype(np.int64), cls[:, :, :7].copy(), cls[:, :, 7].astype(np.int64)
+
+
+def semantic_summary(class_metrics, class_counts):
+    """evaluate_depth.py:492-494 on the host: abs_rel of class c over the split, every image weighted by its pixels of the class,
+    ``sum_i(abs_rel[i, c] * count[i, c]) / (sum_i count[i, c] + 1e-16)`` -> [K] float64 (0 for a class without pixels anywhere)."""
+    abs_rel = np.asarray(class_metrics, np.float64)[:, :, 0].T            # [K, N], the reference's sem_errors[:, :, 0]
+    counts = np.asarray(class_counts, np.float64).T
+    return (abs_rel * counts).sum(1) / (counts.sum(1) + 0.0000000000000001)
+
+
+def semantic_mask_paths(semantic_dir, n):
+    """``<semantic_dir>/pred_mask{i}.png`` for the n images of the split, in scoring order (:452)."""
+    return [os.path.join(semantic_dir, "pred_mask{}.png".format(i)) for i in range(n)]
+
+
+def _require_masks(semantic_dir, n):
+    for path in semantic_mask_paths(semantic_dir, n):
+        if not os.path.isfile(path):
+            raise FileNotFoundError("evaluate_depth: --per_semantic needs the label mask {}".format(path))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the script
@@ -245,14 +359,15 @@ def split_off_splits_dir(argv, default="splits"):
     return found["splits_dir"], rest
 
 
-def _refuse_uncovered(opt):
-    """Everything ``evaluate`` does not cover, before anything touches the GPU."""
+def _refuse_uncovered(opt, semantic_dir=None):
+    """Everything ``evaluate`` does not cover, before anything touches the GPU.  ``--per_semantic`` is covered where the caller names
+    the folder of the masks."""
     if sum((bool(opt.eval_mono), bool(opt.eval_stereo))) != 1:
         raise ValueError("Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo")
     for flag, why in (("visualize", "it writes OpenCV colour maps and .npy dumps to fixed relative folders"),
-                      ("per_semantic", "it reads masks of an external segmentation run from a fixed relative folder"),
+                      ("per_semantic", "it reads masks of an external segmentation run from a fixed relative folder; name theirs with --semantic_dir"),
                       ("demo", "the demo split and its visualisation folders are not part of this package")):
-        if getattr(opt, flag):
+        if getattr(opt, flag) and not (flag == "per_semantic" and semantic_dir is not None):
             raise NotImplementedError("evaluate_depth: --%s is not covered (%s)" % (flag, why))
     if opt.save_sample != -1:
         raise NotImplementedError("evaluate_depth: --save_sample is not covered (a matplotlib plot saved to a path on the author's machine)")
@@ -311,12 +426,18 @@ def save_benchmark_predictions(opt, pred_disps):
     print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
 
 
-def evaluate(opt, splits_dir="splits"):
-    """evaluate_depth.py:74-489: the disparities of a saved model over ``<splits_dir>/<eval_split>/test_files.txt`` (or those of
+def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
+    """evaluate_depth.py:74-496: the disparities of a saved model over ``<splits_dir>/<eval_split>/test_files.txt`` (or those of
     ``--ext_disp_to_eval``), scored against ``gt_depths.npz`` of the split.  Returns ``(mean[7], ratios, per_image[N,7])``
     (``per_image`` is None with ``--eval_gdc``, which scores through ``evaluate_predictions``); None after ``--no_eval`` and for the
-    ``benchmark`` split, which has no ground truth."""
-    _refuse_uncovered(opt)
+    ``benchmark`` split, which has no ground truth.  With ``--per_semantic`` and a ``semantic_dir`` holding ``pred_mask{i}.png`` for
+    image i of the scored list: one line per class that has pixels, ``<semantic_out>/<run_name>.npy`` ([34] abs_rel per class) and
+    ``<semantic_out>/pixel_count.npy`` ([34, N]) as the reference writes them, and a fourth element
+    ``{"abs_rel": [34], "pixel_count": [34, N], "metrics": [N, 34, 7]}``."""
+    _refuse_uncovered(opt, semantic_dir)
+    per_semantic = bool(opt.per_semantic) and not opt.no_eval and opt.eval_split != "benchmark"
+    if per_semantic:
+        _require_masks(semantic_dir, 1)                          # a missing folder fails here, before anything is loaded
     dates = []
     if opt.ext_disp_to_eval is None:
         from .datasets import KITTIRAWBatches
@@ -328,6 +449,8 @@ def evaluate(opt, splits_dir="splits"):
             raise FileNotFoundError("Cannot find a folder at {}".format(folder))
         print("-> Loading weights from {}".format(folder))
         filenames = _read_lines(os.path.join(splits_dir, opt.eval_split, "test_files.txt"))
+        if per_semantic:
+            _require_masks(semantic_dir, len(filenames))
         enc = torch.load(os.path.join(folder, "encoder.pth"), map_location="cpu")
         height, width = int(enc.get("height", opt.height)), int(enc.get("width", opt.width))
         del enc
@@ -353,6 +476,8 @@ def evaluate(opt, splits_dir="splits"):
         pred_disps = np.load(opt.ext_disp_to_eval)
         if opt.eval_eigen_to_benchmark:
             pred_disps = pred_disps[np.load(os.path.join(splits_dir, "benchmark", "eigen_to_benchmark_ids.npy"))]
+        if per_semantic:
+            _require_masks(semantic_dir, len(pred_disps))
 
     if opt.save_pred_disps:
         output_path = os.path.join(opt.load_weights_folder, "disps_{}_split.npy".format(opt.eval_split))
@@ -374,6 +499,10 @@ def evaluate(opt, splits_dir="splits"):
         opt.pred_depth_scale_factor = STEREO_SCALE_FACTOR
     else:
         print("   Mono evaluation - using median scaling")
+    sem_masks, classes = None, None
+    if per_semantic:
+        from PIL import Image
+        sem_masks = [np.asarray(Image.open(path)) for path in semantic_mask_paths(semantic_dir, len(gt_depths))]
     if opt.eval_gdc:
         from . import kitti_utils
         if opt.random_sample == -1:
@@ -383,9 +512,14 @@ def evaluate(opt, splits_dir="splits"):
             beam_path = os.path.join(splits_dir, opt.eval_split, "r{}.npz".format(opt.random_sample))
         beam_depths = np.load(beam_path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
         calibs = [kitti_utils.Calibration(os.path.join(opt.data_path, d, "calib_cam_to_cam.txt")) for d in dates]
-        mean_errors, ratios = evaluate_predictions(pred_disps, gt_depths, opt.eval_split, opt.pred_depth_scale_factor,
-                                                   opt.disable_median_scaling, True, beam_depths, calibs, opt.random_sample, opt.nbeams)
+        scored = evaluate_predictions(pred_disps, gt_depths, opt.eval_split, opt.pred_depth_scale_factor, opt.disable_median_scaling,
+                                      True, beam_depths, calibs, opt.random_sample, opt.nbeams, sem_masks=sem_masks)
+        mean_errors, ratios, classes = scored[0], scored[1], scored[2:]
         per_image = None
+    elif per_semantic:
+        per_image, ratios, _, *classes = eigen_class_scores(pred_disps, list(gt_depths), sem_masks, NUM_CLASSES, opt.eval_split,
+                                                            opt.pred_depth_scale_factor, opt.disable_median_scaling)
+        mean_errors = per_image.mean(0)
     else:
         per_image, ratios, _ = eigen_scores(pred_disps, list(gt_depths), opt.eval_split, opt.pred_depth_scale_factor,
                                             opt.disable_median_scaling)
@@ -396,13 +530,24 @@ def evaluate(opt, splits_dir="splits"):
     print("\n  " + ("{:>8} | " * 7).format(*METRICS))
     print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
     print("\n-> Done!")
-    return mean_errors, ratios, per_image
+    if not per_semantic:
+        return mean_errors, ratios, per_image
+    class_metrics, class_counts = classes
+    abs_rel = semantic_summary(class_metrics, class_counts)
+    pixel_count = class_counts.T.astype(np.float64)              # [34, N], float64 like the reference's np.zeros([34, 697])
+    print("\n  {:>5} | {:>8} | {:>10}".format("class", "abs_rel", "pixels"))
+    for c in np.nonzero(pixel_count.sum(1) > 0)[0]:
+        print("  {:5d} | {: 8.3f} | {:10d}".format(c, abs_rel[c], int(pixel_count[c].sum())))
+    os.makedirs(semantic_out, exist_ok=True)
+    np.save(os.path.join(semantic_out, "{}.npy".format(opt.run_name if opt.run_name is not None else "per_semantic")), abs_rel)
+    np.save(os.path.join(semantic_out, "pixel_count.npy"), pixel_count)
+    return mean_errors, ratios, per_image, {"abs_rel": abs_rel, "pixel_count": pixel_count, "metrics": class_metrics}
 
 
 def main(argv=None):
     from .options import MonodepthOptions
-    splits_dir, rest = split_off_splits_dir(sys.argv[1:] if argv is None else argv)
-    return evaluate(MonodepthOptions().parse(rest), splits_dir)
+    found, rest = split_off_flags(sys.argv[1:] if argv is None else argv, {"splits_dir": "splits", "semantic_dir": None, "semantic_out": "."})
+    return evaluate(MonodepthOptions().parse(rest), found["splits_dir"], found["semantic_dir"], found["semantic_out"])
 
 
 if __name__ == "__main__":

@@ -849,6 +849,21 @@ def depth_errors(gt, pred):
     return tuple(out[i] for i in range(7))
 
 
+def class_errors(gt, pred, labels, num_classes=34, lo=1e-3, hi=80):
+    """evaluate_depth.py:455-467 on matched 1-D device tensors (float32, float32, uint8): for every class c < ``num_classes`` the
+    metrics of the pairs whose label is c, ``pred`` clamped to [lo, hi] -> [K, 8] float64 device tensor (abs_rel, sq_rel, rmse,
+    rmse_log, a1, a2, a3, count); a class without pairs gives eight zeros (fd_class_errors).  No CPU path."""
+    _need_cuda(gt, pred, labels)
+    if labels.dtype != torch.uint8:
+        raise RuntimeError("class_errors: labels must be uint8, got %s" % labels.dtype)
+    gt, pred, labels = f32(gt.detach()).reshape(-1), f32(pred.detach()).reshape(-1), labels.contiguous().reshape(-1)
+    if not gt.numel() == pred.numel() == labels.numel():
+        raise ValueError("class_errors: %d ground-truth values, %d predictions, %d labels" % (gt.numel(), pred.numel(), labels.numel()))
+    out = _empty((max(int(num_classes), 0), 8), gt, torch.float64)
+    call("fd_class_errors", ptr(gt), ptr(pred), ptr(labels), gt.numel(), int(num_classes), float(lo), float(hi), out.data_ptr(), stream())
+    return out
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
     """One torch.optim.Adam update of a flat fp32 tensor, in place."""
     bc1, bc2 = 1.0 - betas[0] ** step, 1.0 - betas[1] ** step

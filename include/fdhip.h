@@ -47,7 +47,9 @@ extern "C" {
  *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8.
  *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd).
  *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc).
- *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores). */
+ *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores).
+ *    Likewise the per-class Eigen-split scorer (fd_eigen_class_scores_ws_bytes, fd_eigen_class_scores, fd_class_errors; it reuses
+ *    struct fd_eigen_desc, and the workspace sizes of the three scorers above are what they were). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -829,6 +831,36 @@ long fd_eigen_scores_ws_bytes(int N, int max_rows, long list_cap);
 int fd_eigen_scores(const float* disp, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc, int N,
                     int max_rows, long list_cap, float gt_lo, float gt_hi, float pred_scale, int median_scaling, float lo, float hi,
                     double* out /*[N][9]*/, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ per-class Eigen-split scoring
+ * evaluate_depth.py's --per_semantic loop (:451-467): for every class c, compute_errors on the selected pixels whose label is c
+ * (csrc/eigen_class.hip).
+ * fd_eigen_class_scores: fd_eigen_scores' arguments from disp through hi, unchanged in meaning, and its launches; then
+ *   labels   packed_floats BYTES: the uint8 label plane of image n is H x W, row-major, and starts at BYTE desc[n].offset (the planes
+ *            lie back to back like the ground truth's, so they start at arbitrary - odd included - addresses; they are read by bytes).
+ *   K        1 .. 256 classes; a pixel whose label is >= K belongs to no class.
+ *   out      [N][9], exactly fd_eigen_scores' out for the same inputs, bit for bit.
+ *   class_out[n][c] = { abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count } as float64 over the selected pixels of image n whose
+ *            label is c: the SAME ratio (the whole image's), clamps and float32 terms as out[n], float64 sums.  While the pairs are
+ *            compacted, each selected pixel's label goes to a uint8 list at the pair's index; then one workgroup of 256 threads per
+ *            (class, image) walks the image's compact list: thread t adds pairs t, t + 256, ... of its class in index order, the
+ *            lanes of a wave add through a fixed shuffle tree, the four waves are added in wave order.  No partials, no float
+ *            atomics: bitwise reproducible.  A class without pixels gives eight zeros (the reference's np.zeros(7), count 0); a NaN
+ *            prediction in a class gives NaN for the first four and 0 for a1-a3, as in out; a refused descriptor (count -1 in out)
+ *            gives zero rows.
+ *   ws: fd_eigen_class_scores_ws_bytes(N, max_rows, list_cap, K) bytes, 8-byte aligned (fd_eigen_scores' layout followed by the label
+ *   list).  K outside 1 .. 256 or sizes outside fd_eigen_scores' limits: status -1, fd_last_error set, nothing launched (the size
+ *   query returns 0).  packed, desc, out, class_out 8-byte aligned.
+ * fd_class_errors: the class kernel alone on n >= 0 matched pairs that are already scaled: p = pred < lo ? lo : pred > hi ? hi : pred,
+ *   then as above -> class_out[c], c < K.  The same workgroup shape, thread stride and tree: the same pairs in the same order give
+ *   the same bits by either entry point.  One launch. */
+long fd_eigen_class_scores_ws_bytes(int N, int max_rows, long list_cap, int K);
+int fd_eigen_class_scores(const float* disp, int M, int h, int w, const float* packed, long packed_floats, const fd_eigen_desc* desc,
+                          int N, int max_rows, long list_cap, float gt_lo, float gt_hi, float pred_scale, int median_scaling, float lo,
+                          float hi, const unsigned char* labels, int K, double* out /*[N][9]*/, double* class_out /*[N][K][8]*/,
+                          void* ws, void* stream);
+int fd_class_errors(const float* gt, const float* pred, const unsigned char* labels, long n, int K, float lo, float hi,
+                    double* class_out /*[K][8]*/, void* stream);
 
 /* ------------------------------------------------------------------ training-time scoring ------
  * compute_depth_losses (trainer.py:598-630) + compute_depth_errors (layers.py:284-302) per image, for N images whose ground-truth maps

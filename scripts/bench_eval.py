@@ -6,6 +6,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py --step detection [--reps 10] [--out profiles/detection_export_time.log]
     python scripts/bench_eval.py --step val [--reps 5] [--out profiles/val_time.log]
     python scripts/bench_eval.py --step completion_val [--reps 5] [--out profiles/completion_val_time.log]
+    python scripts/bench_eval.py --step semantic [--reps 10] [--out profiles/eigen_class_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -29,7 +30,18 @@ the scorer alone between device events with everything resident.  No loader runs
 ``--step completion_val``: the same for ``Completor.val`` (ResNet-18 at 352x1216, batch 1) over 64 and over 1000 synthetic batches with
 352x1216 ground truth of which 15 % is valid: the fused route (``completor.val_scorer`` = a ``validation.CompletionValScorer``:
 ``fd_completion_val_scores`` once per 64 images, one download) against ``Completor.compute_depth_losses`` per batch, alternating; and the
-scorer alone between device events for 1 and for 64 images."""
+scorer alone between device events for 1 and for 64 images.
+
+``--step semantic``: ``--per_semantic``, the metrics per semantic class (34 classes, labels 0 .. 39 drawn uniformly, 8 distinct masks,
+cycled) at N = 1 and 64 on the inputs of the first step.  The library call ``fd_eigen_class_scores`` against the plain
+``fd_eigen_scores`` call on the same resident inputs, alternating, between device events: the increment is the price of the classes.
+Beside it the class kernel's traffic: each of the 34 workgroups of an image reads the image's three compact lists whole (label, gt
+and pred: 9 bytes per pair; the pairs of one class lie one in 40, so every cache line of the two float lists would be touched
+anyway, and reading them unconditionally keeps the loads of 16 steps in flight together) - L2 traffic, the lists were written
+just before; what reaches HBM is the plain call's bound plus 2 bytes per selected pixel (its label read from the plane, written to
+the list).  Then ``eigen_class_scores`` end to end (host
+packing, uploads of ground truth and labels, the call, one download) against the recipe it replaces - per image the ATen code of
+``evaluate_predictions`` and 34 boolean selections with a ``compute_errors`` call each - alternating, wall time."""
 import argparse
 import os
 import sys
@@ -43,6 +55,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from fusiondepth_amd import evaluate_depth as ED          # noqa: E402
+from fusiondepth_amd import functional as FD              # noqa: E402
 from fusiondepth_amd._lib import call, query, stream       # noqa: E402
 
 HBM = 6.3e12
@@ -183,6 +196,80 @@ def detection_step(a):
     return lines
 
 
+def semantic_step(a):
+    K = 34
+    rng = np.random.RandomState(5)
+    lines = ["Per-class Eigen-split scores (--per_semantic), 192x640 disparities, 375x1242 ground truth with 5 %% valid pixels, %d classes "
+             "(labels 0 .. 39), eigen split, median scaling; median (min, max) of %d rounds (3 for the recipe at N = 64) after one warm-up "
+             "round, the two routes alternating" % (K, a.reps)]
+    masks = [rng.randint(0, 40, (375, 1242)).astype(np.uint8) for _ in range(8)]
+    for n in (1, 64):
+        disps, gts = inputs(n, rng)
+        sems = [masks[i % 8] for i in range(n)]
+        plain, packed, bound, selected = library_call(disps, gts)
+        _, desc = ED.pack_gt_depths(gts, "eigen")
+        packed_d, desc_d = packed.cuda(), torch.from_numpy(desc.view(np.uint8).copy()).cuda()
+        labels = ED.pack_labels(sems, desc)
+        labels_d = labels.cuda()
+        rows = int((desc["y1"] - desc["y0"]).max())
+        cap = int(((desc["y1"] - desc["y0"]).astype(np.int64) * (desc["x1"] - desc["x0"])).sum())
+        ws = torch.empty((query("fd_eigen_class_scores_ws_bytes", n, rows, cap, K),), device="cuda", dtype=torch.uint8)
+        out = torch.empty((n, 9), device="cuda", dtype=torch.float64)
+        class_out = torch.empty((n, K, 8), device="cuda", dtype=torch.float64)
+
+        def classes():
+            call("fd_eigen_class_scores", disps.data_ptr(), disps.shape[0], 192, 640, packed_d.data_ptr(), packed_d.numel(), desc_d.data_ptr(), n,
+                 rows, cap, 1e-3, 80.0, 1.0, 1, 1e-3, 80.0, labels_d.data_ptr(), K, out.data_ptr(), class_out.data_ptr(), ws.data_ptr(), stream())
+
+        def recipe():
+            """evaluate_depth.py:344-478 with :451-467 in ATen, as ``evaluate_predictions`` spells the loop."""
+            res = []
+            for i in range(n):
+                gt = torch.as_tensor(gts[i], dtype=torch.float32).cuda()
+                sem = torch.as_tensor(sems[i]).cuda()
+                gh, gw = gt.shape
+                pred = 1.0 / FD.resize_linear_cv(disps[i][None, None], (gh, gw))[0, 0]
+                mask = (gt > ED.MIN_DEPTH) & (gt < ED.MAX_DEPTH)
+                c = ED.garg_crop(gh, gw)
+                crop = torch.zeros_like(mask)
+                crop[c[0]:c[1], c[2]:c[3]] = True
+                mask = mask & crop
+                pred = pred * (ED._median(gt[mask]) / ED._median(pred[mask]))
+                per_class = []
+                for k in range(K):
+                    final = mask & (sem == k)
+                    if int(final.sum()) > 0:
+                        per_class.append(ED.compute_errors(gt[final], torch.clamp(pred[final], ED.MIN_DEPTH, ED.MAX_DEPTH)))
+                    else:
+                        per_class.append((0.0,) * 7)
+                res.append(per_class)
+                ED.compute_errors(gt[mask], torch.clamp(pred[mask], ED.MIN_DEPTH, ED.MAX_DEPTH))
+            return np.array(res)
+
+        def whole():
+            return ED.eigen_class_scores(disps, gts, sems, K)
+
+        got, want = whole()[3], recipe()
+        worst = float(np.abs(got[:, :, 0] - want[:, :, 0]).max() / np.abs(want[:, :, 0]).max())
+        assert worst < 1e-4, "eigen_class_scores and the recipe disagree: %g" % worst
+        t_c, t_p = alternate([classes, plain], a.reps, _event_ms)
+        in_classes = int(class_out[:, :, 7].sum().item())
+        class_bytes = K * selected * 9 + n * K * 64
+        t_e, t_r = alternate([whole, recipe], a.reps if n == 1 else 3, _wall_ms)
+        lines.append("  N = %2d: fd_eigen_class_scores, resident (%d selected pixels, %d of them in a class): %.3f ms (%.3f, %.3f); fd_eigen_scores on "
+                     "the same inputs: %.3f ms (%.3f, %.3f) -> the classes cost %.3f ms = %.1f us / image (%.2fx the plain call); the class kernel's "
+                     "%d workgroups read %.2f MB from the L2, %.2f TB/s over the increment; HBM bound of the call %.2f MB = %.2f us at 6.3 TB/s"
+                     % (n, selected, in_classes, t_c[0], t_c[1], t_c[2], t_p[0], t_p[1], t_p[2], t_c[0] - t_p[0], 1e3 * (t_c[0] - t_p[0]) / n,
+                        t_c[0] / t_p[0], n * K, class_bytes / 1e6, class_bytes / (1e9 * (t_c[0] - t_p[0])), (bound + 2 * selected) / 1e6,
+                        1e6 * (bound + 2 * selected) / HBM))
+        lines.append("          eigen_class_scores end to end (host packing, uploads of %.1f MB ground truth and %.1f MB labels, 1 call, 1 download): "
+                     "%.2f ms (%.2f, %.2f) = %.3f ms / image; the recipe (per image the ATen loop, %d selections and compute_errors calls): "
+                     "%.2f ms (%.2f, %.2f) = %.3f ms / image -> %.2fx; abs_rel per class differs by at most %.1e of the largest"
+                     % (packed.numel() * 4 / 1e6, labels.numel() / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, K, t_r[0], t_r[1], t_r[2], t_r[0] / n,
+                        t_r[0] / t_e[0], worst))
+    return lines
+
+
 def val_step(a):
     from fusiondepth_amd import synthetic
     from fusiondepth_amd.options import MonodepthOptions
@@ -298,14 +385,16 @@ def completion_val_step(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic"), default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
-                                                "val": "val_time.log", "completion_val": "completion_val_time.log"}[a.step])
-    if a.step in ("detection", "val", "completion_val"):
-        text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step}[a.step](a))
+                                                "val": "val_time.log", "completion_val": "completion_val_time.log",
+                                                "semantic": "eigen_class_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val", "semantic"):
+        text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step,
+                          "semantic": semantic_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
