@@ -188,6 +188,7 @@ SIGNATURES = {
     "fd_post_process_disparity": ("ppplii" "p", "i"),
     "fd_adam_step": ("ppppl" "fffffff" "p", "i"),
     "fd_adam_step_dev": ("ppppl" "p" "ffff" "p", "i"),
+    "fd_adam_step_dev_zero": ("ppppl" "p" "ffff" "p", "i"),
     "fd_replay_function_count": ("", "i"),
     "fd_replay_function_name": ("i", "s"),
     "fd_replay_function_signature": ("i", "s"),

@@ -486,53 +486,72 @@ __global__ void __launch_bounds__(256) k_wgrad_finish(const float* __restrict__ 
     }
 }
 
-// The same reduction for 3x3 kernels with both sides coalesced: a workgroup owns (MB output channels m, 32 input channels); thread
-// (r, c) sums slab row [m][r][c0 + c] over the slices (128-byte rows, fixed order, eight loads in flight - with 128 slices of a
-// 64-channel layer or 8 192 (m, c block) pairs of a 512-channel one the pass was latency-bound at 4 loads and one m per workgroup),
-// the R x 32 block goes through LDS, and the 288 results leave as one contiguous run of gw[m][c0 .. c0 + 31][0 .. 8] (the generic
-// kernel writes single floats 36 bytes apart).  R = 9: slab rows are [ky][kx].  R = 12: slab rows are [ri][kx], the row components
-// of k_wgrad_wino<.., true>, and the vertical output transform is applied here:
+// The same reduction for 3x3 kernels with both sides coalesced: a workgroup owns (mb <= 8 output channels m, 32 input channels);
+// thread (r, c) sums slab row [m][r][c0 + c] over the slices (128-byte rows, fixed order: z ascending), the mb blocks of R x 32 sums
+// go through LDS, and the 288 results of a channel leave as one contiguous run of gw[m][c0 .. c0 + 31][0 .. 8] (the generic kernel
+// writes single floats 36 bytes apart).  The pass is bound by memory latency, not by bandwidth, so a thread keeps 16 independent
+// loads in flight whatever the shape: CH of the workgroup's channels x ZU slices at a time (the launcher picks CH from mb), all of
+// them issued in front of the workgroup's only barrier (one channel after the other costs a 512-channel layer - mb = 8, one slice -
+// eight dependent round trips with a barrier pair each: 14 against 7.5 us).  R = 9: slab rows are [ky][kx].  R = 12: slab rows are [ri][kx], the row components of
+// k_wgrad_wino<.., true>, and the vertical output transform is applied here:
 //   dW[ky = 0] = T0 + (T1 + T2) / 2,   dW[1] = (T1 - T2) / 2,   dW[2] = (T1 + T2) / 2 - T3.
-template <int R>
+constexpr int FIN9_MB = 8;                  // most output channels per workgroup: the LDS tile is [FIN9_MB][12][33]
+template <int R, int CH, int ZU>
 __global__ void __launch_bounds__(384) k_wgrad_finish9(const float* __restrict__ slabs, float* __restrict__ gw, int M, int C,
                                                        int splits, int accumulate, int mb) {
-    __shared__ float tile[12][33];
+    __shared__ float tile[FIN9_MB][12][33];
     const int c0 = blockIdx.x * 32;
     const int r = threadIdx.x >> 5, c = threadIdx.x & 31;
-    const size_t n = (size_t)M * R * C;
-    const int m_hi = min(M, ((int)blockIdx.y + 1) * mb);
+    const size_t n = (size_t)M * R * C, ms = (size_t)R * C;
+    const int m_lo = blockIdx.y * mb;
+    const int nch = min(M - m_lo, mb);          // 1 .. FIN9_MB channels of this workgroup
     const int cw = min(32, C - c0);             // the last block of a channel count that is not a multiple of 32 is narrower
-    for (int m = blockIdx.y * mb; m < m_hi; ++m) {
-        if (r < R && c < cw) {
-            const float* p = slabs + ((size_t)m * R + r) * C + c0 + c;
-            float s = 0.f;
-            int z = 0;
-            for (; z + 8 <= splits; z += 8) {
-                float a[8];
+    if (r < R && c < cw) {
+        const float* p = slabs + ((size_t)m_lo * R + r) * C + c0 + c;
+        for (int i0 = 0; i0 < nch; i0 += CH) {
+            float s[CH];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) a[u] = p[(size_t)(z + u) * n];
+            for (int i = 0; i < CH; ++i) s[i] = 0.f;
+            for (int z = 0; z < splits; z += ZU) {
+                // a channel or a slice past the end re-reads the last one (a valid address, a cache hit) and is not added
+                float a[CH][ZU];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) s += a[u];
+                for (int i = 0; i < CH; ++i)
+#pragma unroll
+                    for (int u = 0; u < ZU; ++u)
+                        a[i][u] = p[(size_t)min(i0 + i, nch - 1) * ms + (size_t)min(z + u, splits - 1) * n];
+#pragma unroll
+                for (int i = 0; i < CH; ++i)
+#pragma unroll
+                    for (int u = 0; u < ZU; ++u) s[i] = (z + u < splits) ? s[i] + a[i][u] : s[i];
             }
-            for (; z < splits; ++z) s += p[(size_t)z * n];
-            tile[r][c] = s;
+#pragma unroll
+            for (int i = 0; i < CH; ++i)
+                if (i0 + i < nch) tile[i0 + i][r][c] = s[i];
         }
-        __syncthreads();
-        const int j = threadIdx.x;
-        if (j < 9 * cw) {
-            const int cc = j / 9, tt = j - cc * 9;
+    }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j < 9 * cw) {
+        const int cc = j / 9, tt = j - cc * 9;
+        float* o = gw + ((size_t)m_lo * C + c0) * 9 + j;
+        const size_t os = (size_t)C * 9;
+        float old[FIN9_MB];
+#pragma unroll
+        for (int i = 0; i < FIN9_MB; ++i) old[i] = (accumulate && i < nch) ? o[i * os] : 0.f;
+#pragma unroll
+        for (int i = 0; i < FIN9_MB; ++i) {
+            if (i >= nch) break;
             float v;
-            if constexpr (R == 9) v = tile[tt][cc];
+            if constexpr (R == 9) v = tile[i][tt][cc];
             else {
                 const int ky = tt / 3, kx = tt - ky * 3;
-                const float t0 = tile[kx][cc], t1 = tile[3 + kx][cc], t2 = tile[6 + kx][cc], t3 = tile[9 + kx][cc];
+                const float t0 = tile[i][kx][cc], t1 = tile[i][3 + kx][cc], t2 = tile[i][6 + kx][cc], t3 = tile[i][9 + kx][cc];
                 const float h = 0.5f * (t1 + t2);
                 v = ky == 0 ? t0 + h : (ky == 1 ? 0.5f * (t1 - t2) : h - t3);
             }
-            float* o = gw + ((size_t)m * C + c0) * 9 + j;
-            *o = (accumulate ? *o : 0.f) + v;
+            o[i * os] = old[i] + v;
         }
-        __syncthreads();
     }
 }
 
@@ -672,8 +691,19 @@ int fast_wgrad_finish_launch(const float* slabs, float* gw, int M, int C, int T,
         int mb = (int)(((long)M * cb) / 1024);
         mb = mb < 1 ? 1 : (mb > 8 ? 8 : mb);
         const dim3 grid(cb, (M + mb - 1) / mb);
-        if (T == 9) hipLaunchKernelGGL(k_wgrad_finish9<9>, grid, dim3(384), 0, st, slabs, gw, M, C, splits, accumulate, mb);
-        else hipLaunchKernelGGL(k_wgrad_finish9<12>, grid, dim3(384), 0, st, slabs, gw, M, C, splits, accumulate, mb);
+        // 16 loads in flight per thread: CH channels (the power of two that covers mb) x ZU slices; a single slice needs no second one
+#define FD_FIN9(CH, ZU)                                                                                                    \
+    do {                                                                                                                   \
+        if (T == 9) hipLaunchKernelGGL((k_wgrad_finish9<9, CH, ZU>), grid, dim3(384), 0, st, slabs, gw, M, C, splits, accumulate, mb); \
+        else hipLaunchKernelGGL((k_wgrad_finish9<12, CH, ZU>), grid, dim3(384), 0, st, slabs, gw, M, C, splits, accumulate, mb);       \
+    } while (0)
+        static_assert(FIN9_MB == 8, "the mb rule above and the CH choice below end at 8 channels");
+        if (mb == 1) FD_FIN9(1, 16);
+        else if (mb == 2) FD_FIN9(2, 8);
+        else if (mb <= 4) FD_FIN9(4, 4);
+        else if (splits > 1) FD_FIN9(8, 2);
+        else FD_FIN9(8, 1);
+#undef FD_FIN9
         hipError_t e9 = hipGetLastError();
         if (e9 != hipSuccess) { fd_set_error("k_wgrad_finish9 launch failed: %s", hipGetErrorString(e9)); return (int)e9; }
         return 0;

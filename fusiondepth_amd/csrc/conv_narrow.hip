@@ -185,8 +185,8 @@ __global__ void __launch_bounds__(256) k_reduce_slabs_z(const float* __restrict_
 // Weight gradient of the 7x7 stride-2 pad-3 ResNet stems (networks/resnet_encoder.py:92, Cin = 2 / 3 / 4 / 6 after the
 // input-channel variants of :53-76): M = 64, J = 49*Cin, K = N*Ho*Wo.  Same structure as above: a 4 x 32 output tile of dY
 // (64 rows) and the (2*4+5) x (2*32+5) input patch per channel in LDS, zero padding resolved while staging.  The MFMA
-// N axis is a block of taps: column n = (dy & 1, dx) of a row pair -> 16 columns per (row pair, channel), 49 of 64 used.
-// Wave w owns dY rows 16w .. 16w+15 and walks all 128 pixels of the tile: 4 row pairs x Cin accumulators.
+// N axis is the flat tap index j = (c, dy, dx) in blocks of 16 columns: ceil(49 Cin / 16) blocks, every column but the last
+// block's tail a tap.  Wave w owns dY rows 16w .. 16w+15 and walks all 128 pixels of the tile: one accumulator per block.
 constexpr int STW = 32, STH = 4;                       // output-pixel tile
 constexpr int SPR = 2 * STH + 5, SPC = 2 * STW + 5;     // input patch rows / columns (13 x 69)
 constexpr int SXRS = 70;                               // patch row stride
@@ -195,7 +195,7 @@ constexpr int SYS = 132;                               // dY row stride: >= 128 
 static_assert(SYS >= STH * STW && SYS % 64 == 4, "stem LDS strides");
 
 template <int C>
-__global__ void __launch_bounds__(256) k_wgrad_stem(NarrowWgradArgs g) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_wgrad_stem(NarrowWgradArgs g) {   // two workgroups per CU
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sX = smem;                          // [C][SXCS]
     float* sY = smem + C * SXCS;               // [64][SYS]
@@ -208,13 +208,20 @@ __global__ void __launch_bounds__(256) k_wgrad_stem(NarrowWgradArgs g) {
     const int ntiles = g.N * tiles_per_img;
     const unsigned hw = (unsigned)(g.H * g.W), howo = (unsigned)(Ho * Wo);
 
-    f32x4 acc[4][C];
+    // MFMA column j = (c * 7 + dy) * 7 + dx, the slab's own order, in NB blocks of 16: lane li of block b owns column 16 b + li and
+    // reads its B operand at boff[b] = c * SXCS + dy * SXRS + dx (+ 2 lk: the lane's pixel of the K step).  Only the last block has
+    // columns past 49 C; they read the last tap and are never stored.  (A block per (row pair, channel) - 8 x 2 columns for 7 x 2 taps,
+    // 7 x 1 in the fourth pair - would take 4 C blocks: 24 / 16 / 12 / 8 for 6 / 4 / 3 / 2 channels against 19 / 13 / 10 / 7.)
+    constexpr int NJ = 49 * C, NB = (NJ + 15) / 16;
+    f32x4 acc[NB];
+    int boff[NB];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // B operand of column n = li: tap row parity li >> 3, tap column li & 7 (column 7 and row 7 are padding, never stored)
-    const int boff = (li >> 3) * SXRS + (li & 7) + 2 * lk;
+    for (int b = 0; b < NB; ++b) {
+        acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int j = min(16 * b + li, NJ - 1);
+        const int c = j / 49, t = j - 49 * c, dy = t / 7;
+        boff[b] = c * SXCS + dy * SXRS + (t - 7 * dy) + 2 * lk;
+    }
 
     // Software pipeline over the workgroup's tiles: the global loads of tile t + 1 (patch + all of dY: NXI + 32 registers) are issued
     // in front of the MFMA loop of tile t and written to LDS behind it.  (Round 3 loaded, stored and computed one tile after the
@@ -272,34 +279,29 @@ __global__ void __launch_bounds__(256) k_wgrad_stem(NarrowWgradArgs g) {
         __syncthreads();
         fetch(tile + gridDim.x);                                // in flight during the MFMA loop below
         const float* pa = sY + (wave * 16 + li) * SYS + lk;
-#pragma unroll 1
+        // both loops unrolled: (py, ks) then is an immediate of every LDS read and boff[] the only addresses in registers (in a rolled
+        // loop hipcc keeps a second, stepped copy of the NB addresses per loop level and the six-channel kernel spills)
+#pragma unroll
         for (int py = 0; py < STH; ++py) {
-#pragma unroll 2
+#pragma unroll
             for (int ks = 0; ks < STW / 4; ++ks) {
                 const float a = pa[py * STW + 4 * ks];
-                const float* pb = sX + (2 * py) * SXRS + 8 * ks + boff;     // input row 2*py + dy, column 2*(4ks + k) + dx
+                const float* pb = sX + (2 * py) * SXRS + 8 * ks;            // input row 2*py + dy, column 2*(4ks + k) + dx
 #pragma unroll
-                for (int dp = 0; dp < 4; ++dp)
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float b = pb[c * SXCS + 2 * dp * SXRS];
-                        acc[dp][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[dp][c], 0, 0, 0);
-                    }
+                for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pb[boff[b]], acc[b], 0, 0, 0);
             }
         }
     }
-    // ---- this workgroup's partial slab [m][c][7][7]; wave w holds rows 16w..16w+15 (no cross-wave sum needed)
-    float* slab = g.slabs + (size_t)blockIdx.x * g.M * C * 49;
+    // ---- this workgroup's partial slab [m][c][7][7] = [m][j]; wave w holds rows 16w..16w+15 (no cross-wave sum needed)
+    float* slab = g.slabs + (size_t)blockIdx.x * g.M * NJ;
 #pragma unroll
-    for (int dp = 0; dp < 4; ++dp)
+    for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int m = wave * 16 + 4 * lk + rg;             // C/D layout: row = 4*(lane>>4)+reg, col = lane&15
-                const int dy = 2 * dp + (li >> 3), dx = li & 7;
-                if (m < g.M && dy < 7 && dx < 7) slab[(m * C + c) * 49 + dy * 7 + dx] = acc[dp][c][rg];
-            }
+        for (int rg = 0; rg < 4; ++rg) {
+            const int m = wave * 16 + 4 * lk + rg;                 // C/D layout: row = 4*(lane>>4)+reg, col = lane&15
+            const int j = 16 * b + li;
+            if (m < g.M && j < NJ) slab[m * NJ + j] = acc[b][rg];
+        }
 }
 
 }  // namespace

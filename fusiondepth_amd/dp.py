@@ -165,6 +165,10 @@ class FlatParameters:
     def zero_grad(self):
         pass_state.join_wgrad_streams()          # side-stream weight gradients still accumulating into the buffer come first
         self.flat_grad.zero_()
+        self.attach_grads()
+
+    def attach_grads(self):
+        """``zero_grad`` without the fill, for a buffer that is zero already (the Adam kernel cleared what it read)."""
         for p, o in zip(self.params, self.offsets):     # autograd may have replaced .grad; re-attach the views
             if p.grad is None or p.grad.data_ptr() != self.flat_grad.data_ptr() + 4 * o:
                 p.grad = self.flat_grad[o:o + p.numel()].view(p.shape)

@@ -874,10 +874,11 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), ep
     refresh_weight_layouts()
 
 
-def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
-    """Adam update whose step counter / lr live in ``state`` (device, [step, lr]) — hipGraph-replay safe."""
+def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, zero_grad=False):
+    """Adam update whose step counter / lr live in ``state`` (device, [step, lr]) — hipGraph-replay safe.  ``zero_grad``: the same
+    launch leaves ``grad`` all zeros (fd_adam_step_dev_zero)."""
     sync_late_layouts()
     bump_weights_epoch()
-    call("fd_adam_step_dev", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(state), betas[0],
-         betas[1], float(eps), float(grad_scale), stream())
+    call("fd_adam_step_dev_zero" if zero_grad else "fd_adam_step_dev", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
+         param.numel(), ptr(state), betas[0], betas[1], float(eps), float(grad_scale), stream())
     refresh_weight_layouts()

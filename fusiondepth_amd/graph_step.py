@@ -87,8 +87,8 @@ class GraphedStep:
     def _body(self, tr):
         _, _, losses = tr._forward_backward(self.static_in, eager=False)
         if tr.world_size == 1:
-            tr.optim.step()
-            tr.flat.flat_grad.zero_()
+            if not tr.optim.step():
+                tr.flat.flat_grad.zero_()
         return {k: v.detach() for k, v in losses.items()}
 
     def _sync_and_step(self, tr):

@@ -4,6 +4,7 @@ device-side ``[step, lr]`` pair the kernel reads - and the ``adam.pth`` layout; 
 import torch
 
 from . import functional as FD
+from . import tuning
 
 
 class FlatAdam:
@@ -18,10 +19,14 @@ class FlatAdam:
         self.scheduler_step_size = scheduler_step_size
 
     def step(self, grad_scale=1.0):
-        """One fused launch, the gradient is the caller's to zero.  Step counter and lr are read from device memory, so the launch can
-        live inside a captured hipGraph - whose replays advance the device counter but not ``step_count``."""
+        """One fused launch.  Step counter and lr are read from device memory, so the launch can live inside a captured hipGraph -
+        whose replays advance the device counter but not ``step_count``.  Returns True if the launch also left
+        ``flat_grad`` all zeros (``tuning.host.adam_zero``, the default); otherwise the gradient is the caller's to zero."""
         self.step_count += 1
-        FD.adam_step_dev(self.flat.flat_param, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.state, grad_scale=grad_scale)
+        zero = bool(tuning.host.adam_zero)
+        FD.adam_step_dev(self.flat.flat_param, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.state, grad_scale=grad_scale,
+                         zero_grad=zero)
+        return zero
 
     def scheduler_step(self):
         """StepLR(step_size, 0.1).step()  (trainer.py:266): the learning rate drops by 10x every ``scheduler_step_size`` calls."""

@@ -346,9 +346,12 @@ class Trainer:
             weight_layouts.rebuild_weight_plan()
 
     def optimizer_step(self, grad_scale=1.0):
-        """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel (optim.FlatAdam)."""
-        self.optim.step(grad_scale)
-        self.flat.zero_grad()
+        """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel (optim.FlatAdam), which
+        clears the gradient buffer as it reads it; with ``tuning.host.adam_zero`` off the buffer is filled by a pass of its own."""
+        if self.optim.step(grad_scale):
+            self.flat.attach_grads()
+        else:
+            self.flat.zero_grad()
 
     def lr_scheduler_step(self):
         """StepLR(step_size, 0.1).step()  (trainer.py:266)."""

@@ -512,6 +512,10 @@ int fd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  * by this call; state[1] = lr), so that a captured hipGraph of the training step stays valid across replays. */
 int fd_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float* state, float beta1,
                      float beta2, float eps, float grad_scale, void* stream);
+/* fd_adam_step_dev followed by optimizer.zero_grad(): the same update, bit for bit, and grad[0 .. n) is left all zeros by the
+ * pass that read it (no separate fill of the gradient buffer). */
+int fd_adam_step_dev_zero(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float* state, float beta1,
+                          float beta2, float eps, float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------ sparse LiDAR --------------- */
 
