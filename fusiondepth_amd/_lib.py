@@ -225,6 +225,8 @@ SIGNATURES = {
     "fd_completion_val_scores": ("piii" "pl" "pi" "il" "fff" "p" "pp", "i"),
     "fd_depth_export": ("piii" "pi" "lii" "f" "ppp" "p", "i"),
     "fd_depth_quantize_u16": ("pplp", "i"),
+    "fd_vis_render_ws_bytes": ("il", "l"),
+    "fd_vis_render": ("piii" "fp" "p" "pl" "pi" "l" "ff" "pp" "pp" "l" "pp" "pp", "i"),
 }
 
 _lock = threading.Lock()

@@ -14,8 +14,11 @@
     per image in the reference - from the same library call per chunk (fd_eigen_class_scores, csrc/eigen_class.hip): each selected
     pixel's label rides beside its (gt, pred) pair, one workgroup per (class, image) sums its class over the compact list.  With
     ``--eval_gdc`` the classes are scored per image from the dense map (``functional.class_errors``, fd_class_errors).
-  * ``evaluate(opt, splits_dir, semantic_dir, semantic_out)`` / ``python -m fusiondepth_amd.evaluate_depth``: the script (:74-496), on
-    ``Predictor`` (with ``--refine_2d``: the stage-2 refine decoder) and ``KITTIRAWBatches``.
+  * ``--visualize`` (:252-261, :407-449): the two pictures per test image - the disparity in magma colours, the error through a hue ramp
+    at the evaluation mask - from one library call per chunk (``visualize.render``, fd_vis_render, csrc/visualize.hip), and the
+    ``.npy`` dumps beside them, under ``--vis_dir``.
+  * ``evaluate(opt, splits_dir, semantic_dir, semantic_out, vis_dir)`` / ``python -m fusiondepth_amd.evaluate_depth``: the script
+    (:74-496), on ``Predictor`` (with ``--refine_2d``: the stage-2 refine decoder) and ``KITTIRAWBatches``.
 
 Deviations from the reference, on purpose
   * disparities are scored as float32.  ``--post_process`` yields float64 (numpy's promotion in ``batch_post_process_disparity``), which
@@ -31,7 +34,14 @@ Deviations from the reference, on purpose
     arrays have one column per image of the split, not the reference's fixed 697; ``--run_name`` unset names the file ``per_semantic.npy``.
   * ``--no_eval`` and ``--eval_split benchmark`` return ``None`` instead of ending the interpreter; the benchmark PNGs are written with
     PIL; no wandb run, no ``visualization/dates.npy``, no input statistics printout.
-  * not covered, refused with the reason: ``--visualize``, ``--per_semantic`` without ``--semantic_dir``, ``--save_sample``, ``--demo``, the odometry splits, a model
+  * ``--visualize`` writes under ``--vis_dir`` (taken off the command line like ``--splits_dir``; ``prediction/`` and ``npy/`` are
+    created there) instead of ``visualization/`` in the working directory; without ``--vis_dir`` the flag is refused.  The PNGs are
+    written with PIL, not OpenCV.  ``{idx}rgb.png`` is written for EVERY item of a batch (the reference writes item 0 of each batch
+    under the batch's index), resized with ``FD.resize_linear_cv`` and rounded half to even.  The error picture's default colours
+    are an analytic hue ramp (``visualize.hue_lut``), NOT OpenCV's ``COLORMAP_HSV`` bit for bit: cv2 is not available to pin it.
+    After ``--eval_gdc`` the map is rounded to float32 once before it is drawn and dumped (the reference keeps GDC's float64);
+    ``beam_depth.npy`` is written only then, and holds the beam map as loaded.  No ``dates.npy``.
+  * not covered, refused with the reason: ``--visualize`` without ``--vis_dir``, ``--per_semantic`` without ``--semantic_dir``, ``--save_sample``, ``--demo``, the odometry splits, a model
     without the beam encoder, ``--cat2end`` with ``--refine_2d`` (the reference's refine branch reads ``beam_features``, which ``--cat2end``
     never computes), ``--eval_gdc`` with ``--ext_disp_to_eval`` (the reference's ``dates`` are undefined there).
 No CPU fallback: tensors must live on the GPU.
@@ -359,15 +369,20 @@ def split_off_splits_dir(argv, default="splits"):
     return found["splits_dir"], rest
 
 
-def _refuse_uncovered(opt, semantic_dir=None):
+# the flags of this script that are not among the reference's options (``split_off_flags``), with their defaults
+SCRIPT_FLAGS = {"splits_dir": "splits", "semantic_dir": None, "semantic_out": ".", "vis_dir": None}
+
+
+def _refuse_uncovered(opt, semantic_dir=None, vis_dir=None):
     """Everything ``evaluate`` does not cover, before anything touches the GPU.  ``--per_semantic`` is covered where the caller names
-    the folder of the masks."""
+    the folder of the masks, ``--visualize`` where the caller names the folder the pictures go to."""
     if sum((bool(opt.eval_mono), bool(opt.eval_stereo))) != 1:
         raise ValueError("Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo")
-    for flag, why in (("visualize", "it writes OpenCV colour maps and .npy dumps to fixed relative folders"),
+    named = {"per_semantic": semantic_dir, "visualize": vis_dir}  # covered where the caller names the folder
+    for flag, why in (("visualize", "it writes OpenCV colour maps and .npy dumps to fixed relative folders; name yours with --vis_dir"),
                       ("per_semantic", "it reads masks of an external segmentation run from a fixed relative folder; name theirs with --semantic_dir"),
                       ("demo", "the demo split and its visualisation folders are not part of this package")):
-        if getattr(opt, flag) and not (flag == "per_semantic" and semantic_dir is not None):
+        if getattr(opt, flag) and named.get(flag) is None:
             raise NotImplementedError("evaluate_depth: --%s is not covered (%s)" % (flag, why))
     if opt.save_sample != -1:
         raise NotImplementedError("evaluate_depth: --save_sample is not covered (a matplotlib plot saved to a path on the author's machine)")
@@ -412,6 +427,55 @@ def predict_disps(predictor, batch, opt):
     return pred_disp.cpu().numpy()
 
 
+def selection_mask(gt, eval_split):
+    """evaluate_depth.py:358-368 on the host: the boolean [H,W] mask of the pixels ``eval_split`` scores (``mask.npy`` of --visualize)."""
+    gt = np.asarray(gt, dtype=np.float32)
+    y0, y1, x0, x1 = split_window(eval_split, *gt.shape)
+    lo, hi = split_bounds(eval_split)
+    mask = gt > np.float32(lo)
+    if np.isfinite(hi):
+        mask &= gt < np.float32(hi)
+    crop = np.zeros(gt.shape, dtype=bool)
+    crop[max(y0, 0):max(y1, 0), max(x0, 0):max(x1, 0)] = True
+    return mask & crop
+
+
+def save_rgb_pngs(vis_dir, first, color):
+    """evaluate_depth.py:252-261 for every item of a batch: ``color`` [B,3,h,w] in 0 .. 1 on the device, resized to 375x1242 by
+    OpenCV's INTER_LINEAR rule, ``* 255``, rounded half to even -> ``<vis_dir>/prediction/{first + k}rgb.png``."""
+    from PIL import Image
+    os.makedirs(os.path.join(vis_dir, "prediction"), exist_ok=True)
+    rgb = torch.round(FD.resize_linear_cv(color, (375, 1242)) * 255.0).clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+    for k, img in enumerate(rgb):
+        Image.fromarray(np.ascontiguousarray(img)).save(os.path.join(vis_dir, "prediction", "{}rgb.png".format(first + k)))
+
+
+def save_visuals(vis_dir, vis_name, first, gt_depths, eval_split, pred_disps=None, ratios=None, pred_depth_scale_factor=1.0, depths=None,
+                 beam_depths=None):
+    """evaluate_depth.py:407-449 for images ``first`` .. of the scored list, one ``visualize.render`` call: the error picture
+    ``prediction/{i}{vis_name}.png``, the colour picture ``prediction/{i}{vis_name}depth.png`` and ``npy/{i}{vis_name}pred_depth.npy``,
+    ``..diff.npy``, ``..mask.npy`` (``..beam_depth.npy`` where ``beam_depths`` are given) under ``vis_dir``.  The map comes from
+    ``pred_disps`` with the scorer's ``ratios``, or from ``depths`` (dense device maps, after GDC)."""
+    from PIL import Image
+    from .visualize import render
+    pics, dumps = os.path.join(vis_dir, "prediction"), os.path.join(vis_dir, "npy")
+    os.makedirs(pics, exist_ok=True)
+    os.makedirs(dumps, exist_ok=True)
+    gt_depths = list(gt_depths)
+    colors, errors, maps = render(pred_disps, gt_depths, ratios, eval_split, pred_depth_scale_factor, depths=depths, want_depth=True,
+                                  chunk=max(1, min(len(gt_depths), 64)))
+    for k, gt in enumerate(gt_depths):
+        stem = "{}{}".format(first + k, vis_name)
+        pred = maps[k].cpu().numpy()
+        Image.fromarray(errors[k]).save(os.path.join(pics, stem + ".png"))
+        Image.fromarray(colors[k]).save(os.path.join(pics, stem + "depth.png"))
+        np.save(os.path.join(dumps, stem + "pred_depth.npy"), pred)
+        np.save(os.path.join(dumps, stem + "diff.npy"), np.abs(pred - np.asarray(gt, dtype=np.float32)))
+        np.save(os.path.join(dumps, stem + "mask.npy"), selection_mask(gt, eval_split))
+        if beam_depths is not None:
+            np.save(os.path.join(dumps, stem + "beam_depth.npy"), np.asarray(beam_depths[k]))
+
+
 def save_benchmark_predictions(opt, pred_disps):
     """evaluate_depth.py:291-311: the ``benchmark`` split has no ground truth; its predictions go to 352x1216 16-bit PNGs under
     ``<load_weights_folder>/benchmark_predictions``."""
@@ -426,15 +490,17 @@ def save_benchmark_predictions(opt, pred_disps):
     print("-> No ground truth is available for the KITTI benchmark, so not evaluating. Done.")
 
 
-def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
+def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out=".", vis_dir=None):
     """evaluate_depth.py:74-496: the disparities of a saved model over ``<splits_dir>/<eval_split>/test_files.txt`` (or those of
     ``--ext_disp_to_eval``), scored against ``gt_depths.npz`` of the split.  Returns ``(mean[7], ratios, per_image[N,7])``
     (``per_image`` is None with ``--eval_gdc``, which scores through ``evaluate_predictions``); None after ``--no_eval`` and for the
     ``benchmark`` split, which has no ground truth.  With ``--per_semantic`` and a ``semantic_dir`` holding ``pred_mask{i}.png`` for
     image i of the scored list: one line per class that has pixels, ``<semantic_out>/<run_name>.npy`` ([34] abs_rel per class) and
     ``<semantic_out>/pixel_count.npy`` ([34, N]) as the reference writes them, and a fourth element
-    ``{"abs_rel": [34], "pixel_count": [34, N], "metrics": [N, 34, 7]}``."""
-    _refuse_uncovered(opt, semantic_dir)
+    ``{"abs_rel": [34], "pixel_count": [34, N], "metrics": [N, 34, 7]}``.  With ``--visualize`` and a ``vis_dir``: the pictures and
+    dumps of ``save_visuals`` for every scored image (with the scorer's own ratios; the scores are what they are without the flag)
+    and, when the predictions are computed here, ``save_rgb_pngs`` for every item; the returned tuple keeps its length."""
+    _refuse_uncovered(opt, semantic_dir, vis_dir)
     per_semantic = bool(opt.per_semantic) and not opt.no_eval and opt.eval_split != "benchmark"
     if per_semantic:
         _require_masks(semantic_dir, 1)                          # a missing folder fails here, before anything is loaded
@@ -465,10 +531,13 @@ def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
         loader = KITTIRAWBatches(opt.data_path, filenames, height, width, [0], 4, is_train=False, img_ext=".png" if opt.png else ".jpg",
                                  opt=opt, batch_size=opt.eval_batch_size, drop_last=False)
         print("-> Computing predictions with size {}x{}".format(width, height))
-        pred_disps = []
+        pred_disps, idx = [], 0
         for batch in loader:
             dates += batch["date"]
             pred_disps.append(predict_disps(predictor, batch, opt))
+            if opt.visualize:
+                save_rgb_pngs(vis_dir, idx, batch["color", 0, 0])
+            idx += len(pred_disps[-1])
         loader.close()
         pred_disps = np.concatenate(pred_disps)
     else:
@@ -512,8 +581,23 @@ def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
             beam_path = os.path.join(splits_dir, opt.eval_split, "r{}.npz".format(opt.random_sample))
         beam_depths = np.load(beam_path, fix_imports=True, encoding="latin1", allow_pickle=True)["data"]
         calibs = [kitti_utils.Calibration(os.path.join(opt.data_path, d, "calib_cam_to_cam.txt")) for d in dates]
+        held = []                                                # dense maps after GDC, rounded to float32 once, 64 per render call
+
+        def flush(upto):
+            if held:
+                first = upto - len(held)
+                save_visuals(vis_dir, opt.vis_name, first, gt_depths[first:upto], opt.eval_split, depths=held, beam_depths=beam_depths[first:upto])
+                del held[:]
+
+        def on_depth(i, depth):
+            held.append(depth.detach().to(torch.float32))
+            if len(held) == 64:
+                flush(i + 1)
+
         scored = evaluate_predictions(pred_disps, gt_depths, opt.eval_split, opt.pred_depth_scale_factor, opt.disable_median_scaling,
-                                      True, beam_depths, calibs, opt.random_sample, opt.nbeams, sem_masks=sem_masks)
+                                      True, beam_depths, calibs, opt.random_sample, opt.nbeams, sem_masks=sem_masks,
+                                      on_depth=on_depth if opt.visualize else None)
+        flush(len(gt_depths))
         mean_errors, ratios, classes = scored[0], scored[1], scored[2:]
         per_image = None
     elif per_semantic:
@@ -524,6 +608,11 @@ def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
         per_image, ratios, _ = eigen_scores(pred_disps, list(gt_depths), opt.eval_split, opt.pred_depth_scale_factor,
                                             opt.disable_median_scaling)
         mean_errors = per_image.mean(0)
+    if opt.visualize and not opt.eval_gdc:
+        for a in range(0, len(gt_depths), 64):
+            b = min(a + 64, len(gt_depths))
+            save_visuals(vis_dir, opt.vis_name, a, gt_depths[a:b], opt.eval_split, pred_disps[a:b],
+                         None if opt.disable_median_scaling else ratios[a:b], opt.pred_depth_scale_factor)
     if not opt.disable_median_scaling:
         med = np.median(ratios)
         print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
@@ -546,8 +635,11 @@ def evaluate(opt, splits_dir="splits", semantic_dir=None, semantic_out="."):
 
 def main(argv=None):
     from .options import MonodepthOptions
-    found, rest = split_off_flags(sys.argv[1:] if argv is None else argv, {"splits_dir": "splits", "semantic_dir": None, "semantic_out": "."})
-    return evaluate(MonodepthOptions().parse(rest), found["splits_dir"], found["semantic_dir"], found["semantic_out"])
+    found, rest = split_off_flags(sys.argv[1:] if argv is None else argv, SCRIPT_FLAGS)
+    folders = (found["splits_dir"], found["semantic_dir"], found["semantic_out"])
+    if found["vis_dir"] is not None:                              # a call without --vis_dir stays the call it was
+        folders += (found["vis_dir"],)
+    return evaluate(MonodepthOptions().parse(rest), *folders)
 
 
 if __name__ == "__main__":

@@ -24,6 +24,7 @@ from .loss_ops import (PROJECT_EPS, PhotoOptions, backproject_depth, bilinear_up
 from .pass_state import (add_grad_ready_callback, begin_forward_pass, bn_groups, bump_bn_counter, current_bn_groups,  # noqa: F401
                          defer_bn_counters, direct_grad_target, enable_direct_grad, enable_side_wgrad, grad_ready, has_side_wgrad,
                          join_wgrad_streams, keep_until_wgrad_join, note_use, param_uses, wgrad_stream)
+from .visualize import colorize_disparity  # noqa: F401
 from .weight_layouts import (build_weight_plan, bump_weights_epoch, enable_weight_cache, evict_dead_weight_layouts,  # noqa: F401
                              frozen_epoch, invalidate_frozen_layouts, refresh_weight_layouts, release_retired_layouts,
                              sync_late_layouts, unfreeze, weight_layout, weight_plan_needs_rebuild)

@@ -49,7 +49,8 @@ extern "C" {
  *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc).
  *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores).
  *    Likewise the per-class Eigen-split scorer (fd_eigen_class_scores_ws_bytes, fd_eigen_class_scores, fd_class_errors; it reuses
- *    struct fd_eigen_desc, and the workspace sizes of the three scorers above are what they were). */
+ *    struct fd_eigen_desc, and the workspace sizes of the three scorers above are what they were).
+ *    Likewise the renderer of evaluate_depth --visualize (fd_vis_render_ws_bytes, fd_vis_render; it reuses struct fd_eigen_desc). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -936,6 +937,41 @@ typedef struct fd_export_desc {
 int fd_depth_export(const float* disp, int M, int h, int w, const fd_export_desc* desc, int N, long packed_elems, int max_H, int max_W,
                     float pred_scale, const float* ratio /*[N] or NULL*/, float* depth_out, uint16_t* u16_out, void* stream);
 int fd_depth_quantize_u16(const double* x, uint16_t* out, long n, void* stream);
+
+/* ------------------------------------------------------------------ evaluate_depth --visualize --
+ * The two pictures of evaluate_depth.py:407-449 for N <= 64 maps of different sizes, packed back to back as fd_depth_export and
+ * fd_eigen_scores pack them, in at most 9 launches and one memset whatever N is (csrc/visualize.hip).
+ *   The map: EITHER disp [M][h][w] with pred_scale and ratio ([N] or NULL) - the depth is then formed exactly as fd_depth_export forms
+ *            it (OpenCV's float32 INTER_LINEAR rule through csrc/cv_resize.h, 1 / ., * pred_scale, * ratio[n]) - OR depth_in, packed_floats
+ *            dense float32 values at the descriptors' offsets (the map GDC returns, rounded to float32 once).  Exactly one is given.
+ *   packed_gt / desc  the packed ground truth and the DEVICE descriptors of fd_eigen_scores; gt_lo / gt_hi its bounds (gt_hi = +inf: no
+ *            upper bound).  packed_gt may be NULL when err is.  With depth_in, `pred` is not read.  A descriptor whose plane leaves
+ *            [0, packed_floats), whose window leaves the plane or whose `pred` is not in [0, M) writes nothing; nothing outside the
+ *            buffers is read.  max_pixels >= H * W of every image (it sizes the grids).
+ *   lut_disp / lut_err  two colour tables of 256 x 3 uint8, RGB order.
+ * Outputs, each optional (NULL skips its work), at least one given:
+ *   depth_out  float32, packed_floats: the depth maps.
+ *   stats      [N][2] float32 (vmin, vmax) of d' = 1.0f / depth (IEEE): vmin = min d'; vmax = np.percentile(d', 95) as numpy 2 computes
+ *            it for float32 input, in float32 throughout: q = 95.0f / 100.0f, pos = (float)(n - 1) * q, k = floor(pos), g = pos - k,
+ *            a = sorted[k], b = sorted[min(k + 1, n - 1)], vmax = a + (b - a) * g, or b - (b - a) * (1.0f - g) where g >= 0.5f, or a
+ *            where a == b.  The two order statistics come from a radix select over the whole plane (up to 64 workgroups per image, LDS
+ *            histograms merged into one per image and pass with integer atomics, one launch per 8-bit pass; a fifth pass counts the
+ *            keys <= a's and takes the smallest key above and the minimum).
+ *   color    uint8, 3 * packed_floats: image n is [H][W][3] at byte 3 * offset.  xn = (float)((double)(d' - vmin) / ((double)vmax -
+ *            (double)vmin)) - a float32 difference, a float64 quotient rounded to float32 once -, 0 where vmin == vmax; xa = xn * 256.0f; index = trunc(xa) clamped to 0 .. 255 (xa >= 256 -> 255; NaN and
+ *            negative -> 0; a non-finite d' -> 0); the pixel is lut_disp[index] - matplotlib's Normalize and colormap call.
+ *   err      uint8, 3 * err_pixels: the pictures [ceil(H/2)][ceil(W/2)][3] back to back in descriptor order (a refused descriptor takes no room).  At a pixel inside the
+ *            window whose ground truth is selected (gt > gt_lo && gt < gt_hi): v = trunc(80.0f - clamp(|depth - gt|, 0, 2) * 40.0f)
+ *            and the colour lut_err[v]; elsewhere 0.  Then the 2 x 2 maximum per channel (rows and columns beyond an odd edge count
+ *            as 0) and (220, 220, 220) where all three channels are 0.  A picture that would leave err_pixels is not written.
+ * Each float32 step is one rounding, no contraction, no float atomics: two calls give the same bits.  The pictures are written as
+ * 16-byte stores wherever the address allows, byte by byte before the first and after the last 16-byte boundary of an image.
+ *   ws: fd_vis_render_ws_bytes(N, packed_floats) bytes, 16-byte aligned (0: sizes out of range). */
+long fd_vis_render_ws_bytes(int N, long packed_floats);
+int fd_vis_render(const float* disp, int M, int h, int w, float pred_scale, const float* ratio /*[N] or NULL*/, const float* depth_in,
+                  const float* packed_gt, long packed_floats, const fd_eigen_desc* desc, int N, long max_pixels, float gt_lo, float gt_hi,
+                  const unsigned char* lut_disp, const unsigned char* lut_err, unsigned char* color, unsigned char* err, long err_pixels,
+                  float* stats /*[N][2]*/, float* depth_out, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

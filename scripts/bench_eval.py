@@ -7,6 +7,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py --step val [--reps 5] [--out profiles/val_time.log]
     python scripts/bench_eval.py --step completion_val [--reps 5] [--out profiles/completion_val_time.log]
     python scripts/bench_eval.py --step semantic [--reps 10] [--out profiles/eigen_class_time.log]
+    python scripts/bench_eval.py --step visualize [--reps 10] [--out profiles/visualize_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -41,7 +42,14 @@ anyway, and reading them unconditionally keeps the loads of 16 steps in flight t
 just before; what reaches HBM is the plain call's bound plus 2 bytes per selected pixel (its label read from the plane, written to
 the list).  Then ``eigen_class_scores`` end to end (host
 packing, uploads of ground truth and labels, the call, one download) against the recipe it replaces - per image the ATen code of
-``evaluate_predictions`` and 34 boolean selections with a ``compute_errors`` call each - alternating, wall time."""
+``evaluate_predictions`` and 34 boolean selections with a ``compute_errors`` call each - alternating, wall time.
+
+``--step visualize``: the two pictures of ``--visualize``, ``visualize.render`` (fd_vis_render, csrc/visualize.hip), at N = 1 and 64 maps of
+375x1242 on the inputs of the first step with per-image ratios, against the device recipe it replaces - per image one
+``FD.resize_linear_cv``, ``torch.sort`` for the percentile, a gather per table and ``max_pool2d`` - alternating in one run after the two
+were compared byte for byte.  Per N: the library call alone between device events with its traffic bound (the source and the ground
+truth read once, the pictures written once), the recipe's device part, both end to end with their downloads as wall time, and - for
+orientation, once - the reference's host code for the colour picture (``np.percentile``, ``Normalize``, ``magma``) on 16 threads."""
 import argparse
 import os
 import sys
@@ -193,6 +201,111 @@ def detection_step(a):
         lines.append("          depth_export end to end (descriptor and ratio uploads, 1 call, pinned download of %.1f MB): %.3f ms (%.3f, %.3f) "
                      "= %.3f ms / image; recipe end to end (float32 download, host * 256 and cast): %.3f ms (%.3f, %.3f) = %.3f ms / image -> %.2fx"
                      % (2 * total / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, t_r[0], t_r[1], t_r[2], t_r[0] / n, t_r[0] / t_e[0]))
+    return lines
+
+
+def visualize_step(a):
+    from concurrent.futures import ThreadPoolExecutor
+    from fusiondepth_amd import visualize as V
+    H, W, h, w = 375, 1242, 192, 640
+    rng = np.random.RandomState(5)
+    lut_disp, lut_err = V.magma_lut(), V.hue_lut()
+    luts = torch.from_numpy(np.concatenate([lut_disp, lut_err])).cuda()
+    lut_d, lut_e = luts[:256], luts[256:]
+    lines = ["evaluate_depth --visualize, %dx%d disparities -> %dx%d colour and %dx%d error pictures, eigen split, per-image ratios, 5 %% "
+             "valid ground truth; median of %d (min, max) after one warm-up round, renderer and recipe alternating"
+             % (h, w, H, W, (H + 1) // 2, (W + 1) // 2, a.reps)]
+    y0, y1, x0, x1 = ED.split_window("eigen", H, W)
+    for n in (1, 64):
+        disps, gts = inputs(n, rng)
+        ratios = rng.uniform(1.2, 1.4, n).astype(np.float32)
+        ratios_t = [torch.tensor(r, dtype=torch.float32, device="cuda") for r in ratios]
+        packed, desc = ED.pack_gt_depths(gts, "eigen")
+        total = packed.numel()
+        packed_d, desc_d, ratio_d = packed.cuda(), torch.from_numpy(desc.view(np.uint8).copy()).cuda(), torch.from_numpy(ratios).cuda()
+        gts_d = [packed_d[int(d["offset"]):int(d["offset"]) + H * W].view(H, W) for d in desc]
+        err_pixels = n * ((H + 1) // 2) * ((W + 1) // 2)
+        out = torch.empty((3 * total + 3 * err_pixels,), device="cuda", dtype=torch.uint8)
+        ws = torch.empty((query("fd_vis_render_ws_bytes", n, total),), device="cuda", dtype=torch.uint8)
+
+        def kernel():
+            call("fd_vis_render", disps.data_ptr(), n, h, w, 1.0, ratio_d.data_ptr(), None, packed_d.data_ptr(), total, desc_d.data_ptr(), n,
+                 H * W, 1e-3, 80.0, lut_d.data_ptr(), lut_e.data_ptr(), out.data_ptr(), out.data_ptr() + 3 * total, err_pixels, None, None,
+                 ws.data_ptr(), stream())
+
+        def recipe_device():
+            """The pictures from what the package offered before: one resize per image, a sort for the percentile, gathers, a pool."""
+            res = []
+            for i in range(n):
+                depth = (1.0 / FD.resize_linear_cv(disps[i][None, None], (H, W))[0, 0]) * 1.0 * ratios_t[i]
+                d = 1.0 / depth
+                s, _ = torch.sort(d.reshape(-1))
+                m = s.numel()
+                pos = np.float32(m - 1) * (np.float32(95.0) / np.float32(100.0))
+                k = int(np.floor(pos))
+                g = float(np.float32(pos - np.float32(k)))
+                lo, hi = s[k], s[min(k + 1, m - 1)]
+                vmax = hi - (hi - lo) * (1.0 - g) if g >= 0.5 else lo + (hi - lo) * g
+                vmax = torch.where(lo == hi, lo, vmax)
+                xn = ((d - s[0]).double() / (vmax.double() - s[0].double())).float()
+                xa = xn * 256.0
+                color = lut_d[torch.where(xa >= 256.0, torch.full_like(xa, 255.0), xa).clamp_(0, 255).long()]
+                gt = gts_d[i]
+                mask = (gt > ED.MIN_DEPTH) & (gt < ED.MAX_DEPTH)
+                crop = torch.zeros_like(mask)
+                crop[y0:y1, x0:x1] = True
+                mask = mask & crop
+                v = (80.0 - torch.clamp(torch.abs(depth - gt), 0, 2) * 40.0).long().clamp_(0, 255)
+                col = lut_e[v] * mask[:, :, None]
+                small = torch.nn.functional.max_pool2d(col.permute(2, 0, 1)[None].float(), 2, ceil_mode=True)[0].permute(1, 2, 0)
+                small = torch.where((small == 0).all(2, keepdim=True), torch.full_like(small, 220.0), small).to(torch.uint8)
+                res.append((color, small))
+            return res
+
+        def recipe_all():
+            return [(c.cpu().numpy(), e.cpu().numpy()) for c, e in recipe_device()]
+
+        def render_all():
+            return V.render(disps, gts, ratios, "eigen")
+
+        def host_all():
+            """The reference's host code per image (:437-441), 16 threads; the depth maps are given."""
+            def one(depth):
+                disp = 1 / depth
+                mapper = cm.ScalarMappable(norm=mpl.colors.Normalize(vmin=disp.min(), vmax=np.percentile(disp, 95)), cmap="magma")
+                return (mapper.to_rgba(disp)[:, :, :3] * 255).astype(np.uint8)
+
+            with ThreadPoolExecutor(16) as ex:
+                return list(ex.map(one, host_depths))
+
+        got, want = render_all(), recipe_all()                   # same bytes before anything is timed
+        for i in range(n):
+            assert np.array_equal(got[0][i], want[i][0]) and np.array_equal(got[1][i], want[i][1]), "renderer and recipe disagree at image %d" % i
+        t_k, t_rd = alternate([kernel, recipe_device], a.reps if n == 1 else max(3, a.reps // 3), _event_ms)
+        t_e, t_r = alternate([render_all, recipe_all], a.reps if n == 1 else max(3, a.reps // 3), _wall_ms)
+        try:
+            import matplotlib as mpl
+            from matplotlib import cm
+            cm.ScalarMappable(cmap="magma").to_rgba(np.zeros((2, 2), np.float32))      # first use builds the table: not timed
+            host_depths =[m.cpu().numpy() for m in V.render(disps, gts, ratios, "eigen", want_depth=True)[2]]
+            t0 = time.perf_counter()
+            host = host_all()
+            t_h = 1e3 * (time.perf_counter() - t0)
+            assert all(np.array_equal(a_, b_) for a_, b_ in zip(host, got[0])), "matplotlib and the renderer disagree"
+            host_text = "host numpy + matplotlib for the colour picture alone, 16 threads, maps given: %.1f ms = %.2f ms / image" % (t_h, t_h / n)
+        except ImportError:
+            host_text = "matplotlib is not installed: no host figure"
+        bound = 4 * n * h * w + 4 * total + 3 * total + 3 * err_pixels
+        t_bound = 1e3 * bound / HBM
+        lines.append("  N = %2d: fd_vis_render, resident, both pictures (9 launches): %.3f ms (%.3f, %.3f) = %.1f us / image; traffic bound (source and "
+                     "ground truth read once, pictures written once) %.2f MB = %.2f us at 6.3 TB/s -> %.1fx the bound; the recipe's device part: "
+                     "%.3f ms (%.3f, %.3f) -> %.2fx"
+                     % (n, t_k[0], t_k[1], t_k[2], 1e3 * t_k[0] / n, bound / 1e6, 1e3 * t_bound, t_k[0] / t_bound, t_rd[0], t_rd[1], t_rd[2],
+                        t_rd[0] / t_k[0]))
+        lines.append("          render end to end (host packing, upload of %.1f MB ground truth, 1 call, pinned download of %.1f MB): %.2f ms (%.2f, "
+                     "%.2f) = %.3f ms / image; recipe end to end (two downloads per image): %.2f ms (%.2f, %.2f) = %.3f ms / image -> %.2fx; %s"
+                     % (4 * total / 1e6, out.numel() / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, t_r[0], t_r[1], t_r[2], t_r[0] / n,
+                        t_r[0] / t_e[0], host_text))
     return lines
 
 
@@ -385,16 +498,16 @@ def completion_val_step(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize"), default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
                                                 "val": "val_time.log", "completion_val": "completion_val_time.log",
-                                                "semantic": "eigen_class_time.log"}[a.step])
-    if a.step in ("detection", "val", "completion_val", "semantic"):
+                                                "semantic": "eigen_class_time.log", "visualize": "visualize_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val", "semantic", "visualize"):
         text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step,
-                          "semantic": semantic_step}[a.step](a))
+                          "semantic": semantic_step, "visualize": visualize_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
