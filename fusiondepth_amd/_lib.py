@@ -90,6 +90,18 @@ class RelayoutJob(ctypes.Structure):
                 [("n", ctypes.c_long), ("first_block", ctypes.c_long)])
 
 
+class LogTile(ctypes.Structure):
+    """Mirror of ``fd_log_tile``."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("p0", "p1", "p2", "p3", "p4")] + \
+               [(n, _I) for n in ("kind", "y", "x", "h", "w", "aux", "slot", "reserved")]
+
+
+class LogCfg(ctypes.Structure):
+    """Mirror of ``fd_log_cfg``."""
+    _fields_ = [("Hs", _I), ("Ws", _I), ("n_rows", _I), ("n_disp", _I), ("row_y", _I * 8), ("row_h", _I * 8), ("row_first", _I * 8),
+                ("row_count", _I * 8), ("disp_tile", _I * 8), ("lo", _F), ("span", _F), ("eps", _F), ("reserved", _I)]
+
+
 # name -> (argument kinds, restype kind)  ('p' pointer, 'i' int, 'l' long, 'f' float, 'd' double)
 SIGNATURES = {
     "fd_abi_version": ("", "i"),
@@ -227,6 +239,8 @@ SIGNATURES = {
     "fd_depth_quantize_u16": ("pplp", "i"),
     "fd_vis_render_ws_bytes": ("il", "l"),
     "fd_vis_render": ("piii" "fp" "p" "pl" "pi" "l" "ff" "pp" "pp" "l" "pp" "pp", "i"),
+    "fd_log_sheets_ws_bytes": ("ii", "l"),
+    "fd_log_sheets": ("pp" "ii" "p" "pp" "p", "i"),
 }
 
 _lock = threading.Lock()

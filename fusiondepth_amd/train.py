@@ -1,6 +1,7 @@
 """The reference's ``python trainer.py`` as a command: options -> loaders -> ``Trainer.train`` with in-training validation.
 
     python -m fusiondepth_amd.train [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
+                                    [--log_images]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.train ...          # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  trainer.py:142-174: the training lines of
@@ -24,7 +25,10 @@ Deviations from the reference, on purpose
     flag is spelled out on this command line, which then holds: a short run must be possible without a batch size of 136.
   * ``--dataset`` other than ``kitti`` is refused: the reference's ``KITTIOdomDataset`` has no LiDAR keys, and nothing here reads the
     odometry layout.
-  * no tensorboard / wandb: the scalars go to ``<log_path>/{train,val}/scalars.jsonl`` (``Trainer.log``).
+  * no tensorboard / wandb: the scalars go to ``<log_path>/{train,val}/scalars.jsonl`` (``Trainer.log``).  ``--log_images`` adds the
+    reference's image summaries (trainer.py:656-681) at every log event: one contact sheet per item, rendered on the device
+    (log_images.py), as ``<log_path>/{train,val}/images/{step:07d}_{j}.png``; ``Trainer.image_sink`` takes a tensorboard or wandb
+    writer instead.  Rank 0 alone logs, so the switch is set on rank 0 alone.
 """
 import json
 import os
@@ -37,13 +41,15 @@ from . import dp
 from .evaluate_depth import split_off_flags
 
 EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None}
-EXTRA_SWITCHES = ("no_val",)
+EXTRA_SWITCHES = ("no_val", "log_images")
 
 
 def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({splits_dir, seed, lidar_source, val_limit,
-    no_val}, the remaining arguments)."""
+    no_val}, the remaining arguments); ``log_images: True`` joins the dict where ``--log_images`` is given, and only there."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
+    if not found["log_images"]:
+        del found["log_images"]
     found["seed"] = int(found["seed"])
     if found["val_limit"] is not None:
         found["val_limit"] = int(found["val_limit"])
@@ -137,6 +143,8 @@ def main(argv=None):
     trainer = Trainer(opt, rank=rank, world_size=world)
     if epochs_given is not None:
         trainer.opt.num_epochs = epochs_given
+    if extra.get("log_images") and rank == 0:                    # the other ranks do not log
+        trainer.log_images = True
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader, gt_depths = build_loaders(opt, extra["splits_dir"], rank, world, seed=extra["seed"],
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],
@@ -149,6 +157,7 @@ def main(argv=None):
         trainer.train(train_loader, val_loader)
         write_summary(trainer, train_loader, rank)
     finally:
+        trainer.close()
         train_loader.close()
         if val_loader is not None:
             val_loader.close()

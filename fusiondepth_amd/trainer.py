@@ -192,6 +192,11 @@ class Trainer:
         if verbose and rank == 0:
             self._announce()
 
+    # ---- the image summaries of trainer.py:656-681 (log_pictures); off unless a caller sets the switch ----
+    log_images = False         # every log event of run_epoch also renders the pictures of the batch that was due (log_images.py)
+    image_sink = None          # callable (mode, step, sheets, tiles); None: log_images.PngSink(log_path), made at the first event
+    _last_val_io = None        # (inputs, outputs) of the last validation batch, kept only while log_images is on
+
     # ---- the steps of __init__ that the sibling drivers of the reference (completor.py, refiner.py) take differently ----
     _SI_CONSTANTS = {}         # FD.PhotoOptions' si_* keywords where they are not the trainer's
 
@@ -389,10 +394,19 @@ class Trainer:
             self.num_total_steps = 0
         if self.rank == 0:
             self.save_opts()
-        for self.epoch in range(self.opt.num_epochs):
-            self.run_epoch()
-            if (self.epoch + 1) % self.opt.save_frequency == 0 and self.rank == 0:
-                self.save_model()
+        try:
+            for self.epoch in range(self.opt.num_epochs):
+                self.run_epoch()
+                if (self.epoch + 1) % self.opt.save_frequency == 0 and self.rank == 0:
+                    self.save_model()
+        finally:
+            self.close()                        # the pictures handed to the sink's thread are on disk when train returns
+
+    def close(self):
+        """Wait for the image sink's background thread (``log_images.PngSink.join``); nothing else is held open."""
+        join = getattr(self.image_sink, "join", None)
+        if join is not None:
+            join()
 
     def _log_due(self, batch_idx, step):
         """trainer.py:252-254: every log_frequency batches during the first 2000 steps, then every 2000 steps."""
@@ -426,8 +440,13 @@ class Trainer:
                     last_out = Outputs.for_options(self.opt, {("disp", 0): outputs[("disp", 0)][-n:]})
                     self.compute_depth_losses(last_in, last_out, losses)
                 self.log("train", losses)
+                if self.log_images:
+                    self.log_pictures("train", stacked, outputs)
                 if getattr(self, "val_loader", None) is not None:
                     self.log("val", self.val_losses(self.val_loader))
+                    if self.log_images and self._last_val_io is not None:
+                        self.log_pictures("val", *self._last_val_io, val=True)
+                        self._last_val_io = None
                     self.set_train()
         self.lr_scheduler_step()
 
@@ -446,8 +465,9 @@ class Trainer:
         self.last_log_time = dict(epoch=self.epoch, batch=batch_idx, examples_per_s=samples_per_sec, loss=loss)
 
     def log(self, mode, losses):
-        """trainer.py:644-681 without tensorboard / wandb: one JSON line per event in ``<log_path>/<mode>/scalars.jsonl``
-        (the image summaries are not written; ``outputs`` keeps everything they were made from)."""
+        """trainer.py:644-655 without tensorboard / wandb: one JSON line per event in ``<log_path>/<mode>/scalars.jsonl``.  The
+        image summaries of trainer.py:656-681 go through ``log_pictures``, which ``run_epoch`` calls beside this when
+        ``log_images`` is set."""
         folder = os.path.join(self.log_path, mode)
         os.makedirs(folder, exist_ok=True)
         rec = {"step": self.step, "epoch": self.epoch, "lr": self.lr}
@@ -455,6 +475,49 @@ class Trainer:
             rec[k] = float(v)
         with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
             f.write(json.dumps(rec) + "\n")
+
+    def log_pictures(self, mode, inputs, outputs, val=False):
+        """trainer.py:656-681: the image summaries of one log event, rendered on the device by one ``fd_log_sheets`` call
+        (log_images.render) and handed to ``image_sink(mode, step, sheets, tiles)``.
+
+        Items ``j < min(4, opt.eval_batch_size, n)`` of the batch that was due are drawn - ``min(4, eval_batch_size)`` is the
+        reference's own bound (trainer.py:656), ``n`` the size of that batch: for a training event the window's last micro-batch,
+        the ``[-n:]`` slice ``run_epoch`` scores; for a validation event (``val``: frame 0 only, no mask tiles, as trainer.py:678)
+        the whole batch.  One contact sheet per item: the input colours per frame and scale, the warped colour predictions of scale
+        0, the normalised disparities, the automask or the predictive masks.  Nothing here draws a random number or touches the
+        training state.
+
+        ``image_sink``: None makes a ``log_images.PngSink`` at the first event - ``<log_path>/<mode>/images/{step:07d}_{j}.png``,
+        one sheet per item, PIL-encoded on one background thread that ``train`` and ``close`` join.  For tensorboard or wandb set a
+        callable of your own: ``tiles`` maps the reference's tags ("color_-1_0/2", "disp_3/1", "automask_0/0", ...) to [h,w,3]
+        uint8 views, so ``for tag, tile in tiles.items(): writer.add_image(tag, tile, step, dataformats="HWC")`` is the
+        reference's event.  tensorboard is not a dependency and is not imported."""
+        from . import log_images
+        opt = self.opt
+        B = inputs[("color", 0, 0)].shape[0]
+        n = B if val or not self.stack_microbatches else B // self.accumulate_step
+        J = min(4, opt.eval_batch_size, n)
+        frame_ids = [0] if val else list(opt.frame_ids)
+        Ts = {}
+        with torch.no_grad():
+            for f in frame_ids[1:]:
+                if f == "s":
+                    Ts[f] = inputs["stereo_T"]
+                elif opt.pose_model_type == "posecnn":          # generate_images_pred's matrix for scale 0 (trainer.py:450-460)
+                    disp = outputs[("disp", 0)].detach()
+                    if not opt.v1_multiscale and tuple(disp.shape[2:]) != (opt.height, opt.width):
+                        disp = FD.bilinear_upsample(disp, (opt.height, opt.width))
+                    mean_inv_depth = FD.spatial_mean(disp_to_depth(disp, opt.min_depth, opt.max_depth)[0], 1.0)
+                    Ts[f] = transformation_from_parameters(outputs[("axisangle", 0, f)][:, 0].detach(),
+                                                           outputs[("translation", 0, f)][:, 0].detach() * mean_inv_depth[:, None, :], f < 0)
+                else:
+                    Ts[f] = outputs[("cam_T_cam", 0, f)]
+            sheets, tiles = log_images.render(inputs, outputs, frame_ids, opt.scales, J, Ts=Ts, first=B - n,
+                                              automask=not opt.disable_automasking, predictive_mask=bool(opt.predictive_mask), val=val,
+                                              min_depth=opt.min_depth, max_depth=opt.max_depth, v1_multiscale=bool(opt.v1_multiscale))
+        if self.image_sink is None:
+            self.image_sink = log_images.PngSink(self.log_path)
+        self.image_sink(mode, self.step, sheets, tiles)
 
     # ------------------------------------------------------------------------------------------------
     def train_step_graphed(self, micro_batches):
@@ -1000,6 +1063,8 @@ class Trainer:
                 if "depth_gt" in inputs:
                     self.compute_depth_losses(inputs, outputs, losses, accumulate=True)
                 n += 1
+                if self.log_images:
+                    self._last_val_io = (inputs, outputs)
         for m in self.depth_metric_names:
             losses[m] /= max(n, 1)
         self.set_train()
@@ -1021,6 +1086,8 @@ class Trainer:
                     raise ValueError("Trainer.val_metrics: the loader yields more images than val_gt has maps (%d)" % len(gt))
                 self._val_depths[at:at + B].copy_(depth[:, 0])
                 at += B
+                if self.log_images:
+                    self._last_val_io = (inputs, outputs)
             if at != len(gt):
                 raise ValueError("Trainer.val_metrics: the loader yielded %d images for the %d maps of val_gt" % (at, len(gt)))
             rows = gt.score(self._val_depths).cpu().numpy()          # the one download

@@ -50,7 +50,8 @@ extern "C" {
  *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores).
  *    Likewise the per-class Eigen-split scorer (fd_eigen_class_scores_ws_bytes, fd_eigen_class_scores, fd_class_errors; it reuses
  *    struct fd_eigen_desc, and the workspace sizes of the three scorers above are what they were).
- *    Likewise the renderer of evaluate_depth --visualize (fd_vis_render_ws_bytes, fd_vis_render; it reuses struct fd_eigen_desc). */
+ *    Likewise the renderer of evaluate_depth --visualize (fd_vis_render_ws_bytes, fd_vis_render; it reuses struct fd_eigen_desc).
+ *    Likewise the trainer's image summaries (fd_log_sheets_ws_bytes, fd_log_sheets, struct fd_log_tile, struct fd_log_cfg). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -972,6 +973,48 @@ int fd_vis_render(const float* disp, int M, int h, int w, float pred_scale, cons
                   const float* packed_gt, long packed_floats, const fd_eigen_desc* desc, int N, long max_pixels, float gt_lo, float gt_hi,
                   const unsigned char* lut_disp, const unsigned char* lut_err, unsigned char* color, unsigned char* err, long err_pixels,
                   float* stats /*[N][2]*/, float* depth_out, void* ws, void* stream);
+
+/* ------------------------------------------------------------------ train --log_images --
+ * The image summaries of trainer.py:656-681 for J <= 64 items of a batch: one uint8 RGB contact sheet [Hs][Ws][3] per item, J sheets
+ * back to back, in two launches and one memset whatever J, the number of scales and the number of frames are (csrc/log_images.hip).
+ *   A sheet is a stack of row blocks (one per scale); a row block holds tiles side by side, each with its top edge on the block's.
+ *   Every byte of every sheet is written by the call: a pixel in no tile is 0.  The tile table holds J * NT entries, item-major; the
+ *   geometry (kind, y, x, h, w, aux, slot) of tile i is the same for every item, the pointers are the item's own.
+ *   kind 0 colour      p0 = float [3][h][w]                                   -> q(r), q(g), q(b)
+ *   kind 1 prediction  p0 = the source frame's colours [3][h][w], p1 = the disparity [h][w] of scale 0, p2 = K, p3 = inv_K, p4 = T
+ *                      (float [4][4] each): depth = 1 / (lo + span * disp), X = depth * inv_K[:3,:3] (x, y, 1), pix = P X / ((P X)_z + eps)
+ *                      with P = (K T)[:3], then F.grid_sample(bilinear, border, align_corners=False) of the colours - the steps and the
+ *                      conventions of fd_photo_fwd_ex, restated.  h, w >= 2.
+ *   kind 2 disparity   p0 = float [h][w]: utils.normalize_image - ma, mi the plane's float32 maximum and minimum,
+ *                      d = (float)((double)ma - (double)mi), 1e5 where ma == mi, the pixel q((x - mi) / d) with an IEEE division; a NaN
+ *                      anywhere in the plane makes every pixel 0 (torch's max() is NaN then).  slot = the tile's rank among the item's
+ *                      disparity tiles; cfg.disp_tile[slot] = its index.
+ *   kind 3 automask    p0 = uint8 [h][w], the argmin index fd_photo_*_fwd leaves in `sel`: 255 where index > aux - 1, else 0.
+ *   kind 4 mask        p0 = float [h][w] -> q(x).
+ *   Single-channel kinds fill the three channels alike.  q(x) = trunc(min(max(x * 255.0f, 0), 255)), NaN -> 0, in float32.
+ *   ws: fd_log_sheets_ws_bytes(J, n_disp) bytes, 16-byte aligned (0: out of range).  After the call it holds, per item and disparity
+ *   tile, four uint32: key(ma), ~key(mi), 1 if a NaN was seen, 0 - key(v) = bits ^ 0xffffffff for a negative v, bits | 0x80000000 else.
+ *   tiles_host: the same table in host memory; its geometry is checked against cfg before anything is launched. */
+typedef struct fd_log_tile {
+    const void* p0; const void* p1; const void* p2; const void* p3; const void* p4;
+    int kind, y, x, h, w;            /* the tile's place in the sheet */
+    int aux;                         /* kind 3: the number of identity losses */
+    int slot;                        /* kind 2: rank among the item's disparity tiles */
+    int reserved;
+} fd_log_tile;
+typedef struct fd_log_cfg {
+    int Hs, Ws;                      /* the sheet */
+    int n_rows, n_disp;              /* row blocks (<= 8), disparity tiles per item (<= 8) */
+    int row_y[8], row_h[8];          /* a row block's top edge and height; the blocks follow each other down the sheet */
+    int row_first[8], row_count[8];  /* its tiles, left to right: row_first[0] = 0, row_first[r + 1] = row_first[r] + row_count[r] */
+    int disp_tile[8];                /* the index of the item's k-th disparity tile */
+    float lo, span;                  /* (float)(1 / max_depth), (float)(1 / min_depth - 1 / max_depth): disp_to_depth */
+    float eps;                       /* Project3D's 1e-7 */
+    int reserved;
+} fd_log_cfg;
+long fd_log_sheets_ws_bytes(int J, int n_disp);
+int fd_log_sheets(const fd_log_tile* tiles_host, const fd_log_tile* tiles_dev, int J, int NT, const fd_log_cfg* cfg, unsigned char* sheets,
+                  void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py --step completion_val [--reps 5] [--out profiles/completion_val_time.log]
     python scripts/bench_eval.py --step semantic [--reps 10] [--out profiles/eigen_class_time.log]
     python scripts/bench_eval.py --step visualize [--reps 10] [--out profiles/visualize_time.log]
+    python scripts/bench_eval.py --step log_images [--reps 10] [--out profiles/log_images_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -49,7 +50,16 @@ packing, uploads of ground truth and labels, the call, one download) against the
 ``FD.resize_linear_cv``, ``torch.sort`` for the percentile, a gather per table and ``max_pool2d`` - alternating in one run after the two
 were compared byte for byte.  Per N: the library call alone between device events with its traffic bound (the source and the ground
 truth read once, the pictures written once), the recipe's device part, both end to end with their downloads as wall time, and - for
-orientation, once - the reference's host code for the colour picture (``np.percentile``, ``Normalize``, ``magma``) on 16 threads."""
+orientation, once - the reference's host code for the colour picture (``np.percentile``, ``Normalize``, ``magma``) on 16 threads.
+
+``--step log_images``: the image summaries of ``train --log_images``, ``log_images.render`` (fd_log_sheets, csrc/log_images.hip), at the
+shape of a real run - 192x640, scales 0-3, frames [0, -1, 1], automask on - for J = 1 (the default ``eval_batch_size``) and J = 4 items,
+against the ATen recipe it replaces: per tile a multiply, clamp, cast, permute and copy into the sheet, ``FD.bilinear_upsample`` of the
+disparity, ``disp_to_depth``, back-projection, projection and ``F.grid_sample`` per source frame, a max and a min per disparity.  The two
+alternate in one run after their sheets were compared (byte for byte outside the colour predictions, within one level inside).  Per J:
+the library call alone between device events with its traffic bound (every source read once, the disparities twice, the sheets written
+once), the recipe's device part, both end to end with their download as wall time - what a log event holds the step loop for - and
+the PNG encoding of one sheet, which the default sink does on its background thread."""
 import argparse
 import os
 import sys
@@ -309,6 +319,124 @@ def visualize_step(a):
     return lines
 
 
+def log_images_step(a):
+    import ctypes
+    import torch.nn.functional as F
+    from fusiondepth_amd import log_images as L
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.layers import disp_to_depth
+    H, W, B = 192, 640, 4
+    frame_ids, scales = [0, -1, 1], [0, 1, 2, 3]
+    inputs_ = synthetic.make_scene_batch(B, H, W, frame_ids=frame_ids, seed=5)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(6)
+    outputs = {}
+    for s in scales:
+        coarse = torch.rand(B, 1, 6, 20, device="cuda", generator=gen)
+        outputs[("disp", s)] = (0.02 + 0.6 * F.interpolate(coarse, size=(H >> s, W >> s), mode="bilinear", align_corners=False)).contiguous()
+        outputs[("sel", s)] = (torch.randint(0, 4, (B, H, W), device="cuda", dtype=torch.uint8, generator=gen), 2)
+    Ts = {f: inputs_[("T_gt", f)].contiguous() for f in frame_ids[1:]}
+    K, inv_K = inputs_[("K", 0)], inputs_[("inv_K", 0)]
+    lines = ["train --log_images, %dx%d, scales 0-3, frames [0, -1, 1], automask: one contact sheet per item; median of %d (min, max) after "
+             "one warm-up round, renderer and recipe alternating" % (H, W, a.reps)]
+
+    def q8(x):
+        return (x * 255.0).clamp_(0, 255).to(torch.uint8)
+
+    for J in (1, 4):
+        lay = L.layout(frame_ids, scales, H, W, J=J)
+        per = len(lay.tiles) // J
+
+        def recipe_device():
+            """The sheets from what the package offered before: a few small ATen launches per tile."""
+            sheets = torch.zeros((J, lay.Hs, lay.Ws, 3), device="cuda", dtype=torch.uint8)
+            disp0 = FD.bilinear_upsample(outputs[("disp", 0)][:J], (H, W))
+            depth = disp_to_depth(disp0, 0.1, 100.0)[1]
+            cam = FD.backproject_depth(depth, inv_K[:J])
+            pred = {f: F.grid_sample(inputs_[("color", f, 0)][:J], FD.project_3d(cam, K[:J], Ts[f][:J], H, W, 1e-7), padding_mode="border",
+                                     align_corners=False) for f in frame_ids[1:]}
+            for t in lay.tiles:
+                j = t.item
+                if t.kind == L.KIND_COLOR:
+                    tile = q8(inputs_[("color", t.frame, t.scale)][j]).permute(1, 2, 0)
+                elif t.kind == L.KIND_PRED:
+                    tile = q8(pred[t.frame][j]).permute(1, 2, 0)
+                elif t.kind == L.KIND_DISP:
+                    x = outputs[("disp", t.scale)][j, 0]
+                    ma, mi = x.max(), x.min()
+                    d = torch.where(ma == mi, torch.full_like(ma, 1e5), (ma.double() - mi.double()).float())
+                    tile = q8((x - mi) / d)[:, :, None]
+                else:
+                    sel, n_id = outputs[("sel", t.scale)]
+                    tile = q8((sel[j] > n_id - 1).float())[:, :, None]
+                sheets[j, t.y:t.y + t.h, t.x:t.x + t.w] = tile
+            return sheets
+
+        def recipe_all():
+            with torch.no_grad():
+                return recipe_device().cpu().numpy()
+
+        def render_all():
+            return L.render(inputs_, outputs, frame_ids, scales, J, Ts=Ts)
+
+        # the resident call: the table render builds, kept on the device
+        key = (tuple(frame_ids), tuple(scales), H, W, J, True, False, False, (H, W))
+        _, cfg, template, NT = L._plan(key, 0.1, 100.0)
+        table = type(template)()
+        ctypes.memmove(table, template, ctypes.sizeof(table))
+        for j in range(J):
+            for i, t in enumerate(lay.tiles[:per]):
+                e = table[j * NT + i]
+                if t.kind in (L.KIND_COLOR, L.KIND_PRED):
+                    e.p0 = inputs_[("color", t.frame, t.scale)][j].data_ptr()
+                if t.kind == L.KIND_PRED:
+                    e.p1, e.p2, e.p3, e.p4 = outputs[("disp", 0)][j].data_ptr(), K[j].data_ptr(), inv_K[j].data_ptr(), Ts[t.frame][j].data_ptr()
+                elif t.kind == L.KIND_DISP:
+                    e.p0 = outputs[("disp", t.scale)][j].data_ptr()
+                elif t.kind == L.KIND_AUTOMASK:
+                    e.p0, e.aux = outputs[("sel", t.scale)][0][j].data_ptr(), 2
+        table_d = torch.from_numpy(np.frombuffer(table, dtype=np.uint8).copy()).cuda()
+        ws = torch.empty((query("fd_log_sheets_ws_bytes", J, cfg.n_disp),), device="cuda", dtype=torch.uint8)
+        out = torch.empty((J, lay.Hs, lay.Ws, 3), device="cuda", dtype=torch.uint8)
+
+        def kernel():
+            call("fd_log_sheets", ctypes.addressof(table), table_d.data_ptr(), J, NT, ctypes.addressof(cfg), out.data_ptr(), ws.data_ptr(), stream())
+
+        got, want = render_all()[0], recipe_all()                # the same pictures before anything is timed
+        kernel()
+        assert np.array_equal(out.cpu().numpy(), got), "the resident call and render disagree"
+        warp_diff = 0
+        for t in lay.tiles:
+            g, w_ = got[t.item, t.y:t.y + t.h, t.x:t.x + t.w], want[t.item, t.y:t.y + t.h, t.x:t.x + t.w]
+            if t.kind == L.KIND_PRED:
+                d = np.abs(g.astype(np.int32) - w_.astype(np.int32))
+                assert d.max() <= 1, "renderer and recipe disagree at %s" % t.tag
+                warp_diff = max(warp_diff, float((d != 0).mean()))
+                want[t.item, t.y:t.y + t.h, t.x:t.x + t.w] = g
+        assert np.array_equal(got, want), "renderer and recipe disagree outside the colour predictions"
+        t_k, t_rd = alternate([kernel, recipe_device], a.reps, _event_ms)
+        t_e, t_r = alternate([render_all, recipe_all], a.reps, _wall_ms)
+        with tempfile.TemporaryDirectory() as tmp:
+            t0 = time.perf_counter()
+            L.write_png(os.path.join(tmp, "sheet.png"), got[0])
+            t_png = 1e3 * (time.perf_counter() - t0)
+        read = 0
+        for t in lay.tiles:
+            read += {L.KIND_COLOR: 12, L.KIND_PRED: 16, L.KIND_DISP: 8, L.KIND_AUTOMASK: 1}[t.kind] * t.h * t.w
+        bound = read + out.numel()
+        t_bound = 1e3 * bound / HBM
+        lines.append("  J = %d (%d tiles, sheets %dx%d): fd_log_sheets, resident (2 launches + 1 memset): %.3f ms (%.3f, %.3f); traffic bound (sources "
+                     "read once, disparities twice, sheets written once) %.2f MB = %.2f us at 6.3 TB/s -> %.1fx the bound; the recipe's device "
+                     "part: %.3f ms (%.3f, %.3f) -> %.2fx; colour-prediction bytes that differ from the recipe's grid_sample: %.5f"
+                     % (J, len(lay.tiles), lay.Hs, lay.Ws, t_k[0], t_k[1], t_k[2], bound / 1e6, 1e3 * t_bound, t_k[0] / t_bound, t_rd[0], t_rd[1],
+                        t_rd[2], t_rd[0] / t_k[0], warp_diff))
+        lines.append("          render end to end (checks, table upload, 1 call, pinned download of %.1f MB) = what a log event holds the step loop for: "
+                     "%.2f ms (%.2f, %.2f); recipe end to end (one download): %.2f ms (%.2f, %.2f) -> %.2fx; PNG encoding of one sheet "
+                     "(PIL, the sink's background thread): %.1f ms"
+                     % (out.numel() / 1e6, t_e[0], t_e[1], t_e[2], t_r[0], t_r[1], t_r[2], t_r[0] / t_e[0], t_png))
+    return lines
+
+
 def semantic_step(a):
     K = 34
     rng = np.random.RandomState(5)
@@ -498,16 +626,17 @@ def completion_val_step(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize", "log_images"), default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
                                                 "val": "val_time.log", "completion_val": "completion_val_time.log",
-                                                "semantic": "eigen_class_time.log", "visualize": "visualize_time.log"}[a.step])
-    if a.step in ("detection", "val", "completion_val", "semantic", "visualize"):
+                                                "semantic": "eigen_class_time.log", "visualize": "visualize_time.log",
+                                                "log_images": "log_images_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val", "semantic", "visualize", "log_images"):
         text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step,
-                          "semantic": semantic_step, "visualize": visualize_step}[a.step](a))
+                          "semantic": semantic_step, "visualize": visualize_step, "log_images": log_images_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
