@@ -139,9 +139,6 @@ SIGNATURES = {
     "fd_photo_ms_ws_floats": ("p", "l"),
     "fd_photo_ms_fwd": ("p" * 14, "i"),
     "fd_photo_ms_bwd": ("p" * 11, "i"),
-    "fd_photo_msn_ws_floats": ("p", "l"),
-    "fd_photo_msn_fwd": ("p" * 14, "i"),
-    "fd_photo_msn_bwd": ("p" * 11, "i"),
     "fd_smooth_ws_floats": ("iii", "l"),
     "fd_smooth_fwd": ("ppppiiiip", "i"),
     "fd_smooth_bwd": ("pppppiiiip", "i"),

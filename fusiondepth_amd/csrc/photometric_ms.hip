@@ -15,8 +15,8 @@
 //     three-row ring in registers;
 //   * each pixel of a strip is warped ONCE per scale and frame (halo overhead 64/60 * (R+4)/R instead of the 1.33x re-warp of
 //     the 16x64 tiles, and no second warp in a separate backward kernel);
-//   * the two source frames of a strip run in the two waves of a 128-thread workgroup (half the live ring state per wave);
-//     they exchange one loss value per pixel row through LDS for the 4-way argmin;
+//   * the source frames of a strip run in the waves of one workgroup, ONE WAVE PER SOURCE FRAME (64 * NF threads; half the live
+//     ring state per wave at NF = 2); they exchange one loss value per pixel row through LDS for the argmin;
 //   * the gradient w.r.t. the upsampled disparity for a unit upstream gradient (d mean / d disp_up) and the projection-matrix
 //     gradients are produced in the same pass, two rows behind the warp front; the backward entry point only scales them by
 //     the incoming gradients, adds the sparse LiDAR term and runs the adjoint of the bilinear upsampling;
@@ -25,6 +25,24 @@
 //     (scripts/ssim_formulation_error.py).
 // HBM-bound by design (169.2 B/pixel forward + 174.5 backward over the 4 scales); what bounds it in practice is
 // the ~800 VALU lane-instructions per pixel and scale that remain.
+//
+// The number of source frames NF is a template parameter, 1 to 3.  Two frames (-1, +1) is the default configuration and what the
+// headline benchmark times; --use_stereo adds the stereo partner "s" (trainer.py:63-64, 436-447): frame_ids [0, "s"] has one
+// source frame, [0, -1, 1, "s"] three.  To the loss "s" is a frame like any other; its pose is the fixed stereo_T, which arrives
+// here as one more projection matrix P.
+//   * each wave streams its frame down the strip and holds its own lagged-row ring in LDS (12 KB per frame, 36 KB at NF = 3);
+//   * per pixel row the waves exchange one (reprojection, identity) candidate pair through LDS; every wave evaluates the same
+//     minimum over the 2 NF candidates in the order of torch.min over cat(identity_0.., reprojection_0..) - the first minimum
+//     wins - and learns whether its own frame won.  NF = 1 exchanges nothing and has no barrier in its row loop;
+//   * the depth gradient of a pixel is the sum of the frames' contributions (only the frame that won a pixel contributes
+//     through that pixel): waves 1.. hand theirs to wave 0 through LDS, wave 0 adds them in frame order and stores;
+//   * wave 0 accumulates the minimum and writes `sel`; the LiDAR term runs in wave 1 (wave 0 when NF = 1).
+// The two-frame instantiation is tuned instruction by instruction.  Where the general N-frame text does not compile to the same
+// instructions and registers, an `if constexpr (NF == 2)` arm keeps the two-frame text: section D of the row loop (the pairwise
+// argmin, the single hand-off slot, the LiDAR wave in the `else` of wave 0), the last hand-off after the loop, and a never-taken
+// arm that pins the register allocation.  The LiDAR row is spelled out in both arms of section D: as a helper that takes the
+// accumulators by reference it puts them into scratch memory.
+// All sums are in a fixed order (shuffle trees, then k_photo_ms_fin): no atomics, the same bits on every run.
 #include "../../include/fdhip.h"
 #include "fd_common.h"
 
@@ -54,23 +72,14 @@ __device__ __forceinline__ int refl_clamp(int i, int n) {
 // gfx950 issues fp32 add / mul / fma / mov on VGPR, inline-constant or literal operands at twice the rate of everything else
 // (scripts/ubench/valu_rate2.hip: 2.6-2.9 vs 4.3-5.0 cycles per wave-instruction); ANY SGPR operand, and min / max / med3 /
 // cmp / floor / cvt / shifts, are on the slow side.  Wave-uniform constants of the hot loop are therefore kept in VGPRs.
-#ifndef FD_MS_EXACT_GRID
-#define FD_MS_EXACT_GRID 0   // 1: normalise / unnormalise the sampling grid with the reference's operation sequence
-#endif
-#ifndef FD_MS_VCONST
-#define FD_MS_VCONST 1
-#endif
-#ifndef FD_MS_PREFETCH
-#define FD_MS_PREFETCH 1
-#endif
 __device__ __forceinline__ float vreg(float s) {
     float v = s;
-    if (FD_MS_VCONST) asm volatile("" : "+v"(v));
+    asm volatile("" : "+v"(v));
     return v;
 }
 __device__ __forceinline__ int vreg(int s) {
     int v = s;
-    if (FD_MS_VCONST) asm volatile("" : "+v"(v));
+    asm volatile("" : "+v"(v));
     return v;
 }
 __device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
@@ -78,7 +87,7 @@ __device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t r, int voff, int soff
 }
 
 struct MsArgs {
-    fd_photo_cfg cfg;        // B, H, W, NF (= 2), depth range, SI parameters, groups (Hs / Ws unused)
+    fd_photo_cfg cfg;        // B, H, W, NF (1..3), depth range, SI parameters, groups (Hs / Ws unused)
     int S, R;                // scales, rows per strip
     float lo, span;          // 1 / max_depth, 1 / min_depth - 1 / max_depth (host doubles -> float, as the reference's python floats)
     int Hs[4], Ws[4];
@@ -86,12 +95,12 @@ struct MsArgs {
     int nx, ny;              // strips per image along x / y
     unsigned beam_mask;      // bit s: scale s carries the LiDAR term
     const float* disp[4];
-    const float* noise[4];   // [B,2,H,W] each, or NULL
-    const float* inv_K; const float* P; const float* src[2]; const float* target; const float* ident; const float* beam;
+    const float* noise[4];   // [B,NF,H,W] each, or NULL
+    const float* inv_K; const float* P; const float* src[3]; const float* target; const float* ident; const float* beam;
     uint8_t* sel;            // [S,B,H,W]
     float* d1;               // [S,B,H,W]   d to_optimise.mean() / d disp_up (unit upstream gradient)
     float* part;             // [nblk][4]   sum(min), n_valid, sum(d), sum(d^2)
-    float* gpart;            // [nblk][2][12]
+    float* gpart;            // [nblk][NF][12]
 };
 
 // Lagged row data (written when a row is warped, read two rows later by the gradient stage) lives in LDS, 16 floats per
@@ -107,14 +116,15 @@ struct Pre {
     float idv, nzv, bdv;        // identity candidate / noise / LiDAR value of the row ABOVE (consumed in the same step)
 };
 
-template <bool IDENT, bool GRAD>
-__global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
-    __shared__ float xl[2][2][2][64];        // [row parity][frame][loss | identity candidate][lane]
-    __shared__ float xd[2][64];              // [row parity][lane]   frame-1 depth gradient
-    __shared__ float4 lagr[2][3][4][64];     // [frame][row % 3][group][lane]
+template <int NF, bool IDENT, bool GRAD>
+__global__ void __launch_bounds__(64 * NF, FD_MS_WAVES) k_photo_ms(MsArgs a) {
+    constexpr int FB = NF > 1 ? 1 : 0;       // the wave that carries the LiDAR term
+    __shared__ float xl[2][NF][2][64];       // [row parity][frame][loss | identity candidate][lane]
+    __shared__ float xd[2][NF > 1 ? NF - 1 : 1][64];   // [row parity][frame - 1][lane]   depth gradient of frames 1..
+    __shared__ float4 lagr[NF][3][4][64];    // [frame][row % 3][group][lane]
     const fd_photo_cfg& cfg = a.cfg;
     const int lane = threadIdx.x & 63;
-    const int f = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int f = NF > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
     const int B = cfg.B, H = cfg.H, W = cfg.W;
     // 1-D grid, XCD-aware: workgroup L runs on XCD L % 8 (observed dispatch rule, used for speed only).  The S scales of one strip
     // read the same target / source / identity rows, so they get consecutive slots of ONE XCD - L = 8 S q + 8 s + r is scale s of
@@ -122,7 +132,9 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     const int L = blockIdx.x;
     const int q8 = L / (8 * a.S), r8 = L - q8 * (8 * a.S);
     const int s = r8 >> 3, strip = q8 * 8 + (r8 & 7);
-    if (strip >= B * a.ny * a.nx) return;                    // padding of the last group of 8 strips (whole workgroup)
+    // padding of the last group of 8 strips.  Workgroup-uniform (it depends on blockIdx alone) and ahead of every barrier: all
+    // waves of a workgroup leave here together, or none does.
+    if (strip >= B * a.ny * a.nx) return;
     const int b = strip / (a.ny * a.nx);
     const int by = (strip - b * a.ny * a.nx) / a.nx, bx = strip - (b * a.ny + by) * a.nx;
     const int P = H * W;
@@ -143,7 +155,7 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     const float* iK = a.inv_K + b * 16;
     const float rayx0 = iK[0] * (float)gx + iK[2], rayx1 = iK[4] * (float)gx + iK[6], rayx2 = iK[8] * (float)gx + iK[10];
     const float iky0 = vreg(iK[1]), iky1 = vreg(iK[5]), iky2 = vreg(iK[9]);
-    const float* Pf = a.P + ((long)b * 2 + f) * 12;
+    const float* Pf = a.P + ((long)b * NF + f) * 12;
     float Pm[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Pm[k] = vreg(Pf[k]);
@@ -176,8 +188,8 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     const __amdgpu_buffer_rsrc_t r_tgt = fd_make_rsrc(a.target + (long)b * 3 * P);
     const __amdgpu_buffer_rsrc_t r_disp = fd_make_rsrc(a.disp[s] + (long)b * Hs * Ws);
     const bool has_noise = IDENT && a.noise[s];
-    const __amdgpu_buffer_rsrc_t r_id = fd_make_rsrc(IDENT ? a.ident + ((long)b * 2 + f) * P : a.target);
-    const __amdgpu_buffer_rsrc_t r_nz = fd_make_rsrc(has_noise ? a.noise[s] + ((long)b * 2 + f) * P : a.target);
+    const __amdgpu_buffer_rsrc_t r_id = fd_make_rsrc(IDENT ? a.ident + ((long)b * NF + f) * P : a.target);
+    const __amdgpu_buffer_rsrc_t r_nz = fd_make_rsrc(has_noise ? a.noise[s] + ((long)b * NF + f) * P : a.target);
     const __amdgpu_buffer_rsrc_t r_beam = fd_make_rsrc(has_beam ? a.beam + (long)b * P : a.target);
     const __amdgpu_buffer_rsrc_t r_sel = fd_make_rsrc(a.sel + ((long)s * B + b) * P);
     const __amdgpu_buffer_rsrc_t r_d1 = fd_make_rsrc(GRAD ? a.d1 + ((long)s * B + b) * P : a.part);
@@ -198,7 +210,7 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     float gP[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) gP[k] = 0.f;
-    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;   // wave 0: sum(min); wave 1: n_valid, sum(d), sum(d^2)
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;   // wave 0: sum(min); wave FB: n_valid, sum(d), sum(d^2)
     float pend = 0.f, pend_k = 0.f;                           // wave 0: its own depth gradient of the row in flight
     Pre pre[2];
     float dtap[2][5];                                         // disparity taps + row weight, issued two rows ahead
@@ -244,7 +256,7 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         p.idv = 0.f; p.nzv = 0.f; p.bdv = 0.f;
         if (IDENT) p.idv = ld(r_id, cxc4, o1);
         if (has_noise) p.nzv = ld(r_nz, cxc4, o1);
-        if (has_beam && f == 1) p.bdv = ld(r_beam, cxc4, o1);
+        if (has_beam && f == FB) p.bdv = ld(r_beam, cxc4, o1);
         float dup;
         if (same) {
             dup = da[0];
@@ -267,12 +279,7 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         u = fmaf(fmaf(-u, den, c0), rc, u);
         v = fmaf(fmaf(-v, den, c1), rc, v);
         // layers.py:224-226 + aten grid_sampler unnormalize (align_corners=False): ((2(u/(W-1) - .5) + 1) W - 1) / 2
-#if FD_MS_EXACT_GRID
-        const float gxn = (u / (float)(W - 1) - 0.5f) * 2.0f, gyn = (v / (float)(H - 1) - 0.5f) * 2.0f;
-        const float ix = ((gxn + 1.0f) * (float)W - 1.0f) * 0.5f, iy = ((gyn + 1.0f) * (float)H - 1.0f) * 0.5f;
-#else
         const float ix = fmaf(u, sWx, -0.5f), iy = fmaf(v, sHy, -0.5f);
-#endif
         const float ixc = __builtin_amdgcn_fmed3f(ix, 1e-30f, xmm), iyc = __builtin_amdgcn_fmed3f(iy, 1e-30f, ymm);
         const float kx = ixc == ix ? sWx : 0.f;                  // clip_coordinates_set_grad: borders count as outside
         const float ky = iyc == iy ? sHy : 0.f;
@@ -327,13 +334,16 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         if (GRAD) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) lagr[f][KC][k][lane] = lg.q[k];
-        } else if (GRAD) {
-            // never taken.  Naming acc3 here fixes the order in which this lambda captures the accumulators, and with it the
-            // register allocation: without the arm the same instructions come out on permuted registers.  Remove it in a change
-            // that is judged by a measurement, not by identical assembly.
-            acc3 += lg.q[0].x + lg.q[0].y + lg.q[0].z + lg.q[0].w + lg.q[1].x + lg.q[1].y + lg.q[3].y + lg.q[3].z + lg.q[3].w;
-        } else if (has_beam) {
-            lagr[f][KC][3][lane] = lg.q[3];
+        } else {
+            if constexpr (NF == 2) {
+                if (GRAD) {
+                    // never taken.  Naming acc3 here fixes the order in which this lambda captures the accumulators, and with it
+                    // the register allocation of the two-frame kernel: without the arm the same instructions come out on permuted
+                    // registers.  Remove it in a change that is judged by a measurement, not by identical assembly.
+                    acc3 += lg.q[0].x + lg.q[0].y + lg.q[0].z + lg.q[0].w + lg.q[1].x + lg.q[1].y + lg.q[3].y + lg.q[3].z + lg.q[3].w;
+                }
+            }
+            if (has_beam) lagr[f][KC][3][lane] = lg.q[3];
         }
         // vertical 3-sums of row i-1: (h[i-2] + h[i-1]) + h[i]
         float S[15];
@@ -377,50 +387,112 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         }
         const float Lown = fmaf(wS, ssum, wL * lsum1);           // trainer.py:476-488
         const float vown = IDENT ? fmaf(p.nzv, 0.00001f, p.idv) : 0.f;   // trainer.py:551-552
-        // ---- D: exchange with the other frame's wave, 4-way argmin (trainer.py:549-567) ------------------------------------
+        // ---- D: exchange with the other frames' waves, argmin over the 2 NF candidates (trainer.py:549-567) -------------------
+        // order of cat(identity_0 .. identity_{NF-1}, reprojection_0 .. reprojection_{NF-1}); the first minimum wins
         const int par = i & 1;
-        xl[par][f][0][lane] = Lown;
-        if (IDENT) xl[par][f][1][lane] = vown;
-        __syncthreads();
-        const float Loth = xl[par][1 - f][0][lane];
-        // order of cat(identity -1, identity +1, reprojection -1, reprojection +1); the first minimum wins
-        bool selown = f == 0 ? !(Loth < Lown) : (Lown < Loth);
-        float best = fminf(Lown, Loth);
-        float vmin = 0.f, voth = 0.f;
-        if (IDENT) {
-            voth = xl[par][1 - f][1][lane];
-            vmin = fminf(vown, voth);
-            selown = selown && (Lown < vmin);
-            best = fminf(best, vmin);
-        }
-        const bool rowown1 = i >= 3 && i < rows + 3;             // row index i-1 in [2, rows+2)
-        const bool own1 = rowown1 && colown;
-        if (f == 0) {
-            if (own1) {
-                acc0 += best;
-                int bi;
-                if (IDENT) bi = (vmin <= best) ? (voth < vown ? 1 : 0) : (selown ? 2 : 3);
-                else bi = selown ? 0 : 1;
-                __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bi, r_sel, cx, ry1 * W, 0);
+        bool selown;                                             // this wave's frame holds the minimum
+        if constexpr (NF == 2) {
+            // the tuned two-frame text: one candidate pair read, no index bookkeeping, one hand-off slot, and the LiDAR wave in
+            // the `else` of wave 0.  The general text below compiles to other instructions and registers at NF = 2.
+            xl[par][f][0][lane] = Lown;
+            if (IDENT) xl[par][f][1][lane] = vown;
+            __syncthreads();
+            const float Loth = xl[par][1 - f][0][lane];
+            selown = f == 0 ? !(Loth < Lown) : (Lown < Loth);
+            float best = fminf(Lown, Loth);
+            float vmin = 0.f, voth = 0.f;
+            if (IDENT) {
+                voth = xl[par][1 - f][1][lane];
+                vmin = fminf(vown, voth);
+                selown = selown && (Lown < vmin);
+                best = fminf(best, vmin);
             }
-            if (GRAD && i >= 5) {   // D1 of row i-3: this wave's part is in `pend`, frame 1's arrived through xd
-                const float other = xd[(i - 1) & 1][lane];
-                if (colown) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (pend + other) * pend_k), r_d1, cx * 4, (ry - 3) * W * 4, 0);
+            const bool rowown1 = i >= 3 && i < rows + 3;         // row index i-1 in [2, rows+2)
+            const bool own1 = rowown1 && colown;
+            if (f == 0) {
+                if (own1) {
+                    acc0 += best;
+                    int bi;
+                    if (IDENT) bi = (vmin <= best) ? (voth < vown ? 1 : 0) : (selown ? 2 : 3);
+                    else bi = selown ? 0 : 1;
+                    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bi, r_sel, cx, ry1 * W, 0);
+                }
+                if (GRAD && i >= 5) {   // D1 of row i-3: this wave's part is in `pend`, frame 1's arrived through xd
+                    const float other = xd[(i - 1) & 1][0][lane];
+                    if (colown) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (pend + other) * pend_k), r_d1, cx * 4, (ry - 3) * W * 4, 0);
+                }
+            } else if (has_beam) {                                  // trainer.py:577-589 / completor.py:718-723
+                const float dep1 = lagr[f][K1][3][lane].x;
+                const float d26 = dep1 * cfg.si_depth_scale;
+                const float bd = p.bdv * cfg.si_beam_scale;
+                bool m = own1 && bd > cfg.si_lo && d26 < 80.f && d26 > cfg.si_lo;
+                if (cfg.si_mode == 0) m = m && fabsf(d26 - bd) < cfg.si_threshold;
+                if (__any(m)) {
+                    if (m) {
+                        if (cfg.si_mode == 1) { acc1 += 1.f; acc2 += fabsf(d26 - bd); }
+                        else { const float d = logf(d26) - logf(bd); acc1 += 1.f; acc2 += d; acc3 += d * d; }
+                    }
+                }
             }
-        } else if (has_beam) {                                      // trainer.py:577-589 / completor.py:718-723
-            const float dep1 = lagr[f][K1][3][lane].x;
-            const float d26 = dep1 * cfg.si_depth_scale;
-            const float bd = p.bdv * cfg.si_beam_scale;
-            bool m = own1 && bd > cfg.si_lo && d26 < 80.f && d26 > cfg.si_lo;
-            if (cfg.si_mode == 0) m = m && fabsf(d26 - bd) < cfg.si_threshold;
-            if (__any(m)) {
-                if (m) {
-                    if (cfg.si_mode == 1) { acc1 += 1.f; acc2 += fabsf(d26 - bd); }
-                    else { const float d = logf(d26) - logf(bd); acc1 += 1.f; acc2 += d; acc3 += d * d; }
+        } else {
+            selown = true;
+            float best = Lown, vmin = vown;
+            int il = 0, iv = 0;                                  // first minimum among the reprojection / identity candidates
+            if (NF > 1) {
+                xl[par][f][0][lane] = Lown;
+                if (IDENT) xl[par][f][1][lane] = vown;
+                __syncthreads();
+                float Lj[NF], vj[NF];
+#pragma unroll
+                for (int j = 0; j < NF; ++j) {
+                    Lj[j] = xl[par][j][0][lane];
+                    vj[j] = IDENT ? xl[par][j][1][lane] : 0.f;
+                }
+                best = Lj[0]; vmin = vj[0];
+#pragma unroll
+                for (int j = 1; j < NF; ++j) {
+                    if (Lj[j] < best) { best = Lj[j]; il = j; }
+                    if (IDENT && vj[j] < vmin) { vmin = vj[j]; iv = j; }
+                }
+                selown = il == f;
+            }
+            const float lmin = best;
+            if (IDENT) {
+                selown = selown && (Lown < vmin);
+                best = fminf(best, vmin);
+            }
+            const bool rowown1 = i >= 3 && i < rows + 3;         // row index i-1 in [2, rows+2)
+            const bool own1 = rowown1 && colown;
+            if (f == 0) {
+                if (own1) {
+                    acc0 += best;
+                    int bi;
+                    if (IDENT) bi = (vmin <= lmin) ? iv : NF + il;
+                    else bi = il;
+                    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bi, r_sel, cx, ry1 * W, 0);
+                }
+                if (GRAD && i >= 5) {   // D1 of row i-3: this wave's part is in `pend`, the other frames' arrived through xd
+                    float tot = pend;
+#pragma unroll
+                    for (int j = 0; j < NF - 1; ++j) tot += xd[(i - 1) & 1][j][lane];
+                    if (colown) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, tot * pend_k), r_d1, cx * 4, (ry - 3) * W * 4, 0);
+                }
+            }
+            if (f == FB && has_beam) {                              // trainer.py:577-589 / completor.py:718-723
+                const float dep1 = lagr[f][K1][3][lane].x;
+                const float d26 = dep1 * cfg.si_depth_scale;
+                const float bd = p.bdv * cfg.si_beam_scale;
+                bool m = own1 && bd > cfg.si_lo && d26 < 80.f && d26 > cfg.si_lo;
+                if (cfg.si_mode == 0) m = m && fabsf(d26 - bd) < cfg.si_threshold;
+                if (__any(m)) {
+                    if (m) {
+                        if (cfg.si_mode == 1) { acc1 += 1.f; acc2 += fabsf(d26 - bd); }
+                        else { const float d = logf(d26) - logf(bd); acc1 += 1.f; acc2 += d; acc3 += d * d; }
+                    }
                 }
             }
         }
-        if (!GRAD) return;
+        if (!GRAD) return;      // a template parameter: uniform over the workgroup, and behind this row's only barrier
 
         // ---- E: mask the coefficients by the selection, horizontal 3-sums -----------------------------------------------------
         const bool act = selown && rowvalid1 && colvalid;
@@ -482,8 +554,8 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         if (f == 0) {
             pend = dd;
             pend_k = -l2.q[3].x * l2.q[3].x * span_s;
-        } else {
-            xd[par][lane] = dd;
+        } else if constexpr (NF > 1) {
+            xd[par][NF == 2 ? 0 : f - 1][lane] = dd;             // two frames: one slot, no index arithmetic
         }
     };
 
@@ -491,15 +563,12 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     for (int k = 0; k < 3; ++k)
 #pragma unroll
         for (int j = 0; j < 4; ++j) lagr[f][k][j][lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-#if FD_MS_PREFETCH
     load_disp(dtap[0], 0);
     load_disp(dtap[1], 1);
     issue(pre[0], dtap[0], 0);
-#endif
     // two rows per trip (the prefetch buffers alternate with compile-time indices); an odd row count runs one masked extra row.
     // Rows past the strip are clamped by refl_clamp / fd_clampi: harmless loads, results unused.
     const int n_run = (n_iter + 1) & ~1;
-#if FD_MS_PREFETCH
     // sched_barrier: hipcc otherwise sinks the prefetch loads down to their first use
     for (int i = 0; i < n_run; i += 2) {
         load_disp(dtap[0], i + 2);
@@ -513,18 +582,19 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
         process(pre[1], i + 1);
         __builtin_amdgcn_sched_barrier(0);
     }
-#else
-    for (int i = 0; i < n_run; ++i) {      // no software prefetch: fewer live registers, latency hidden by a third wave per SIMD
-        load_disp(dtap[0], i);
-        issue(pre[0], dtap[0], i);
-        process(pre[0], i);
-    }
-#endif
     if (GRAD && n_run == n_iter) {
-        __syncthreads();
+        if (NF > 1) __syncthreads();
         if (f == 0) {   // last owned row: index n_iter-3
-            const float other = xd[(n_iter - 1) & 1][lane];
-            if (colown) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (pend + other) * pend_k), r_d1, cx * 4, (y0s + rows - 1) * W * 4, 0);
+            float tot;
+            if constexpr (NF == 2) {
+                const float other = xd[(n_iter - 1) & 1][0][lane];
+                tot = pend + other;
+            } else {
+                tot = pend;
+#pragma unroll
+                for (int j = 0; j < NF - 1; ++j) tot += xd[(n_iter - 1) & 1][j][lane];
+            }
+            if (colown) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, tot * pend_k), r_d1, cx * 4, (y0s + rows - 1) * W * 4, 0);
         }
     }
 
@@ -533,7 +603,8 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
     if (f == 0) {
         const float t = fd_wave_sum(acc0);
         if (lane == 0) a.part[blk * 4 + 0] = t;
-    } else {
+    }
+    if (NF == 2 ? f != 0 : f == FB) {
         const float t1 = fd_wave_sum(acc1), t2 = fd_wave_sum(acc2), t3 = fd_wave_sum(acc3);
         if (lane == 0) { a.part[blk * 4 + 1] = t1; a.part[blk * 4 + 2] = t2; a.part[blk * 4 + 3] = t3; }
     }
@@ -541,18 +612,21 @@ __global__ void __launch_bounds__(128, FD_MS_WAVES) k_photo_ms(MsArgs a) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
             const float t = fd_wave_sum(gP[k]);
-            if (lane == 0) a.gpart[(blk * 2 + f) * 12 + k] = t;
+            if (lane == 0) a.gpart[(blk * NF + f) * 12 + k] = t;
         }
     }
 }
 
 // Blocks [0, S): the scalar loss terms of scale s (same `out` layout as fd_photo_fwd, FD_PHOTO_OUT_FLOATS floats per scale).
-// Blocks [S, S + S*B): gP1[s][b][f][12] = sum over the strips of image b at scale s.
+// Blocks [S, S + S*B): gP1[s][b][f][12] = sum over the strips of image b at scale s (NK = NF * 12 values per image): G groups of
+// NK threads, group gi strides through the strips by G, then the groups are added in index order.
+template <int NF>
 __global__ void __launch_bounds__(256) k_photo_ms_fin(const float* __restrict__ part, const float* __restrict__ gpart, int S, int B,
                                                       int groups, int blocks_per_image, float count, float si_var, unsigned beam_mask,
                                                       int si_mode, int want_grad, float* __restrict__ out, float* __restrict__ gP1) {
+    constexpr int NK = 12 * NF, G = 256 / NK;
     __shared__ float red[4][4];
-    __shared__ float gred[10][24];
+    __shared__ float gred[G][NK];
     const int t = threadIdx.x;
     if ((int)blockIdx.x < S) {
         const int s = blockIdx.x;
@@ -589,18 +663,18 @@ __global__ void __launch_bounds__(256) k_photo_ms_fin(const float* __restrict__ 
     }
     if (!want_grad) return;
     const int img = blockIdx.x - S;       // s * B + b
-    const int k = t % 24, gi = t / 24;
-    if (gi < 10) {
+    const int k = t % NK, gi = t / NK;
+    if (gi < G) {
         float sacc = 0.f;
-        for (int i = gi; i < blocks_per_image; i += 10) sacc += gpart[((long)img * blocks_per_image + i) * 24 + k];
+        for (int i = gi; i < blocks_per_image; i += G) sacc += gpart[((long)img * blocks_per_image + i) * NK + k];
         gred[gi][k] = sacc;
     }
     __syncthreads();
-    if (t < 24) {
+    if (t < NK) {
         float sacc = 0.f;
 #pragma unroll
-        for (int j = 0; j < 10; ++j) sacc += gred[j][t];
-        gP1[(long)img * 24 + t] = sacc;
+        for (int j = 0; j < G; ++j) sacc += gred[j][t];
+        gP1[(long)img * NK + t] = sacc;
     }
 }
 
@@ -608,7 +682,7 @@ __global__ void __launch_bounds__(256) k_photo_ms_fin(const float* __restrict__ 
 // (trainer.py:434-435) for the scales below full resolution, then gP = sum_s g_photo[s] * gP1[s].
 struct MsBwdArgs {
     fd_photo_cfg cfg;
-    int S;
+    int S, nk;                                                 // scales, NF * 12
     float lo, span;
     int Hs[4], Ws[4];
     int first_block[5];                                        // block range of scale s: [first_block[s], first_block[s+1])
@@ -619,7 +693,7 @@ struct MsBwdArgs {
     const float* g_photo[4]; const float* g_si[4];             // one device float each, or NULL (= 0)
     const float* d1;                                           // [S,B,H,W]
     float* d_disp[4];
-    const float* gP1; float* gP;                               // [S][B*24], [B*24]
+    const float* gP1; float* gP;                               // [S][B*nk], [B*nk]
 };
 
 struct SiTerm {      // per (scale, image): everything the LiDAR gradient of one pixel needs
@@ -706,10 +780,10 @@ __global__ void __launch_bounds__(256) k_photo_ms_bwd(MsBwdArgs a) {
     int blk = blockIdx.x;
     if (blk >= a.first_block[a.S]) {                 // gP blocks
         const int i = (blk - a.first_block[a.S]) * 256 + t;
-        if (i < B * 24) {
+        if (i < B * a.nk) {
             float acc = 0.f;
             for (int s = 0; s < a.S; ++s)
-                if (a.g_photo[s]) acc += *a.g_photo[s] * a.gP1[(long)s * B * 24 + i];
+                if (a.g_photo[s]) acc += *a.g_photo[s] * a.gP1[(long)s * B * a.nk + i];
             a.gP[i] = acc;
         }
         return;
@@ -818,8 +892,8 @@ int check_ms(const fd_photo_ms_cfg* c, const char* who) {
     FD_REQUIRE(c->n_scales >= 1 && c->n_scales <= 4, "%s: n_scales must be 1..4 (got %d)", who, c->n_scales);
     for (int s = 0; s < c->n_scales; ++s)
         FD_REQUIRE(c->Hs[s] > 0 && c->Ws[s] > 0 && c->Hs[s] <= b.H && c->Ws[s] <= b.W, "%s: bad disparity size at scale %d", who, s);
-    FD_REQUIRE(b.NF == 2 && b.use_ssim && !b.avg_reprojection,
-               "%s: the multi-scale kernel covers NF == 2, SSIM, per-frame minimum (use fd_photo_fwd for the other variants)", who);
+    FD_REQUIRE(b.NF >= 1 && b.NF <= 3 && b.use_ssim && !b.avg_reprojection,
+               "%s: the multi-scale kernel covers 1 <= NF <= 3, SSIM, per-frame minimum (use fd_photo_fwd for the other variants)", who);
     FD_REQUIRE(b.groups >= 1 && b.groups <= 16 && b.B % b.groups == 0, "%s: batch %d not divisible into %d groups", who, b.B, b.groups);
     FD_REQUIRE(b.min_depth > 0 && b.max_depth > b.min_depth, "%s: bad depth range", who);
     FD_REQUIRE(b.si_mode == 0 || b.si_mode == 1, "%s: si_mode must be 0 or 1", who);
@@ -835,19 +909,37 @@ inline long ms_blocks_per_image(const fd_photo_ms_cfg* c) {
     return (long)fd_cdiv(c->base.W, OW) * fd_cdiv(c->base.H, ms_rows(c));
 }
 
+template <int NF>
+int launch_fwd(const MsArgs& a, dim3 grid, dim3 fin_grid, int bpi, float count, float* out, float* gP1, hipStream_t st) {
+    const bool ident = a.has_ident, grad = a.want_grad;
+    if (ident && grad) hipLaunchKernelGGL((k_photo_ms<NF, true, true>), grid, dim3(64 * NF), 0, st, a);
+    else if (ident) hipLaunchKernelGGL((k_photo_ms<NF, true, false>), grid, dim3(64 * NF), 0, st, a);
+    else if (grad) hipLaunchKernelGGL((k_photo_ms<NF, false, true>), grid, dim3(64 * NF), 0, st, a);
+    else hipLaunchKernelGGL((k_photo_ms<NF, false, false>), grid, dim3(64 * NF), 0, st, a);
+    FD_LAUNCH_CHECK("fd_photo_ms_fwd");
+    hipLaunchKernelGGL(k_photo_ms_fin<NF>, fin_grid, dim3(256), 0, st, a.part, a.gpart, a.S, a.cfg.B, a.cfg.groups, bpi, count,
+                       a.cfg.si_var, a.beam_mask, a.cfg.si_mode, a.want_grad, out, gP1);
+    FD_LAUNCH_CHECK("fd_photo_ms_fin");
+    return 0;
+}
+
 }  // namespace
 
+// workspace: part [nblk][4], gpart [nblk][NF][12], gP1 [S][B][NF][12]
 extern "C" long fd_photo_ms_ws_floats(const fd_photo_ms_cfg* c) {
-    if (!c || c->n_scales < 1 || c->base.B < 1) return 0;
+    if (!c || c->n_scales < 1 || c->base.B < 1 || c->base.NF < 1 || c->base.NF > 3) return 0;
     const long nblk = ms_blocks_per_image(c) * c->base.B * c->n_scales;
-    return nblk * 4 + nblk * 24 + (long)c->n_scales * c->base.B * 24;
+    const long nk = c->base.NF * 12;
+    return nblk * 4 + nblk * nk + (long)c->n_scales * c->base.B * nk;
 }
 
 extern "C" int fd_photo_ms_fwd(const fd_photo_ms_cfg* c, const float* const* disp, const float* inv_K, const float* P,
                                const float* const* src, const float* target, const float* ident, const float* const* noise,
                                const float* beam, uint8_t* sel, float* d1, float* ws, float* out, void* stream) {
     if (int rc = check_ms(c, "fd_photo_ms_fwd")) return rc;
-    FD_REQUIRE(disp && inv_K && P && src && src[0] && src[1] && target && sel && ws && out, "fd_photo_ms_fwd: NULL argument");
+    const int NF = c->base.NF, nk = NF * 12;
+    FD_REQUIRE(disp && inv_K && P && src && target && sel && ws && out, "fd_photo_ms_fwd: NULL argument");
+    for (int f = 0; f < NF; ++f) FD_REQUIRE(src[f], "fd_photo_ms_fwd: src[%d] is NULL", f);
     FD_REQUIRE(!(c->beam_mask && !beam), "fd_photo_ms_fwd: beam_mask without beam");
     MsArgs a;
     a.cfg = c->base;
@@ -863,26 +955,21 @@ extern "C" int fd_photo_ms_fwd(const fd_photo_ms_cfg* c, const float* const* dis
     a.has_ident = ident ? 1 : 0;
     a.want_grad = d1 ? 1 : 0;
     a.beam_mask = beam ? c->beam_mask : 0u;
-    a.inv_K = inv_K; a.P = P; a.src[0] = src[0]; a.src[1] = src[1]; a.target = target; a.ident = ident; a.beam = beam;
+    a.inv_K = inv_K; a.P = P; a.target = target; a.ident = ident; a.beam = beam;
+    for (int f = 0; f < 3; ++f) a.src[f] = src[f < NF ? f : NF - 1];
     a.sel = sel; a.d1 = d1;
     const long bpi = ms_blocks_per_image(c);
     const long nblk = bpi * c->base.B * c->n_scales;
     a.part = ws; a.gpart = ws + nblk * 4;
-    float* gP1 = ws + nblk * 28;
+    float* gP1 = ws + nblk * (4 + nk);
     hipStream_t st = (hipStream_t)stream;
     a.nx = fd_cdiv(c->base.W, OW); a.ny = fd_cdiv(c->base.H, a.R);
-    dim3 grid(fd_cdiv((long)c->base.B * a.ny * a.nx, 8) * 8 * c->n_scales);
-    if (ident && d1) hipLaunchKernelGGL((k_photo_ms<true, true>), grid, dim3(128), 0, st, a);
-    else if (ident) hipLaunchKernelGGL((k_photo_ms<true, false>), grid, dim3(128), 0, st, a);
-    else if (d1) hipLaunchKernelGGL((k_photo_ms<false, true>), grid, dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((k_photo_ms<false, false>), grid, dim3(128), 0, st, a);
-    FD_LAUNCH_CHECK("fd_photo_ms_fwd");
+    const dim3 grid(fd_cdiv((long)c->base.B * a.ny * a.nx, 8) * 8 * c->n_scales);
+    const dim3 fin_grid(c->n_scales + (d1 ? c->n_scales * c->base.B : 0));
     const float count = (float)c->base.B * (float)c->base.H * (float)c->base.W;
-    hipLaunchKernelGGL(k_photo_ms_fin, dim3(c->n_scales + (d1 ? c->n_scales * c->base.B : 0)), dim3(256), 0, st, a.part, a.gpart,
-                       c->n_scales, c->base.B, c->base.groups, (int)bpi, count, c->base.si_var, a.beam_mask, c->base.si_mode,
-                       a.want_grad, out, gP1);
-    FD_LAUNCH_CHECK("fd_photo_ms_fin");
-    return 0;
+    if (NF == 1) return launch_fwd<1>(a, grid, fin_grid, (int)bpi, count, out, gP1, st);
+    if (NF == 2) return launch_fwd<2>(a, grid, fin_grid, (int)bpi, count, out, gP1, st);
+    return launch_fwd<3>(a, grid, fin_grid, (int)bpi, count, out, gP1, st);
 }
 
 extern "C" int fd_photo_ms_bwd(const fd_photo_ms_cfg* c, const float* const* disp, const float* beam, const float* stats,
@@ -892,9 +979,9 @@ extern "C" int fd_photo_ms_bwd(const fd_photo_ms_cfg* c, const float* const* dis
     FD_REQUIRE(disp && stats && g_photo && g_si && d1 && ws && d_disp && gP, "fd_photo_ms_bwd: NULL argument");
     MsBwdArgs a;
     a.cfg = c->base;
-    a.S = c->n_scales;
+    a.S = c->n_scales; a.nk = c->base.NF * 12;
     a.lo = (float)(1.0 / c->base.max_depth); a.span = (float)(1.0 / c->base.min_depth - 1.0 / c->base.max_depth);
-    const int B = c->base.B, H = c->base.H, W = c->base.W;
+    const int B =c->base.B, H = c->base.H, W = c->base.W;
     int nb = 0;
     for (int s = 0; s < 4; ++s) {
         const bool on = s < c->n_scales;
@@ -922,8 +1009,8 @@ extern "C" int fd_photo_ms_bwd(const fd_photo_ms_cfg* c, const float* const* dis
     a.beam_mask = beam ? c->beam_mask : 0u;
     a.beam = beam; a.stats = stats; a.d1 = d1;
     const long nblk = ms_blocks_per_image(c) * B * c->n_scales;
-    a.gP1 = ws + nblk * 28; a.gP = gP;
-    nb += fd_cdiv(B * 24, 256);
+    a.gP1 = ws + nblk * (4 + a.nk); a.gP = gP;
+    nb += fd_cdiv(B * a.nk, 256);
     hipLaunchKernelGGL(k_photo_ms_bwd, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
     FD_LAUNCH_CHECK("fd_photo_ms_bwd");
     return 0;

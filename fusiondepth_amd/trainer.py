@@ -889,7 +889,7 @@ class Trainer:
         noise_in = inputs.get("_noise")               # injected tie-break noise (tests); else drawn like trainer.py:551-552
         if self._multiscale_loss_ok(fids):
             # default configuration: ALL scales in one launch that also produces the gradients (csrc/photometric_ms.hip; with
-            # --use_stereo the one- / three-frame kernel of csrc/photometric_msn.hip, "s" posed by stereo_T: trainer.py:444-447)
+            # --use_stereo its one- / three-frame instantiations, "s" posed by stereo_T: trainer.py:444-447)
             scales = list(self.opt.scales)
             B, _, H, W = inputs[("color", 0, 0)].shape
             Ts = [inputs["stereo_T"] if f == "s" else outputs[("cam_T_cam", 0, f)] for f in fids]

@@ -45,7 +45,8 @@ extern "C" {
  *    Added later WITHOUT raising the number: the KITTI 3-D detection depth export (fd_depth_export + struct fd_export_desc,
  *    fd_depth_quantize_u16).  Nothing removed, no signature changed: a client built against 8 runs unchanged, and one that wants the
  *    export looks the two symbols up (dlsym) instead of comparing the number, which tests/test_eigen_eval_cpu.py pins at 8.
- *    Likewise the all-scales loss for one or three source frames (fd_photo_msn_ws_floats, fd_photo_msn_fwd, fd_photo_msn_bwd).
+ *    Likewise the all-scales loss for one or three source frames: fd_photo_ms_ws_floats / _fwd / _bwd accept cfg.base.NF 1..3
+ *    (first shipped as a separate fd_photo_msn_* triple, since folded into these; calls with NF == 2 are unchanged).
  *    Likewise the training-time scorer (fd_val_scores_ws_bytes, fd_val_scores; it reuses struct fd_eigen_desc).
  *    Likewise the Completor's training-time scorer (fd_completion_val_scores_ws_bytes, fd_completion_val_scores).
  *    Likewise the per-class Eigen-split scorer (fd_eigen_class_scores_ws_bytes, fd_eigen_class_scores, fd_class_errors; it reuses
@@ -257,18 +258,22 @@ int fd_photo_bwd_ex(const fd_photo_cfg* cfg, const float* disp, const float* inv
 
 /* ---- all pyramid scales in one launch, value + unit-cotangent gradient in the same pass ------------------------------
  * Replaces the per-scale loop of trainer.py:425-474 (generate_images_pred) + trainer.py:509-567, 577-589 (compute_losses)
- * for the default configuration: two source frames, SSIM + L1, per-frame minimum (automasking on or off), SI-log or masked
- * L1 LiDAR term on any subset of the scales.  The flag variants (--no_ssim, --avg_reprojection, one source frame, the
- * materialised ("depth"|"sample"|"color", f, s) outputs) stay on fd_photo_fwd / fd_photo_bwd.
- *   cfg.base      as for fd_photo_fwd (Hs / Ws ignored: per-scale sizes are cfg.Hs[] / cfg.Ws[]); NF must be 2
- *   disp[s]       [B,1,Hs[s],Ws[s]]      noise[s]  [B,2,H,W] or NULL (the array itself may be NULL)
- *   ident         [B,2,H,W] or NULL      beam      [B,1,H,W] or NULL; cfg.beam_mask bit s = scale s carries the LiDAR term
- *   sel           [S,B,H,W] u8 out       d1        [S,B,H,W] out: d out[s][0] / d disp_up, or NULL to skip every gradient
+ * for the default configuration: SSIM + L1, per-frame minimum (automasking on or off), SI-log or masked L1 LiDAR term on any
+ * subset of the scales, and NF = 1 to 3 source frames: two by default; --use_stereo makes it one (frame_ids [0, "s"]) or three
+ * ([0, -1, 1, "s"]), the stereo partner's pose being just one more P.  One wave per source frame and strip
+ * (csrc/photometric_ms.hip).  The flag variants (--no_ssim, --avg_reprojection, the materialised ("depth"|"sample"|"color", f, s)
+ * outputs) stay on fd_photo_fwd / fd_photo_bwd.
+ *   cfg.base      as for fd_photo_fwd (Hs / Ws ignored: per-scale sizes are cfg.Hs[] / cfg.Ws[]); NF must be 1, 2 or 3
+ *   src[NF]       [B,3,H,W] each         P         [B,NF,3,4]
+ *   disp[s]       [B,1,Hs[s],Ws[s]]      noise[s]  [B,NF,H,W] or NULL (the array itself may be NULL)
+ *   ident         [B,NF,H,W] or NULL     beam      [B,1,H,W] or NULL; cfg.beam_mask bit s = scale s carries the LiDAR term
+ *   sel           [S,B,H,W] u8 out: index into cat(ident_0.., reproj_0..) (0 .. 2 NF - 1; 0 .. NF - 1 without ident)
+ *   d1            [S,B,H,W] out: d out[s][0] / d disp_up, or NULL to skip every gradient
  *   ws            fd_photo_ms_ws_floats(cfg) floats; must stay untouched until fd_photo_ms_bwd has run
  *   out           [S][FD_PHOTO_OUT_FLOATS], each laid out like fd_photo_fwd's `out`
  * fd_photo_ms_bwd: g_photo[s] / g_si[s] = device pointers to dL/d out[s][0] / dL/d out[s][4] (NULL = 0); d1 is read only;
  * d_disp[s] [B,1,Hs[s],Ws[s]] out (H / Hs[s] == W / Ws[s] must be an integer <= 16);
- * gP [B,2,3,4] out = sum over scales of g_photo[s] * d out[s][0] / d P. */
+ * gP [B,NF,3,4] out = sum over scales of g_photo[s] * d out[s][0] / d P. */
 typedef struct {
     fd_photo_cfg base;
     int n_scales;            /* 1..4 */
@@ -283,18 +288,6 @@ int fd_photo_ms_fwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const 
 int fd_photo_ms_bwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* beam, const float* stats,
                     const float* const* g_photo, const float* const* g_si, float* d1, const float* ws,
                     float* const* d_disp, float* gP, void* stream);
-/* The same three entry points for ONE or THREE source frames (--use_stereo: frame_ids [0, "s"] and [0, -1, 1, "s"]; the stereo
- * partner's pose is just one more P).  Semantics, layouts and `out` exactly as above with cfg.base.NF in {1, 3}: src[NF],
- * P [B,NF,3,4], noise[s] / ident [B,NF,H,W], sel = index into cat(ident_0.., reproj_0..) (0 .. 2 NF - 1; 0 .. NF - 1 without
- * ident), gP [B,NF,3,4].  One wave per source frame and strip (csrc/photometric_msn.hip); NF == 2 is refused here as NF != 2
- * is above. */
-long fd_photo_msn_ws_floats(const fd_photo_ms_cfg* cfg);
-int fd_photo_msn_fwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* inv_K, const float* P,
-                     const float* const* src, const float* target, const float* ident, const float* const* noise,
-                     const float* beam, uint8_t* sel, float* d1, float* ws, float* out, void* stream);
-int fd_photo_msn_bwd(const fd_photo_ms_cfg* cfg, const float* const* disp, const float* beam, const float* stats,
-                     const float* const* g_photo, const float* const* g_si, float* d1, const float* ws,
-                     float* const* d_disp, float* gP, void* stream);
 
 /* layers.py:235-248 get_smooth_loss on the mean-normalised disparity (trainer.py:569-571):
  * out[0] = get_smooth_loss(disp/(mean_hw(disp)+1e-7), img).  ws: fd_smooth_ws_floats(B,H,W). */

@@ -1,9 +1,9 @@
 """The --use_stereo optimiser step on one GPU, ResNet-18, 640x192, --batch_size 12, synthetic scene batches with the stereo partner
 "s" resident in HBM: frame_ids [0, -1, 1] (three source frames) and [0] (stereo only).  Two routes of the loss, alternated round by
 round inside ONE run so that both see the same machine state:
-    fused      the all-scales kernel for one / three source frames (csrc/photometric_msn.hip: fd_photo_msn_fwd / _bwd)
+    fused      the all-scales kernel at one / three source frames (csrc/photometric_ms.hip: fd_photo_ms_fwd / _bwd)
     per-scale  ``tuning.host.photo_ms = False``: four fd_photo_fwd_ex + four fd_photo_bwd_ex launches - the only route these
-               configurations had before that kernel existed (a tree without it prints this column only)
+               configurations had before that kernel took them (a tree from before prints this column only)
 Per configuration: the step's wall clock (bracketed by synchronize, like bench.py) per round, and the device time between two
 HIP events around the loss path alone - forward + backward on resident inputs, many iterations back to back.  The spread is what
 the script itself observes between its rounds; a difference smaller than that is not a difference.
@@ -24,7 +24,7 @@ ap.add_argument("--loss_iters", type=int, default=200)
 ap.add_argument("--height", type=int, default=192)
 ap.add_argument("--width", type=int, default=640)
 args = ap.parse_args()
-HAS_FUSED = FD.photo_ms_supported(FD.PhotoOptions(), 3)          # False on a tree from before the one- / three-frame kernel
+HAS_FUSED = FD.photo_ms_supported(FD.PhotoOptions(), 3)          # False on a tree whose all-scales kernel takes two frames only
 ROUTES = [("fused", True), ("per-scale", False)] if HAS_FUSED else [("per-scale", False)]
 
 

@@ -27,7 +27,7 @@ def main():
                         "-I", os.path.join(ROOT, "include"), "-I", os.path.dirname(SRC), "-S", "--cuda-device-only", "-o", asm, SRC],
                        check=True, stderr=subprocess.DEVNULL)
         lines = open(asm).read().split("\n")
-    start = [i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_photo_msILb1ELb1E\S*:", l)][0]
+    start = [i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_photo_msILi2ELb1ELb1E\S*:", l)][0]
     end = [i for i, l in enumerate(lines) if l.startswith(".Lfunc_end") and i > start][0]
     body = lines[start:end]
     labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}

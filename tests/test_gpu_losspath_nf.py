@@ -1,4 +1,4 @@
-"""fd_photo_msn_fwd / fd_photo_msn_bwd (csrc/photometric_msn.hip): the all-scales fused loss for ONE and THREE source frames, the
+"""fd_photo_ms_fwd / fd_photo_ms_bwd (csrc/photometric_ms.hip) with NF = 1 and 3: the all-scales fused loss for ONE and THREE source frames, the
 stereo configurations of --use_stereo (frame_ids [0, "s"] and [0, -1, 1, "s"]).  Same yardsticks and tolerances as the two-frame
 kernel's tests in test_gpu_losspath.py, whose helpers are reused: the CPU oracle, its float64 run, and the per-scale HIP kernels.
 The stereo partner "s" is the scene of frame 0 shifted by 3 pixels; its pose ``stereo_T`` carries no gradient."""
@@ -91,7 +91,8 @@ def test_multiscale_photo_loss_nf_vs_oracle(FD, monkeypatch, nf, seed, B, H, W, 
     real_call = loss_ops.call
     monkeypatch.setattr(loss_ops, "call", lambda name, *a: (called.append(name), real_call(name, *a))[1])
     tot_g.backward()
-    assert called.count("fd_photo_msn_bwd") == 1 and called.count("fd_proj_matrix_bwd") == len(temporal), called
+    assert called.count("fd_photo_ms_bwd") == 1 and called.count("fd_proj_matrix_bwd") == len(temporal), called
+    assert called.count("fd_photo_ms_fwd") == 0, called          # the forward ran before the hook: backward launches no second one
     assert T_g["s"].grad is None and not T_g["s"].requires_grad
     got = [cpu(d_g[s].grad) for s in range(4)] + [cpu(T_g[f].grad) for f in temporal]
     for s in range(4):
@@ -137,7 +138,7 @@ def test_loss_path_nf_error_against_float64(FD, nf):
 
 @pytest.mark.parametrize("nf", [1, 3])
 def test_multiscale_photo_loss_nf_matches_per_scale_kernels(FD, nf):
-    """Counterpart of test_multiscale_photo_loss_matches_per_scale_kernels: value, selection and gradients of fd_photo_msn_* against
+    """Counterpart of test_multiscale_photo_loss_matches_per_scale_kernels: value, selection and gradients of fd_photo_ms_* (NF = 1, 3) against
     fd_photo_fwd_ex / fd_photo_bwd_ex, with the LiDAR term on scale 0 only."""
     opt, inp, disp0, T0, noise = _case(404, 2, 64, 96, nf)
     temporal = [f for f in FRAMES[nf] if f != "s"]
