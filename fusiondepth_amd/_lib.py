@@ -83,6 +83,14 @@ class ExportDesc(ctypes.Structure):
     _fields_ = [("offset", _L), ("H", _I), ("W", _I), ("pred", _I), ("reserved", _I)]
 
 
+class PointsCalib(ctypes.Structure):
+    """Mirror of ``fd_points_calib``."""
+    _fields_ = [(n, _D) for n in ("c_u", "c_v", "f_u", "f_v", "b_x", "b_y")] + [("A", _D * 9), ("t", _D * 3)]
+
+
+assert ctypes.sizeof(PointsCalib) == 144
+
+
 class RelayoutJob(ctypes.Structure):
     """Mirror of ``fd_relayout_job``."""
     _fields_ = ([("w", ctypes.c_void_p), ("dst", ctypes.c_void_p)] +
@@ -234,6 +242,8 @@ SIGNATURES = {
     "fd_completion_val_scores": ("piii" "pl" "pi" "il" "fff" "p" "pp", "i"),
     "fd_depth_export": ("piii" "pi" "lii" "f" "ppp" "p", "i"),
     "fd_depth_quantize_u16": ("pplp", "i"),
+    "fd_points_export_ws_bytes": ("ii", "l"),
+    "fd_points_export": ("ppp" "il" "ii" "d" "p" "pp" "p", "i"),
     "fd_vis_render_ws_bytes": ("il", "l"),
     "fd_vis_render": ("piii" "fp" "p" "pl" "pi" "l" "ff" "pp" "pp" "l" "pp" "pp", "i"),
     "fd_log_sheets_ws_bytes": ("ii", "l"),

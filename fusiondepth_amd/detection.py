@@ -9,6 +9,19 @@
   * ``export_gt_depths_detec`` / ``detec_output_name``   ``gt_depths.npz`` / ``4beam.npz`` of ``splits/detection``.
   * ``depth_export``                ``fd_depth_export`` (csrc/detection.hip): resize, invert, scale and quantise N maps of different
     sizes in one library call per chunk; ``quantize_u16``: the same quantiser on the float64 map GDC produces.
+  * ``points_export``               ``fd_points_export`` (csrc/pseudo_lidar.hip): pseudo-LiDAR clouds, the other half of the
+    Pseudo-LiDAR family this project's LiDAR pipeline comes from (``project_depth_to_points``) - N float32 maps of different sizes
+    back-projected into the Velodyne frame, filtered and compacted in three launches per chunk, one download of the kept points.
+
+The point rule.  For pixel column ``u``, row ``v`` (integers) and ``z = float64(depth[v, u])``, with ``Calibration``'s camera-2 scalars and
+``(A, t) = kitti_utils.rect_to_velo(date folder)``, all in float64, each operation rounded once, no contraction, in this order:
+    x = ((u - c_u) * z) / f_u + b_x
+    y = ((v - c_v) * z) / f_v + b_y
+    X = ((A00*x + A01*y) + A02*z) + t0                  # Y, Z likewise with rows 1, 2
+    keep = (X >= 0) & (Z < max_high)                    # max_high defaults to 1.0 m; NaN falls out through the comparisons
+    point = float32(X), float32(Y), float32(Z), 1.0f
+Kept points follow in row-major pixel order (numpy's boolean indexing), images back to back; there are no other filters
+(tests/pseudo_lidar_ref.py restates it in numpy).
 
 Deviations from the reference, on purpose
   * an image size outside ``get_detec_calib``'s table raises ``ValueError`` naming it (the reference returns ``None`` and fails later).
@@ -16,10 +29,15 @@ Deviations from the reference, on purpose
     path component of the line (``training``): ``--eval_gdc`` needs the date to find ``calib_cam_to_cam.txt``.
   * the calibration lives under ``<data_path>/<date>`` (the reference hardcodes ``kitti_data/<date>`` relative to the working directory).
   * out of the ``uint16`` range numpy's ``astype`` is undefined; the quantiser defines it: NaN and negative -> 0, ``>= 65535`` -> 65535.
-No CPU fallback: ``depth_export`` and the loader need the GPU; the path rules and the table do not.
+  * the pseudo-LiDAR calibration is the recording DATE's (``calib_cam_to_cam.txt`` / ``calib_velo_to_cam.txt``, chosen from the image
+    size like everything else here), not the object set's per-frame ``calib/*.txt`` that Pseudo-LiDAR reads.
+  * the matrix products of the point rule are written out in this project's order, so a cloud agrees with Pseudo-LiDAR's ``np.dot``
+    chain to float64 rounding (far below the float32 it is stored in), not to the bit.
+No CPU fallback: ``depth_export``, ``points_export`` and the loader need the GPU; the path rules and the table do not.
 """
 import ctypes
 import os
+import threading
 
 import numpy as np
 import torch
@@ -143,13 +161,17 @@ def pack_export_sizes(sizes):
     return desc, at
 
 
-def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, want_depth=False, chunk=64):
+def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, want_depth=False, chunk=64, want_packed=False):
     """export_detection.py:322-325, 344-348, 388 for N images, ``chunk`` of them per ``fd_depth_export`` call: the disparity resized to
     ``sizes[i] = (H_i, W_i)`` by OpenCV's float32 INTER_LINEAR rule, ``1 / .``, ``* pred_depth_scale_factor``, ``* ratios[i]`` (when
     given), ``* 256`` and the cast to ``uint16`` - each step one float32 rounding, the cast as the module docstring defines it.
     ``pred_disps``: [N,h,w] device tensor or host array (float64 is rounded to float32 once, as ``eigen_scores`` does).
     Returns a list of N ``uint16`` [H_i,W_i] arrays, views into one pinned download per chunk; with ``want_depth`` also the float32
-    maps before the ``* 256`` (what the scorer clamps and scores) as device tensors: ``(u16 list, depth list)``."""
+    maps before the ``* 256`` (what the scorer clamps and scores) as device tensors: ``(u16 list, depth list)``.  ``want_packed``
+    (with ``want_depth``) adds a third element: per chunk, ``(packed float32 device tensor, EXPORT_DESC array)`` - what the depth list
+    is made of views of, in the form ``points_export(packed=...)`` takes without another launch or copy."""
+    if want_packed and not want_depth:
+        raise ValueError("depth_export: want_packed needs want_depth")
     if not torch.cuda.is_available():
         raise RuntimeError("fusiondepth_amd.detection.depth_export needs an MI355X: there is no CPU path (tests/detection_ref.py restates it)")
     from . import functional as FD
@@ -162,7 +184,7 @@ def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, wa
         ratios = np.ascontiguousarray(np.asarray(ratios, dtype=np.float32).reshape(-1))
         if ratios.size != N:
             raise ValueError("depth_export: %d ratios for %d maps" % (ratios.size, N))
-    maps, depths = [], []
+    maps, depths, packs = [], [], []
     for a in range(0, N, chunk):
         b = min(a + chunk, N)
         disp = pred_disps[a:b]
@@ -187,7 +209,122 @@ def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, wa
             maps.append(flat[o:o + n].reshape(int(d["H"]), int(d["W"])))
             if want_depth:
                 depths.append(depth[o:o + n].view(int(d["H"]), int(d["W"])))
+        if want_packed:
+            packs.append((depth, desc))
+    if want_packed:
+        return maps, depths, packs
     return (maps, depths) if want_depth else maps
+
+
+# ---------------------------------------------------------------------------------------------------------------- pseudo-LiDAR
+# numpy mirror of ``fd_points_calib`` (144 bytes, as ``_lib.PointsCalib``): c_u, c_v, f_u, f_v, b_x, b_y, A[9], t[3]
+POINTS_CALIB_DOUBLES = 18
+assert POINTS_CALIB_DOUBLES * 8 == ctypes.sizeof(_lib.PointsCalib)
+_POINTS_STAGE = [None]                                           # the pinned staging buffer, reused across chunks and calls
+_POINTS_LOCK = threading.Lock()                                  # one chunk at a time owns it, from its download to its copy-out
+_COPY_POOL = [None]                                              # host threads that copy the clouds out of it
+_COPY_POOL_MIN_POINTS = 1 << 18                                  # 4 MiB of points: below it one thread is as quick
+
+
+def _copy_pool():
+    if _COPY_POOL[0] is None:
+        import concurrent.futures
+        _COPY_POOL[0] = concurrent.futures.ThreadPoolExecutor(max_workers=min(8, max(1, os.cpu_count() or 1)),
+                                                              thread_name_prefix="fd_points_copy")
+    return _COPY_POOL[0]
+
+
+def points_calib_row(calibration, A, t):
+    """One ``fd_points_calib`` as 18 float64: ``kitti_utils.Calibration``'s camera-2 scalars, then ``rect_to_velo``'s A and t."""
+    A, t = np.asarray(A, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    if A.shape != (3, 3) or t.shape != (3,):
+        raise ValueError("points_export: A must be [3,3] and t [3], got %s and %s" % (A.shape, t.shape))
+    c = calibration
+    return np.concatenate([np.array([c.c_u, c.c_v, c.f_u, c.f_v, c.b_x, c.b_y], dtype=np.float64), A.reshape(9), t])
+
+
+def _stage(floats):
+    """A pinned float32 buffer of at least ``floats`` elements; grown by doubling, kept for the next chunk."""
+    cur = _POINTS_STAGE[0]
+    if cur is None or cur.numel() < floats:
+        cur = torch.empty((max(floats, 2 * (cur.numel() if cur is not None else 0), 1 << 16),), dtype=torch.float32, pin_memory=True)
+        _POINTS_STAGE[0] = cur
+    return cur
+
+
+def _points_chunk(depth, desc, calibs, max_high):
+    """One ``fd_points_export`` call on a packed float32 device tensor: one table upload (descriptors and calibrations in one buffer),
+    the call, the read-back of ``starts``, one pinned download of exactly 16 bytes per kept point."""
+    n = len(desc)
+    total_px = int(depth.numel())
+    dev = depth.device
+    table = np.concatenate([np.ascontiguousarray(desc).view(np.uint8).reshape(-1),
+                            np.stack([points_calib_row(*c) for c in calibs]).view(np.uint8).reshape(-1)])
+    table_d = torch.from_numpy(table).to(dev)                    # 24 n bytes of descriptors, then 144 n of calibrations: both 8-aligned
+    max_H, max_W = int(desc["H"].max()), int(desc["W"].max())
+    ws_bytes = _lib.query("fd_points_export_ws_bytes", n, max_H)
+    if ws_bytes <= 0:
+        raise ValueError("points_export: %d maps of up to %d rows are out of range" % (n, max_H))
+    ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+    points = torch.empty((4 * total_px,), device=dev, dtype=torch.float32)
+    starts = torch.empty((n + 1,), device=dev, dtype=torch.int64)
+    _lib.call("fd_points_export", depth.data_ptr(), table_d.data_ptr(), table_d.data_ptr() + desc.nbytes, n, total_px, max_H, max_W,
+              float(max_high), ws.data_ptr(), points.data_ptr(), starts.data_ptr(), _lib.stream())
+    starts_h = starts.cpu().numpy()                              # synchronises: table_d and ws are free to go afterwards
+    total = int(starts_h[-1])
+    if total > total_px:
+        raise ValueError("points_export: descriptors overlap (%d points for %d pixels)" % (total, total_px))
+    if not total:
+        return [np.empty((0, 4), dtype=np.float32) for _ in range(n)]
+    with _POINTS_LOCK:                                           # two threads in points_export take turns at the staging buffer
+        stage = _stage(4 * total)[:4 * total]
+        stage.copy_(points[:4 * total])                          # 16 * total bytes, nothing more
+        staged = stage.numpy().reshape(total, 4)
+        views = [staged[int(starts_h[i]):int(starts_h[i + 1])] for i in range(n)]
+        # out of the staging buffer, which the next chunk reuses: a copy per cloud - for more than a few MB on host threads (numpy
+        # releases the GIL in a copy; on one thread this copy, not the download, is what a chunk of 16 KITTI-sized maps waits for)
+        if n == 1 or total < _COPY_POOL_MIN_POINTS:
+            return [v.copy() for v in views]
+        return list(_copy_pool().map(np.copy, views))
+
+
+def points_export(depth_maps, calibs, max_high=1.0, chunk=16, packed=None):
+    """Pseudo-LiDAR clouds by the point rule of the module docstring (``fd_points_export``).  ``depth_maps``: a list of 2-D float32
+    device tensors of different sizes, such as the maps ``depth_export(want_depth=True)`` returns; ``calibs``: one
+    ``(kitti_utils.Calibration, A, t)`` per map, ``(A, t) = kitti_utils.rect_to_velo(...)``.  Returns a list of float32 ``[M_i, 4]`` host
+    arrays (x, y, z, 1): the layout of a KITTI ``.bin``.  ``chunk`` maps share one library call.
+    ``packed=(tensor, EXPORT_DESC array)`` instead of ``depth_maps`` (pass ``None``): the maps already lie packed on the device, as one
+    element of ``depth_export(want_depth=True, want_packed=True)[2]`` - one call for all of them, no per-image launch or copy.
+    The pinned staging buffer and the copy threads are module state (``_POINTS_STAGE``, ``_COPY_POOL``: idle worker threads that the
+    interpreter joins at exit); a lock serialises the download and copy-out of concurrent callers, everything else may overlap."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("fusiondepth_amd.detection.points_export needs an MI355X GPU: there is no CPU path "
+                           "(tests/pseudo_lidar_ref.py restates it)")
+    if chunk < 1 or chunk > 4096:
+        raise ValueError("points_export: chunk must be 1 .. 4096")
+    if packed is not None:
+        if depth_maps is not None:
+            raise ValueError("points_export: give depth_maps or packed, not both")
+        depth, desc = packed
+        if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 1 and depth.is_contiguous()):
+            raise ValueError("points_export: packed[0] must be a contiguous 1-D float32 device tensor")
+        if len(desc) != len(calibs):
+            raise ValueError("points_export: %d calibrations for %d maps" % (len(calibs), len(desc)))
+        return _points_chunk(depth, desc, calibs, max_high) if len(desc) else []
+    N = len(depth_maps)
+    if len(calibs) != N:
+        raise ValueError("points_export: %d calibrations for %d maps" % (len(calibs), N))
+    clouds = []
+    for a in range(0, N, chunk):
+        b = min(a + chunk, N)
+        part = depth_maps[a:b]
+        for i, m in enumerate(part):
+            if not (torch.is_tensor(m) and m.is_cuda and m.dtype == torch.float32 and m.dim() == 2):
+                raise ValueError("points_export: map %d must be a 2-D float32 device tensor" % (a + i))
+        desc, _ = pack_export_sizes([tuple(m.shape) for m in part])
+        depth = part[0].reshape(-1).contiguous() if b - a == 1 else torch.cat([m.reshape(-1) for m in part])
+        clouds += _points_chunk(depth, desc, calibs[a:b], max_high)
+    return clouds
 
 
 def quantize_u16(depth):

@@ -2,7 +2,7 @@
 like ``evaluate_depth`` scores the Eigen split and saved as the 16-bit PNGs a monocular 3-D detector is trained on.
 
     python -m fusiondepth_amd.export_detection --splits_dir splits --data_path kitti_data --load_weights_folder <folder> \\
-        --eval_mono --png --det_name <name> [--refine_2d ...] [--post_process] [--eval_gdc]
+        --eval_mono --png --det_name <name> [--refine_2d ...] [--post_process] [--eval_gdc] [--pl_name <name> [--pl_max_high 1.0]]
 
 ``evaluate(opt, splits_dir)`` (:77-413): lines from ``<splits_dir>/detection/test.txt``, ``Predictor`` exactly as
 ``evaluate_depth.evaluate`` constructs it, ``detection.KITTIDetecBatches`` as the loader, ``evaluate_depth.predict_disps`` for the
@@ -18,8 +18,15 @@ disparities, ground truth ``<splits_dir>/detection/gt_depths.npz`` (``detection.
   * the maps go to ``<data_path>/<folder of the line>/<det_name>/{:06d}.png``, written with PIL on a pool of at most 16 host threads
     while the next chunk runs on the device.  As in the reference (:388), the map is saved BEFORE the [1e-3, 80] clamp of the scorer.
 
-Returns ``(mean_errors[7], ratios, per_image[N,7] or None with --eval_gdc, paths)``; ``None`` after ``--no_eval`` and for the
-``benchmark`` split.
+  * ``--pl_name NAME [--pl_max_high F]`` (this script's flags, taken off the command line like ``--splits_dir``): next to each PNG a
+    pseudo-LiDAR cloud ``<data_path>/<folder of the line>/<pl_name>/{:06d}.bin`` (float32 x, y, z, 1 in the Velodyne frame, the input
+    of a LiDAR-based detector), by ``detection.points_export`` and the point rule stated there - from the SAME float32 map the PNG is
+    quantised from (``depth_export(want_depth=True)`` of the chunk; with ``--eval_gdc`` the corrected map rounded to float32 once),
+    with the calibration of the line's recording date.  PNG, score and cloud cannot disagree.  Refused with ``--no_eval`` and
+    ``--eval_split benchmark``.
+
+Returns ``(mean_errors[7], ratios, per_image[N,7] or None with --eval_gdc, paths)``, with ``--pl_name`` a fifth element, the ``.bin``
+paths; ``None`` after ``--no_eval`` and for the ``benchmark`` split.
 
 Deviations from the reference, on purpose (next to those of ``evaluate_depth`` and ``detection``)
   * the file name is the LINE'S FRAME INDEX.  The reference names the PNG after the loop counter and uses the counter for the GDC
@@ -28,6 +35,8 @@ Deviations from the reference, on purpose (next to those of ``evaluate_depth`` a
   * the output folder is ``<data_path>/<folder of the line>/<det_name>`` (the reference hardcodes ``kitti_data/kitti_detect/training``),
     and a missing ``--det_name`` raises ``ValueError`` (the reference writes into a folder called ``None``).
   * values the 16-bit payload cannot hold are defined instead of left to the C cast: NaN and negative -> 0, >= 65535 -> 65535.
+  * the clouds are not in the reference at all (its ``project_image_to_velo`` calls a method that is commented out); their two
+    deviations from Pseudo-LiDAR - the date's calibration, this project's product order - are stated in ``detection``.
 """
 import concurrent.futures
 import os
@@ -48,17 +57,30 @@ def png_path(data_path, line, det_name):
     return os.path.join(data_path, folder, det_name, "{:06d}.png".format(frame_index))
 
 
+def bin_path(data_path, line, pl_name):
+    folder, frame_index, _ = parse_line(line)
+    return os.path.join(data_path, folder, pl_name, "{:06d}.bin".format(frame_index))
+
+
+def _save_bin(path, cloud):
+    cloud.tofile(path)
+    return path
+
+
 def _save_png(path, depth_u16):
     from PIL import Image
     Image.fromarray(depth_u16).save(path)
     return path
 
 
-def evaluate(opt, splits_dir="splits"):
+def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0):
     """See the module docstring."""
     ED._refuse_uncovered(opt)
     if not opt.det_name:
         raise ValueError("export_detection: --det_name is required (the folder the depth PNGs are written to)")
+    if pl_name and (opt.no_eval or opt.eval_split == "benchmark"):
+        raise ValueError("export_detection: --pl_name needs the scaled depth maps; it cannot be combined with --no_eval or "
+                         "--eval_split benchmark")
     filenames = ED._read_lines(os.path.join(splits_dir, "detection", "test.txt"))
     dates = []
     if opt.ext_disp_to_eval is None:
@@ -118,7 +140,19 @@ def evaluate(opt, splits_dir="splits"):
         print("   Mono evaluation - using median scaling")
 
     paths = [png_path(opt.data_path, line, opt.det_name) for line in filenames]
-    for d in sorted(set(os.path.dirname(p) for p in paths)):
+    pl_paths, pl_calibs = [], []
+    if pl_name:
+        from . import kitti_utils
+        pl_paths = [bin_path(opt.data_path, line, pl_name) for line in filenames]
+        if not dates:                                            # the loader did not run (--ext_disp_to_eval)
+            for line in filenames:
+                folder, frame_index, _ = parse_line(line)
+                image = os.path.join(opt.data_path, folder, "image_02/data/{:06d}.png".format(frame_index))
+                dates.append(detection.detec_calib_date(*detection.image_size(image)))
+        by_date = {d: (kitti_utils.Calibration(os.path.join(opt.data_path, d, "calib_cam_to_cam.txt")),)
+                      + kitti_utils.rect_to_velo(os.path.join(opt.data_path, d)) for d in sorted(set(dates))}
+        pl_calibs = [by_date[d] for d in dates]
+    for d in sorted(set(os.path.dirname(p) for p in paths + pl_paths)):
         os.makedirs(d, exist_ok=True)
     writes = []
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, max(1, os.cpu_count() or 1))) as pool:
@@ -133,6 +167,9 @@ def evaluate(opt, splits_dir="splits"):
 
             def on_depth(i, depth):                              # after scaling and GDC, before the clamp (:388)
                 writes.append(pool.submit(_save_png, paths[i], detection.quantize_u16(depth)))
+                if pl_name:                                      # the corrected map, rounded to float32 once (as --visualize does)
+                    cloud, = detection.points_export([depth.detach().to(torch.float32)], [pl_calibs[i]], pl_max_high)
+                    writes.append(pool.submit(_save_bin, pl_paths[i], cloud))
 
             mean_errors, ratios = ED.evaluate_predictions(pred_disps, gt_depths, opt.eval_split, opt.pred_depth_scale_factor,
                                                           opt.disable_median_scaling, True, beam_depths, calibs, opt.random_sample, opt.nbeams,
@@ -145,25 +182,42 @@ def evaluate(opt, splits_dir="splits"):
             sizes = [np.asarray(g).shape for g in gt_depths]
             for a in range(0, N, EXPORT_CHUNK):                  # the pool writes chunk k while the device runs chunk k + 1
                 b = min(a + EXPORT_CHUNK, N)
-                maps = detection.depth_export(pred_disps[a:b], sizes[a:b], None if opt.disable_median_scaling else ratios[a:b],
-                                              opt.pred_depth_scale_factor, chunk=EXPORT_CHUNK)
+                chunk_ratios = None if opt.disable_median_scaling else ratios[a:b]
+                if not pl_name:
+                    maps = detection.depth_export(pred_disps[a:b], sizes[a:b], chunk_ratios, opt.pred_depth_scale_factor, chunk=EXPORT_CHUNK)
+                else:                                            # the cloud from the float32 map the PNG is quantised from
+                    maps, _, (pack,) = detection.depth_export(pred_disps[a:b], sizes[a:b], chunk_ratios, opt.pred_depth_scale_factor,
+                                                              want_depth=True, chunk=EXPORT_CHUNK, want_packed=True)
+                    clouds = detection.points_export(None, pl_calibs[a:b], pl_max_high, packed=pack)
+                    writes += [pool.submit(_save_bin, pl_paths[a + k], c) for k, c in enumerate(clouds)]
                 writes += [pool.submit(_save_png, paths[a + k], m) for k, m in enumerate(maps)]
         for w in writes:
             w.result()                                           # a failed write raises here
     print("-> Saved {} depth maps to <data_path>/<folder>/{}".format(N, opt.det_name))
+    if pl_name:
+        print("-> Saved {} pseudo-LiDAR clouds to <data_path>/<folder>/{}".format(N, pl_name))
     if not opt.disable_median_scaling:
         med = np.median(ratios)
         print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
     print("\n  " + ("{:>8} | " * 7).format(*ED.METRICS))
     print(("&{: 8.3f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
     print("\n-> Done!")
+    if pl_name:
+        return mean_errors, ratios, per_image, paths, pl_paths
     return mean_errors, ratios, per_image, paths
+
+
+# the flags of this script that are not among the reference's options (``evaluate_depth.split_off_flags``), with their defaults
+SCRIPT_FLAGS = {"splits_dir": "splits", "pl_name": None, "pl_max_high": "1.0"}
 
 
 def main(argv=None):
     from .options import MonodepthOptions
-    splits_dir, rest = ED.split_off_splits_dir(sys.argv[1:] if argv is None else argv)
-    return evaluate(MonodepthOptions().parse(rest), splits_dir)
+    found, rest = ED.split_off_flags(sys.argv[1:] if argv is None else argv, SCRIPT_FLAGS)
+    opt = MonodepthOptions().parse(rest)
+    if found["pl_name"] is None:                                 # the call of a command line without the new flags, as before
+        return evaluate(opt, found["splits_dir"])
+    return evaluate(opt, found["splits_dir"], pl_name=found["pl_name"], pl_max_high=float(found["pl_max_high"]))
 
 
 if __name__ == "__main__":

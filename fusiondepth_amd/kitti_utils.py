@@ -7,6 +7,8 @@ offline ``gen2channel.py`` script can call these instead:
     float32 x 4 per point; ``calib_*.txt`` = ``key: v0 v1 ...`` lines)
   * ``generate_depth_map(calib_dir, velo_filename, cam, vel_depth, shape)``   kitti_utils.py:40-102  -> float64 numpy image
   * ``Calibration``                                           kitti_util_from_pse.py:47-102 (the camera of GDC, gdc.py)
+  * ``rect_to_velo(calib_dir)``                               the rectified camera -> Velodyne map of the pseudo-LiDAR export
+    (``detection.points_export``); not in the reference, whose ``project_image_to_velo`` calls a method that is commented out
   * ``get_4beam`` / ``get_4beam_2channel`` / ``gen2channel``  kitti_dataset.py:93-117, gen2channel.py:42-58,60-117,122-183
     (writes ``<idx>_<side>_<flip>.npy`` float32 [2,192,640], the files ``KITTIDataset.load_4beam_2channel`` reads).
 
@@ -65,6 +67,20 @@ def velo_to_image(calib_dir, cam=2):
     projection = intr["P_rect_0%d" % cam].reshape(3, 4)
     width, height = (int(v) for v in intr["S_rect_02"][:2])
     return (projection @ rectify) @ to_cam, (height, width)
+
+
+def rect_to_velo(calib_dir):
+    """Rectified camera-0 coordinates -> Velodyne, the inverse of ``velo_to_image``'s rigid part: (A [3,3], t [3]) float64 with
+    ``p_velo = A @ p_rect + t``.  ``R``, ``T`` (``calib_velo_to_cam.txt``) and ``R_rect_00`` (``calib_cam_to_cam.txt``) are read as
+    ``velo_to_image`` reads them; A = R.T @ inv(R_rect_00), t = -(R.T @ T) - kitti_util_from_pse.py's ``project_rect_to_ref``
+    followed by ``project_ref_to_velo`` (``inverse_rigid_trans``: the transpose stands for the inverse of the rotation) folded into
+    one matrix.  The camera-2 offsets b_x, b_y stay with ``Calibration``."""
+    intr = read_calib_file(os.path.join(calib_dir, "calib_cam_to_cam.txt"))
+    extr = read_calib_file(os.path.join(calib_dir, "calib_velo_to_cam.txt"))
+    R = extr["R"].reshape(3, 3)
+    A = R.T @ np.linalg.inv(intr["R_rect_00"].reshape(3, 3))
+    t = -(R.T @ extr["T"])
+    return np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(t, dtype=np.float64)
 
 
 class Calibration:

@@ -52,7 +52,9 @@ extern "C" {
  *    Likewise the per-class Eigen-split scorer (fd_eigen_class_scores_ws_bytes, fd_eigen_class_scores, fd_class_errors; it reuses
  *    struct fd_eigen_desc, and the workspace sizes of the three scorers above are what they were).
  *    Likewise the renderer of evaluate_depth --visualize (fd_vis_render_ws_bytes, fd_vis_render; it reuses struct fd_eigen_desc).
- *    Likewise the trainer's image summaries (fd_log_sheets_ws_bytes, fd_log_sheets, struct fd_log_tile, struct fd_log_cfg). */
+ *    Likewise the trainer's image summaries (fd_log_sheets_ws_bytes, fd_log_sheets, struct fd_log_tile, struct fd_log_cfg).
+ *    Likewise the pseudo-LiDAR point clouds (fd_points_export_ws_bytes, fd_points_export, struct fd_points_calib; it reuses
+ *    struct fd_export_desc). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -931,6 +933,42 @@ typedef struct fd_export_desc {
 int fd_depth_export(const float* disp, int M, int h, int w, const fd_export_desc* desc, int N, long packed_elems, int max_H, int max_W,
                     float pred_scale, const float* ratio /*[N] or NULL*/, float* depth_out, uint16_t* u16_out, void* stream);
 int fd_depth_quantize_u16(const double* x, uint16_t* out, long n, void* stream);
+
+/* ------------------------------------------------------------------ pseudo-LiDAR point clouds --
+ * Pseudo-LiDAR's project_depth_to_points for N dense depth maps of different sizes, packed back to back as fd_depth_export writes
+ * them, in THREE launches whatever N is and without atomics of any kind (csrc/pseudo_lidar.hip): every pixel back-projected into the
+ * Velodyne frame, filtered, and the kept points written as float32 (X, Y, Z, 1) records - the KITTI .bin layout.
+ *   depth    packed float32 planes; desc: DEVICE array of N fd_export_desc - map n is H x W, row-major, at element `offset`; `pred` is
+ *            ignored.  A descriptor whose plane leaves [0, packed_elems), whose size is not positive or whose H / W exceeds max_H /
+ *            max_W is skipped: it contributes no point, starts[n + 1] == starts[n].  max_H / max_W size the grid and the workspace.
+ *   calib    DEVICE array of N fd_points_calib (144 bytes each): the camera of kitti_util_from_pse.py's Calibration and the rectified
+ *            camera -> Velodyne map A = R^T inv(R_rect_00), t = -(R^T T) of calib_velo_to_cam.txt.
+ * For pixel column u, row v (integers) and z = (double)depth[v][u], every step in float64, each operation rounded ONCE, no contraction,
+ * IEEE divisions, in exactly this order:
+ *   x = ((u - c_u) * z) / f_u + b_x
+ *   y = ((v - c_v) * z) / f_v + b_y
+ *   X = ((A[0] * x + A[1] * y) + A[2] * z) + t[0]        Y, Z likewise with A[3..5], t[1] and A[6..8], t[2]
+ *   keep = (X >= 0) && (Z < max_high)                     a NaN falls out through the comparisons; there is no other filter
+ *   point = (float)X, (float)Y, (float)Z, 1.0f
+ * A kept point has a finite-or-infinite X and Z by the predicate; its Y can be a NaN only for an infinite depth (inf - inf), and the sign
+ * and payload of that NaN are the hardware's - the one thing the rule leaves open.
+ * Kept points follow in row-major pixel order (numpy's boolean indexing), the maps back to back in descriptor order.
+ *   points   float32, 16-byte aligned, room for 4 * packed_elems floats; each kept point is ONE 16-byte store at points + 4 * index.
+ *            Only the first 4 * starts[N] floats are written.  (Overlapping descriptors can name more pixels than packed_elems; a
+ *            point whose index is >= packed_elems is counted in `starts` but not written.)
+ *   starts   long [N + 1]: the index of the first point of each map, the total last.
+ *   ws       fd_points_export_ws_bytes(N, max_H) bytes, 16-byte aligned (0: sizes out of range): two ints per row - its count and
+ *            its first slot, in separate arrays, because the scan's workgroups read the counts of each other's maps.
+ * N is 1 .. 65535, max_H * max_W < 2^30.  The position of a point depends on the predicate alone, never on arrival: two calls give
+ * the same bytes.  The scan reads the row counts of all earlier maps once per map - quadratic in N, meant for chunks of tens of maps. */
+typedef struct fd_points_calib {
+    double c_u, c_v, f_u, f_v, b_x, b_y; /* Calibration of camera 2 */
+    double A[9];                         /* row-major 3 x 3 */
+    double t[3];
+} fd_points_calib;
+long fd_points_export_ws_bytes(int N, int max_H);
+int fd_points_export(const float* depth, const fd_export_desc* desc, const fd_points_calib* calib, int N, long packed_elems, int max_H,
+                     int max_W, double max_high, void* ws, float* points, long* starts /*[N + 1]*/, void* stream);
 
 /* ------------------------------------------------------------------ evaluate_depth --visualize --
  * The two pictures of evaluate_depth.py:407-449 for N <= 64 maps of different sizes, packed back to back as fd_depth_export and

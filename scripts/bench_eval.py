@@ -9,6 +9,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py --step semantic [--reps 10] [--out profiles/eigen_class_time.log]
     python scripts/bench_eval.py --step visualize [--reps 10] [--out profiles/visualize_time.log]
     python scripts/bench_eval.py --step log_images [--reps 10] [--out profiles/log_images_time.log]
+    python scripts/bench_eval.py --step pseudo_lidar [--reps 10] [--out profiles/pseudo_lidar_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -59,7 +60,15 @@ disparity, ``disp_to_depth``, back-projection, projection and ``F.grid_sample`` 
 alternate in one run after their sheets were compared (byte for byte outside the colour predictions, within one level inside).  Per J:
 the library call alone between device events with its traffic bound (every source read once, the disparities twice, the sheets written
 once), the recipe's device part, both end to end with their download as wall time - what a log event holds the step loop for - and
-the PNG encoding of one sheet, which the default sink does on its background thread."""
+the PNG encoding of one sheet, which the default sink does on its background thread.
+
+``--step pseudo_lidar``: the pseudo-LiDAR clouds of ``export_detection --pl_name``, ``detection.points_export`` (fd_points_export,
+csrc/pseudo_lidar.hip), at N = 1 and 16 maps of 375x1242 with a KITTI camera, against the ATen recipe it replaces - per image a
+meshgrid, the float64 expression of the point rule in torch, a boolean index per coordinate, a concatenation and a cast -
+alternating in one run after the two were compared byte for byte.  Per N: the library call alone between device events with its
+traffic bound (8 B x pixels: the depth read by the count and by the write pass; 16 B x kept points), the recipe's device part (also
+with its meshgrid hoisted out of the loop), and both end to end with their downloads as wall time - ``points_export`` from a list of
+maps and from the packed tensor ``depth_export`` hands over."""
 import argparse
 import os
 import sys
@@ -211,6 +220,87 @@ def detection_step(a):
         lines.append("          depth_export end to end (descriptor and ratio uploads, 1 call, pinned download of %.1f MB): %.3f ms (%.3f, %.3f) "
                      "= %.3f ms / image; recipe end to end (float32 download, host * 256 and cast): %.3f ms (%.3f, %.3f) = %.3f ms / image -> %.2fx"
                      % (2 * total / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, t_r[0], t_r[1], t_r[2], t_r[0] / n, t_r[0] / t_e[0]))
+    return lines
+
+
+def pseudo_lidar_step(a):
+    import types
+    from fusiondepth_amd import detection as D
+    H, W = 375, 1242
+    rng = np.random.RandomState(5)
+    # the camera and the Velodyne transform of a KITTI recording date (2011_09_26, rounded as published)
+    cam = types.SimpleNamespace(c_u=609.5593, c_v=172.854, f_u=721.5377, f_v=721.5377, b_x=44.85728 / -721.5377, b_y=0.2163791 / -721.5377)
+    R = np.array([[7.533745e-03, -9.999714e-01, -6.166020e-04], [1.480249e-02, 7.280733e-04, -9.998902e-01],
+                  [9.998621e-01, 7.523790e-03, 1.480755e-02]])
+    T = np.array([-4.069766e-03, -7.631618e-02, -2.717806e-01])
+    R0 = np.array([[9.999239e-01, 9.837760e-03, -7.445048e-03], [-9.869795e-03, 9.999421e-01, -4.278459e-03],
+                   [7.402527e-03, 4.351614e-03, 9.999631e-01]])
+    A, t = R.T @ np.linalg.inv(R0), -(R.T @ T)
+    calib = (cam, A, t)
+    Ad, td = [[float(v) for v in row] for row in A], [float(v) for v in t]
+    lines = ["Pseudo-LiDAR clouds, %dx%d float32 depth maps (uniform 2 .. 80 m), max_high 1.0; median of %d (min, max) after one warm-up round, "
+             "the call and the ATen recipe alternating" % (H, W, a.reps)]
+    vv, uu = torch.meshgrid(torch.arange(H, dtype=torch.float64, device="cuda"), torch.arange(W, dtype=torch.float64, device="cuda"), indexing="ij")
+
+    def recipe_one(depth, grid=None):
+        v, u = grid if grid is not None else torch.meshgrid(torch.arange(H, dtype=torch.float64, device="cuda"),
+                                                            torch.arange(W, dtype=torch.float64, device="cuda"), indexing="ij")
+        z = depth.to(torch.float64)
+        x = ((u - cam.c_u) * z) / cam.f_u + cam.b_x
+        y = ((v - cam.c_v) * z) / cam.f_v + cam.b_y
+        X, Y, Z = (((Ad[r][0] * x + Ad[r][1] * y) + Ad[r][2] * z) + td[r] for r in range(3))
+        keep = (X >= 0) & (Z < 1.0)
+        return torch.cat([X[keep][:, None], Y[keep][:, None], Z[keep][:, None], torch.ones_like(X[keep])[:, None]], 1).to(torch.float32)
+
+    for n in (1, 16):
+        maps = [torch.from_numpy(rng.uniform(2.0, 80.0, (H, W)).astype(np.float32)).cuda() for _ in range(n)]
+        calibs = [calib] * n
+        desc, total = D.pack_export_sizes([(H, W)] * n)
+        depth = torch.cat([m.reshape(-1) for m in maps])
+        table = torch.from_numpy(np.concatenate([desc.view(np.uint8).reshape(-1),
+                                                 np.stack([D.points_calib_row(*c) for c in calibs]).view(np.uint8).reshape(-1)])).cuda()
+        ws = torch.empty((query("fd_points_export_ws_bytes", n, H),), device="cuda", dtype=torch.uint8)
+        points = torch.empty((4 * total,), device="cuda", dtype=torch.float32)
+        starts = torch.empty((n + 1,), device="cuda", dtype=torch.int64)
+
+        def kernel():
+            call("fd_points_export", depth.data_ptr(), table.data_ptr(), table.data_ptr() + desc.nbytes, n, total, H, W, 1.0, ws.data_ptr(),
+                 points.data_ptr(), starts.data_ptr(), stream())
+
+        def recipe_device():
+            return [recipe_one(m) for m in maps]
+
+        def recipe_device_grid():                                # the recipe with its meshgrid hoisted out: what a careful caller would write
+            return [recipe_one(m, (vv, uu)) for m in maps]
+
+        def recipe_all():
+            return [c.cpu().numpy() for c in recipe_device()]
+
+        def export_all():
+            return D.points_export(maps, calibs, 1.0, chunk=16)
+
+        def export_packed():                                     # as export_detection calls it: the maps already lie packed
+            return D.points_export(None, calibs, 1.0, packed=(depth, desc))
+
+        got, want = export_all(), recipe_all()
+        assert all(g.shape == x.shape and np.array_equal(g.view(np.uint32), x.view(np.uint32)) for g, x in zip(got, want)), \
+            "the call and the recipe disagree"
+        assert all(np.array_equal(g, x) for g, x in zip(export_packed(), got))
+        kept = sum(len(g) for g in got)
+        t_k, t_rd, t_rg = alternate([kernel, recipe_device, recipe_device_grid], a.reps, _event_ms)
+        t_e, t_p, t_r = alternate([export_all, export_packed, recipe_all], a.reps, _wall_ms)
+        bound = 8 * total + 16 * kept
+        t_bound = 1e3 * bound / HBM
+        lines.append("  N = %2d (%d of %d pixels kept = %.2f; equal bytes): fd_points_export, resident, 3 launches: %.3f ms (%.3f, %.3f) = %.1f us / image; "
+                     "traffic bound 8 B x pixels + 16 B x kept = %.2f MB = %.2f us at 6.3 TB/s -> %.1fx the bound; the recipe's device part: "
+                     "%.3f ms (%.3f, %.3f) -> %.1fx, with the meshgrid hoisted %.3f ms (%.3f, %.3f) -> %.1fx"
+                     % (n, kept, total, kept / total, t_k[0], t_k[1], t_k[2], 1e3 * t_k[0] / n, bound / 1e6, 1e3 * t_bound, t_k[0] / t_bound,
+                        t_rd[0], t_rd[1], t_rd[2], t_rd[0] / t_k[0], t_rg[0], t_rg[1], t_rg[2], t_rg[0] / t_k[0]))
+        lines.append("          points_export end to end (pack, table upload, 1 call, starts read-back, pinned download of %.1f MB, host split): "
+                     "%.3f ms (%.3f, %.3f) = %.3f ms / image; from the packed tensor: %.3f ms (%.3f, %.3f); recipe end to end (a download per "
+                     "image): %.3f ms (%.3f, %.3f) = %.3f ms / image -> %.2fx (packed: %.2fx)%s"
+                     % (16 * kept / 1e6, t_e[0], t_e[1], t_e[2], t_e[0] / n, t_p[0], t_p[1], t_p[2], t_r[0], t_r[1], t_r[2], t_r[0] / n,
+                        t_r[0] / t_e[0], t_r[0] / t_p[0], "" if t_r[0] > t_e[0] else "  THE RECIPE WINS HERE"))
     return lines
 
 
@@ -626,17 +716,19 @@ def completion_val_step(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize", "log_images"), default="eigen")
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar"),
+                    default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
                                                 "val": "val_time.log", "completion_val": "completion_val_time.log",
                                                 "semantic": "eigen_class_time.log", "visualize": "visualize_time.log",
-                                                "log_images": "log_images_time.log"}[a.step])
-    if a.step in ("detection", "val", "completion_val", "semantic", "visualize", "log_images"):
+                                                "log_images": "log_images_time.log", "pseudo_lidar": "pseudo_lidar_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar"):
         text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step,
-                          "semantic": semantic_step, "visualize": visualize_step, "log_images": log_images_step}[a.step](a))
+                          "semantic": semantic_step, "visualize": visualize_step, "log_images": log_images_step,
+                          "pseudo_lidar": pseudo_lidar_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
