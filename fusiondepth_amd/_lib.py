@@ -104,6 +104,21 @@ class LogTile(ctypes.Structure):
                [(n, _I) for n in ("kind", "y", "x", "h", "w", "aux", "slot", "reserved")]
 
 
+class JpegInfo(ctypes.Structure):
+    """Mirror of ``fd_jpeg_info``."""
+    _fields_ = [(n, _I) for n in ("width", "height", "components", "h_samp", "v_samp", "covered")] + \
+               [("blocks_w", _I * 3), ("blocks_h", _I * 3), ("restart_interval", _I), ("reserved", _I), ("coef_count", _L)]
+
+
+class JpegDesc(ctypes.Structure):
+    """Mirror of ``fd_jpeg_desc``."""
+    _fields_ = [(n, _L) for n in ("coef_off", "qt_off", "plane_off", "out_off")] + \
+               [(n, _I) for n in ("kind", "width", "height", "components", "h_samp", "v_samp")] + [("reserved", _I * 2)]
+
+
+assert ctypes.sizeof(JpegInfo) == 64 and ctypes.sizeof(JpegDesc) == 64
+
+
 class LogCfg(ctypes.Structure):
     """Mirror of ``fd_log_cfg``."""
     _fields_ = [("Hs", _I), ("Ws", _I), ("n_rows", _I), ("n_disp", _I), ("row_y", _I * 8), ("row_h", _I * 8), ("row_first", _I * 8),
@@ -248,6 +263,9 @@ SIGNATURES = {
     "fd_vis_render": ("piii" "fp" "p" "pl" "pi" "l" "ff" "pp" "pp" "l" "pp" "pp", "i"),
     "fd_log_sheets_ws_bytes": ("ii", "l"),
     "fd_log_sheets": ("pp" "ii" "p" "pp" "p", "i"),
+    "fd_jpeg_probe": ("plp", "i"),
+    "fd_jpeg_entropy_decode": ("pl" "pl" "pp", "i"),
+    "fd_jpeg_reconstruct": ("pl" "pi" "pl" "p", "i"),
 }
 
 _lock = threading.Lock()

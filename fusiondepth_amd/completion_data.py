@@ -208,11 +208,12 @@ def _depth_into(path, dst):
 class KITTICompletionBatches(KITTIRAWBatches):
     """See the module docstring.  The first eight arguments are ``KITTICompletion``'s (``data_path`` is the completion tree);
     the others are ``KITTIRAWBatches``'.  The split is ``train`` if ``is_train`` else ``val`` (``val_split`` = "select" / "full"), and
-    ``test_completion`` when ``opt.completion_test``."""
+    ``test_completion`` when ``opt.completion_test``.  ``decoder="device"`` is accepted and changes nothing: the colour frames of
+    the completion tree are PNG files, which stay with Pillow."""
 
     def __init__(self, data_path, height, width, frame_idxs, num_scales, is_train=False, val_split="select", opt=None, batch_size=1,
                  shuffle=False, seed=0, device="cuda", workers=8, draws=None, loader=None, prefetch=True, drop_last=True,
-                 rank=0, world_size=1):
+                 rank=0, world_size=1, decoder="pil"):
         if opt is None:
             raise ValueError("KITTICompletionBatches: opt is required (completion_not_full_res, completion_test, ...)")
         self.full_res = not getattr(opt, "completion_not_full_res", False)
@@ -226,7 +227,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
         self.paths = completion_paths(data_path, self.split, val_split)
         super().__init__(data_path, self.paths["rgb"], height, width, frame_idxs, num_scales, is_train=is_train, img_ext=".png", opt=opt,
                          batch_size=batch_size, shuffle=shuffle, seed=seed, device=device, workers=workers, draws=draws, loader=loader,
-                         prefetch=prefetch, drop_last=drop_last, rank=rank, world_size=world_size)
+                         prefetch=prefetch, drop_last=drop_last, rank=rank, world_size=world_size, decoder=decoder)
         self.frames = list(self.frame_idxs) if self.is_train else [0]
         self.eval_gdc = bool(self._opt("eval_gdc"))
 

@@ -497,3 +497,211 @@ def image_pyramid(frames_u8, height, width, num_scales, flip=None, jitter=None):
             descs.append((u8_off[s] + n * per, -1, pl_off[s] + (N + n) * per, pl_off[s] + n * per, h, w, factors, order))
     _run_jitter(arena, descs, None, planes, sizes[0][0] * sizes[0][1])
     return out
+
+
+# ------------------------------------------------------------------------------------ baseline JPEG frames -------
+# Pillow's decode of a baseline JPEG, split as include/fdhip.h ("baseline JPEG frames") describes: Huffman decoding on a host pool
+# behind the C ABI (ctypes releases the interpreter lock), everything after it in csrc/jpeg.hip.  tests/jpeg_ref.py restates it.
+_JPEG_POOL = []
+
+
+def _round16(n):
+    return (n + 15) // 16 * 16
+
+
+def jpeg_pool():
+    """The 16-thread pool ``decode_jpeg_batch`` uses when the caller brings none."""
+    if not _JPEG_POOL:
+        import concurrent.futures
+        _JPEG_POOL.append(concurrent.futures.ThreadPoolExecutor(max_workers=16))
+    return _JPEG_POOL[0]
+
+
+def jpeg_probe(data):
+    """``fd_jpeg_probe`` of a bytes-like object -> (status, JpegInfo).  Host only."""
+    info = _lib.JpegInfo()
+    buf = (ctypes.c_ubyte * len(data)).from_buffer_copy(data) if not isinstance(data, bytes) else data
+    return _lib.load().fd_jpeg_probe(buf, len(data), ctypes.byref(info)), info
+
+
+def jpeg_entropy_decode(data, coef, qt):
+    """``fd_jpeg_entropy_decode`` into ``coef`` (a contiguous int16 numpy array; its size is ``coef_cap``) and ``qt`` (uint16, 192
+    values) -> (status, JpegInfo).  Host only; the reason of a non-zero status is ``_lib.last_error()`` on the calling thread."""
+    info = _lib.JpegInfo()
+    buf = (ctypes.c_ubyte * len(data)).from_buffer_copy(data) if not isinstance(data, bytes) else data
+    st = _lib.load().fd_jpeg_entropy_decode(buf, len(data), coef.ctypes.data, coef.size, qt.ctypes.data, ctypes.byref(info))
+    return st, info
+
+
+def _pil_rgb(data):
+    import io
+    import numpy as np
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as img:
+        return np.asarray(img.convert("RGB"))
+
+
+class JpegBatchJob:
+    """The host side of ``decode_jpeg_batch``, started on ``pool`` without blocking the caller: every file is read and probed; the
+    worker that finishes the last probe lays out ONE pinned staging buffer (descriptors, then per frame its tables and coefficients
+    or, for a frame Pillow decodes, its RGB bytes) and submits the entropy decoders, each writing straight into its slice.
+    ``finish(device)`` waits, uploads the buffer once and calls ``fd_jpeg_reconstruct`` once."""
+
+    def __init__(self, files, pool=None):
+        import threading
+        self.files = list(files)
+        if not self.files:
+            raise ValueError("decode_jpeg_batch: no files")
+        if len(self.files) > 65535:
+            raise ValueError("decode_jpeg_batch: %d files in one call; the kernel takes 65535" % len(self.files))
+        self.pool = pool if pool is not None else jpeg_pool()
+        self._lock, self._ready, self._error = threading.Lock(), threading.Event(), None
+        self._left = len(self.files)
+        self._probed = [None] * len(self.files)
+        self._futures = []
+        for i, f in enumerate(self.files):
+            self.pool.submit(self._probe, i, f)
+
+    # ---- pool side --------------------------------------------------------------------------------------------------------------
+    def _probe(self, i, f):
+        try:
+            if isinstance(f, (bytes, bytearray, memoryview)):
+                data = bytes(f)
+            else:
+                with open(f, "rb") as fh:
+                    data = fh.read()
+            st, info = jpeg_probe(data)
+            if st == 0 and info.covered:
+                self._probed[i] = (data, info, None)
+            else:                                                # not covered, or not a JPEG at all: Pillow decides
+                self._probed[i] = (data, None, _pil_rgb(data))
+        except BaseException as e:                               # noqa: B902 - handed to finish()
+            with self._lock:
+                self._error = self._error or e
+        with self._lock:
+            self._left -= 1
+            last = self._left == 0
+        if last:
+            self._plan()
+
+    def _plan(self):
+        try:
+            if self._error is not None:
+                return
+            n = len(self.files)
+            at = _round16(n * ctypes.sizeof(_lib.JpegDesc))
+            self._slots, planes = [], 0
+            for data, info, rgb in self._probed:
+                if info is not None:
+                    h, w, need = info.height, info.width, 384 + 2 * info.coef_count
+                    planes += _round16(info.coef_count)
+                else:
+                    h, w, need = rgb.shape[0], rgb.shape[1], 0
+                size = _round16(max(need, 3 * h * w))            # a frame whose entropy decoding fails gets Pillow's bytes instead
+                self._slots.append((at, size, h, w))
+                at += size
+            self._upload_bytes, self._plane_bytes = at, planes
+            self._staging = torch.empty((at,), dtype=torch.uint8, pin_memory=True)
+            self._host = self._staging.numpy()
+            self._kinds = [1] * n
+            self._futures = [self.pool.submit(self._decode, i) for i in range(n)]
+        except BaseException as e:                               # noqa: B902
+            self._error = e
+        finally:
+            self._ready.set()
+
+    def _decode(self, i):
+        import numpy as np
+        data, info, rgb = self._probed[i]
+        at, size, h, w = self._slots[i]
+        if info is not None:
+            qt = self._host[at:at + 384].view(np.uint16)
+            coef = self._host[at + 384:at + 384 + 2 * info.coef_count].view(np.int16)
+            st, _ = jpeg_entropy_decode(data, coef, qt)
+            if st == 0:
+                self._kinds[i] = 0
+                return
+            rgb = _pil_rgb(data)                                 # a damaged stream: as tolerant, or as strict, as Pillow is
+            if rgb.shape[:2] != (h, w):
+                raise RuntimeError("decode_jpeg_batch: Pillow decoded %s, the frame header says %s" % (rgb.shape[:2], (h, w)))
+        self._host[at:at + 3 * h * w] = rgb.reshape(-1)
+
+    # ---- caller side ------------------------------------------------------------------------------------------------------------
+    def wait_host(self):
+        """Block until the host phase (read, probe, Huffman decoding or Pillow) is done; raise what it raised.  Returns the layout:
+        ``{"staging": the pinned uint8 buffer, "upload_bytes": its size, "plane_bytes": the device-only room behind it,
+        "total_bytes": their sum}`` - the descriptor table at the start of the buffer is written by ``finish``."""
+        self._ready.wait()
+        if self._error is not None:
+            raise self._error
+        for f in self._futures:
+            f.result()
+        return {"staging": self._staging, "upload_bytes": self._upload_bytes, "plane_bytes": self._plane_bytes,
+                "total_bytes": self._upload_bytes + self._plane_bytes}
+
+    def descriptors(self):
+        """A copy of the ``fd_jpeg_desc`` table ``finish`` wrote (a ctypes array of ``_lib.JpegDesc``)."""
+        n = len(self.files)
+        return (_lib.JpegDesc * n).from_buffer_copy(self._host[:n * ctypes.sizeof(_lib.JpegDesc)].tobytes())
+
+    def finish(self, device="cuda"):
+        """-> (groups, stats): ``groups`` = {(H, W): (uint8 [n, H, W, 3] device tensor, input indices)} in order of first
+        appearance, all views of one buffer.  Runs on ``device``'s current stream, whichever device is current."""
+        self.wait_host()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("decode_jpeg_batch runs on the GPU only (got %s); there is no CPU path" % device)
+        with torch.cuda.device(device):
+            return self._finish_on(device)
+
+    def _finish_on(self, device):
+        n = len(self.files)
+        members = {}
+        for i, (_, _, h, w) in enumerate(self._slots):
+            members.setdefault((h, w), []).append(i)
+        out_off, at = [0] * n, 0
+        spans = {}
+        for (h, w), idx in members.items():
+            spans[(h, w)] = at
+            for i in idx:
+                out_off[i] = at
+                at += 3 * h * w
+            at = _round16(at)
+        out_bytes = max(at, 16)
+        table = (_lib.JpegDesc * n)()
+        plane_at = self._upload_bytes
+        for i, (d, (slot, _, h, w)) in enumerate(zip(table, self._slots)):
+            info = self._probed[i][1]
+            d.kind, d.width, d.height, d.out_off = self._kinds[i], w, h, out_off[i]
+            if self._kinds[i] == 0:
+                d.qt_off, d.coef_off, d.plane_off = slot, slot + 384, plane_at
+                d.components, d.h_samp, d.v_samp = info.components, info.h_samp, info.v_samp
+                plane_at += _round16(info.coef_count)
+            else:
+                d.coef_off = slot
+        nbytes = n * ctypes.sizeof(_lib.JpegDesc)
+        import numpy as np
+        self._host[:nbytes] = np.frombuffer(table, dtype=np.uint8)
+        total = self._upload_bytes + self._plane_bytes
+        dev = torch.empty((total,), dtype=torch.uint8, device=device)
+        dev[:self._upload_bytes].copy_(self._staging, non_blocking=True)       # the batch's one host-to-device copy
+        out = torch.empty((out_bytes,), dtype=torch.uint8, device=device)
+        call("fd_jpeg_reconstruct", dev.data_ptr(), total, dev.data_ptr(), n, out.data_ptr(), out_bytes, stream())
+        groups = {(h, w): (out[spans[(h, w)]:spans[(h, w)] + len(idx) * 3 * h * w].view(len(idx), h, w, 3), idx)
+                  for (h, w), idx in members.items()}
+        device_n = sum(1 for k in self._kinds if k == 0)
+        return groups, {"device": device_n, "fallback": n - device_n}
+
+
+def decode_jpeg_batch(files, device="cuda", pool=None):
+    """``np.asarray(Image.open(f).convert("RGB"))`` of every file, byte for byte, on the device.  ``files``: paths or ``bytes``.
+    Returns ``(frames, stats)``: a list of uint8 [H, W, 3] device tensors - views into one buffer, same-size frames contiguous - and
+    ``{"device": n, "fallback": n}``.  Covered baseline streams (include/fdhip.h) are Huffman-decoded on the host pool and finished
+    by ``fd_jpeg_reconstruct``; everything else - progressive, CMYK, a PNG, a damaged stream - is decoded by Pillow into the same
+    staging buffer and copied by the same call.  One host-to-device copy and one library call whatever the number of files."""
+    groups, stats = JpegBatchJob(files, pool).finish(device)
+    frames = [None] * len(files)
+    for stack, idx in groups.values():
+        for k, i in enumerate(idx):
+            frames[i] = stack[k]
+    return frames, stats

@@ -126,11 +126,14 @@ class KITTIRAWBatches:
     out the current one, ``lidar_source`` = ``"files"`` (sparse scans written offline) or ``"raw"`` (sparsified here from
     ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default: the reference's list for ``opt.nbeams``),
     ``sparsify_grid`` = (H, W) of its angular grid, ``rank`` / ``world_size`` = this process's shard of every epoch (data-parallel
-    training; the defaults give the whole epoch, exactly as before)."""
+    training; the defaults give the whole epoch, exactly as before), ``decoder`` = ``"pil"`` (Pillow on the pool, the default) or
+    ``"device"`` (``data_ops.JpegBatchJob``: Huffman decoding on the pool, the rest in HIP, byte for byte Pillow's frames;
+    ``decode_stats`` counts the frames each way; a ``.png`` tree keeps Pillow, ``loader=`` with it raises)."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
                  batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
-                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True, rank=0, world_size=1):
+                 prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True, rank=0, world_size=1,
+                 decoder="pil"):
         self.data_path, self.filenames = data_path, list(filenames)
         self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
         self.frame_idxs = list(frame_idxs)
@@ -141,6 +144,13 @@ class KITTIRAWBatches:
         self.workers = max(1, min(int(workers), 16))
         self.jitter_per_image = bool(jitter_per_image)
         self.draws, self.loader, self.prefetch = draws, loader or pil_loader, bool(prefetch)
+        if decoder not in ("pil", "device"):
+            raise ValueError("KITTIRAWBatches: decoder must be 'pil' or 'device', got %r" % (decoder,))
+        if decoder == "device" and loader is not None:
+            raise ValueError("KITTIRAWBatches: decoder='device' decodes the files itself; it cannot be combined with loader=")
+        # a .png tree stays with Pillow (inflate is serial): the device route is for JPEG frames
+        self.decoder = decoder if str(img_ext).lower() in (".jpg", ".jpeg") else "pil"
+        self.decode_stats = {"device": 0, "fallback": 0}
         if self.batch_size < 1:
             raise ValueError("KITTIRAWBatches: batch_size must be positive")
         self.rank, self.world_size = int(rank), int(world_size)
@@ -339,8 +349,11 @@ class KITTIRAWBatches:
         """Submit the file work of a batch to the pool."""
         items = self.plan_batch(epoch, indices)
         pool = self._workers()
+        if self.decoder == "device":                             # frame-major, the order of every colour key
+            items[0]["jpeg_job"] = data_ops.JpegBatchJob([it["images"][fi] for fi in range(len(self.frame_idxs)) for it in items], pool)
         for it in items:
-            it["image_futures"] = [pool.submit(self.loader, p) for p in it["images"]]
+            if self.decoder != "device":
+                it["image_futures"] = [pool.submit(self.loader, p) for p in it["images"]]
             if self.lidar_source == "raw":
                 continue
             it["beam_futures"] = [pool.submit(kitti_utils.load_velodyne_points, p) for p in it["beams"]]
@@ -358,17 +371,27 @@ class KITTIRAWBatches:
     # ---- device side of a batch -------------------------------------------------------------------------------------------------
     def _colour_keys(self, items, batch):
         B, F = len(items), len(self.frame_idxs)
-        frames = [[f.result() for f in it["image_futures"]] for it in items]
-        groups = {}                                              # native size -> [(frame slot, item)]: drives differ in size
-        for fi in range(F):                                      # frame-major: with one native size every key is a contiguous slice
-            for b in range(B):
-                groups.setdefault(frames[b][fi].shape, []).append((fi, b))
+        groups, stacks = {}, {}                                  # native size -> [(frame slot, item)]: drives differ in size
+        if "jpeg_job" in items[0]:                               # decoded on the device: the stacks are views of one buffer
+            decoded, stats = items[0]["jpeg_job"].finish(self.device)
+            for name in stats:
+                self.decode_stats[name] += stats[name]
+            for (h, w), (stack, idx) in decoded.items():
+                groups[(h, w, 3)], stacks[(h, w, 3)] = [(i // B, i % B) for i in idx], stack
+        else:
+            frames = [[f.result() for f in it["image_futures"]] for it in items]
+            for fi in range(F):                                  # frame-major: with one native size every key is a contiguous slice
+                for b in range(B):
+                    groups.setdefault(frames[b][fi].shape, []).append((fi, b))
         sizes = [(self.height // 2 ** s, self.width // 2 ** s) for s in range(self.num_scales)]
         whole = {}
         for shape, members in groups.items():
             if len(shape) != 3 or shape[2] != 3:
                 raise RuntimeError("KITTIRAWBatches: a decoded frame has shape %s, expected [H,W,3]" % (shape,))
-            stack = torch.from_numpy(np.stack([frames[b][fi] for fi, b in members])).to(self.device, non_blocking=True)
+            if shape in stacks:
+                stack = stacks[shape]
+            else:
+                stack = torch.from_numpy(np.stack([frames[b][fi] for fi, b in members])).to(self.device, non_blocking=True)
             flip = [items[b]["do_flip"] for _, b in members]
             jitter = None
             if any(it["jitter"] is not None for it in items):

@@ -1047,6 +1047,103 @@ long fd_log_sheets_ws_bytes(int J, int n_disp);
 int fd_log_sheets(const fd_log_tile* tiles_host, const fd_log_tile* tiles_dev, int J, int NT, const fd_log_cfg* cfg, unsigned char* sheets,
                   void* ws, void* stream);
 
+/* ------------------------------------------------------------------ baseline JPEG frames --
+ * Pillow's `Image.open(f).convert("RGB")` of a baseline JPEG, split where GPU loaders split it: the serial Huffman decoding on the
+ * host (csrc/jpeg_entropy.h: plain C++, no GPU call, no globals, thread-safe, usable on a machine without a GPU), everything after it
+ * on the device (csrc/jpeg.hip).  libjpeg's default back half is integer arithmetic throughout, so the result is held to Pillow's
+ * bytes (tests/jpeg_ref.py restates the rules below in numpy, entropy decoder included).
+ *
+ * Covered streams: SOF0, and SOF1 at 8 bits; Huffman coding; ONE interleaved scan; three-component YCbCr (a JFIF marker, or no Adobe
+ * marker and component ids other than 'R','G','B') with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, or one-component greyscale;
+ * restart intervals; custom Huffman tables; 8- or 16-bit quantisation tables.  NOT covered: progressive, lossless, arithmetic coding,
+ * 12 bits, CMYK / Adobe RGB, 4:4:0 and every other sampling, multi-scan baseline, DNL.  For those `covered` is 0, the probe still
+ * returns 0 once it has read the frame header, and the decoder returns FD_JPEG_UNCOVERED: a status, never a guess.
+ *
+ * Neither host function reads outside [file, file + n) or writes outside coef[0 .. coef_cap) and qt[0 .. 192), whatever the bytes are.
+ * A status other than 0 leaves its reason in fd_last_error() (thread-local): FD_JPEG_TRUNCATED when the data ends before the last
+ * block (or inside the headers), FD_JPEG_CORRUPT for an undefined Huffman code, a coefficient index above 63, a missing or wrong
+ * restart marker, a bad segment.
+ *   coef  the QUANTISED coefficients, int16 [blocks][64] in natural (row-major, de-zigzagged) order, component after component, each
+ *         component's blocks row-major over its PADDED block grid blocks_h[c] x blocks_w[c] (whole MCUs: blocks_w[0] = mcus_x * h_samp,
+ *         blocks_w[1] = blocks_w[2] = mcus_x; a greyscale frame has ceil(W / 8) x ceil(H / 8) blocks).  coef_cap counts int16 values;
+ *         info->coef_count of them are written (blocks past an end-of-block are zero).  The DC predictor wraps in int16.
+ *   qt    uint16 [3][64], natural order: the table of each component (greyscale: three copies). */
+#define FD_JPEG_OK 0
+#define FD_JPEG_BAD_ARGS 1
+#define FD_JPEG_NOT_JPEG 2
+#define FD_JPEG_UNCOVERED 3
+#define FD_JPEG_TRUNCATED 4
+#define FD_JPEG_CORRUPT 5
+#define FD_JPEG_CAPACITY 6
+typedef struct fd_jpeg_info {
+    int width, height;
+    int components;                  /* as the frame header says: 1, 3 (or 2, 4: not covered) */
+    int h_samp, v_samp;              /* luma sampling factors (1, 1 for greyscale); 0 when not covered */
+    int covered;
+    int blocks_w[3], blocks_h[3];    /* the padded block grid of each component */
+    int restart_interval;
+    int reserved;
+    long coef_count;                 /* int16 values the frame needs: 64 * the sum of blocks_w[c] * blocks_h[c] */
+} fd_jpeg_info;
+int fd_jpeg_probe(const unsigned char* file, long n, fd_jpeg_info* info);
+int fd_jpeg_entropy_decode(const unsigned char* file, long n, int16_t* coef, long coef_cap, uint16_t* qt /*[3][64]*/, fd_jpeg_info* info);
+
+/* The device half: one chunk of 1 <= N <= 65535 frames of different sizes and samplings in TWO launches whatever N is,
+ * no atomics, no workspace beyond the component planes the descriptors place inside `staging`.
+ *   staging   the device copy of the chunk's staging buffer, 16-byte aligned, staging_bytes long; every offset below is in bytes from it.
+ *   desc      DEVICE array of N fd_jpeg_desc, 8-byte aligned (it may lie inside staging).
+ *   out       uint8; frame n is written as [height][width][3] RGB at out + out_off.  16-byte stores at the address's 16-byte
+ *             boundaries, single bytes before the first and after the last boundary of a frame.
+ * kind 0 (coefficients): coef_off -> the int16 coefficients as fd_jpeg_entropy_decode writes them (16-byte aligned), qt_off -> its
+ *   uint16 [3][64] tables (16-byte aligned), plane_off -> room for the uint8 component planes, 8 * blocks_h[c] rows of 8 * blocks_w[c]
+ *   bytes, component after component (16-byte aligned; the planes need not be uploaded, and no other region may overlap them).
+ * kind 1 (raw): coef_off -> height * width * 3 bytes of RGB that a host decoder wrote; launch B copies them.
+ * A descriptor whose frame leaves `out`, whose width or height is outside 1 .. 65535 or whose 3 * width * height exceeds 2^31 - 1 is skipped.  A descriptor that is otherwise
+ * unusable - a region that leaves staging, a misaligned offset, an unknown kind, sampling or component count - yields a ZERO frame.  Nothing outside
+ * the two buffers is read or written.  Two calls on the same input give the same bytes.
+ *
+ * Launch A, per 8 x 8 block (jidctint.c, ISLOW; CONST_BITS = 13, PASS1_BITS = 2), all in int32 with wrap-around:
+ *   d[k] = coef[k] * qt[k]                                     a 32-bit product
+ *   the 1-D transform of eight values x0 .. x7 with the multipliers FIX(0.298631336) = 2446, FIX(0.390180644) = 3196, FIX(0.541196100) =
+ *   4433, FIX(0.765366865) = 6270, FIX(0.899976223) = 7373, FIX(1.175875602) = 9633, FIX(1.501321110) = 12299, FIX(1.847759065) = 15137,
+ *   FIX(1.961570560) = 16069, FIX(2.053119869) = 16819, FIX(2.562915447) = 20995, FIX(3.072711026) = 25172:
+ *     z1 = (x2 + x6) * 4433; t2 = z1 - x6 * 15137; t3 = z1 + x2 * 6270; t0 = (x0 + x4) << 13; t1 = (x0 - x4) << 13
+ *     t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2
+ *     o0 = x7, o1 = x5, o2 = x3, o3 = x1; z1 = o0 + o3; z2 = o1 + o2; z3 = o0 + o2; z4 = o1 + o3; z5 = (z3 + z4) * 9633
+ *     o0 *= 2446; o1 *= 16819; o2 *= 25172; o3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5
+ *     o0 += z1 + z3; o1 += z2 + z4; o2 += z2 + z3; o3 += z1 + z4
+ *     y0, y7 = t10 +- o3; y1, y6 = t11 +- o2; y2, y5 = t12 +- o1; y3, y4 = t13 +- o0
+ *   first down every column with y -> (y + (1 << 10)) >> 11, then along every row with y -> (y + (1 << 17)) >> 18 (arithmetic shifts;
+ *   libjpeg's all-zero shortcuts give the same values), then the sample = limit(y & 1023) with limit(i) = 128 + i for i < 128, 255 for
+ *   i < 512, 0 for i < 896, i - 896 above: the level shift and libjpeg's masked range-limit table in one.
+ * Launch B, per pixel (jdsample.c, jdcolor.c), dw = ceil(width / 2) and dh = ceil(height / 2) the chroma plane's REAL size:
+ *   1x1 and greyscale: the chroma sample is the pixel's own.
+ *   2x1 (h2v1 fancy): c = x >> 1, a = C[y][c]; even x: a at c = 0, else (3 a + C[y][c - 1] + 1) >> 2; odd x: a at c = dw - 1, else
+ *       (3 a + C[y][c + 1] + 2) >> 2.
+ *   2x2 (h2v2 fancy): r = y >> 1, far = r - 1 for an even y, r + 1 for an odd one, clamped to [0, dh - 1] (the real rows, not the padded
+ *       block rows); s(c) = 3 C[r][c] + C[far][c]; even x: (4 s(c) + 8) >> 4 at c = 0, else (3 s(c) + s(c - 1) + 8) >> 4; odd x:
+ *       (4 s(c) + 7) >> 4 at c = dw - 1, else (3 s(c) + s(c + 1) + 7) >> 4.
+ *   dw <= 2: plain replication, C[y >> (v_samp - 1)][x >> 1], as jinit_upsampler chooses.
+ *   R = clamp(Y + ((91881 * (Cr - 128) + 32768) >> 16)); B = clamp(Y + ((116130 * (Cb - 128) + 32768) >> 16));
+ *   G = clamp(Y + ((-22554 * (Cb - 128) + 32768 - 46802 * (Cr - 128)) >> 16)); arithmetic shifts, clamp to 0 .. 255.
+ *   Greyscale writes Y to the three channels.
+ * Bit-exactness: the result equals Pillow's (libjpeg-turbo's) decode for every stream whose dequantised coefficients d[k] fit int16 -
+ * every 8-bit encoder's output does.  Outside that range libjpeg's own paths disagree with each other; the result then follows the
+ * int32 rule above and is not pinned to Pillow. */
+typedef struct fd_jpeg_desc {
+    long coef_off;                   /* kind 0: the coefficients; kind 1: the RGB bytes */
+    long qt_off;
+    long plane_off;
+    long out_off;                    /* into `out` */
+    int kind;                        /* 0 coefficients, 1 raw RGB */
+    int width, height;
+    int components;                  /* 1 or 3 */
+    int h_samp, v_samp;              /* luma sampling: 1x1, 2x1 or 2x2 (1x1 for greyscale) */
+    int reserved[2];
+} fd_jpeg_desc;
+int fd_jpeg_reconstruct(void* staging, long staging_bytes, const fd_jpeg_desc* desc, int N, unsigned char* out, long out_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,13 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
                           ``torch.sort``-based median recipe of evaluate_depth.py on the same tensors (device events); then the kernels' own
                           times under ``rocprofv3 --kernel-trace --stats`` (a run of its own).
 
+ 12. ``jpeg``             ``--step jpeg`` (a run of its own, ``| tee profiles/jpeg_decode_time.log``): 36 JPEG frames of 1242x375 (4:2:2, quality
+                          92) through ``data_ops.decode_jpeg_batch`` and through pil_loader on 16 threads + np.stack + upload, alternating; the
+                          host Huffman phase, the upload and the two kernels against their traffic bound; the entropy decoder against
+                          Pillow's whole decode on one thread; ``KITTIRAWBatches`` items/s and Trainer images/s fed by either ``decoder=``.
+                          The kernels' own times: ``rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_loader.py --step
+                          jpeg_kernels``, then ``--step jpeg_trace_report --trace_dir DIR``.
+
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
 import argparse
@@ -340,6 +347,208 @@ def step_trainer(args):
             share = args.colour_ms * (per_step / BATCH) / (1e3 * syn)
             say("    condition: colour path %.3f ms per %d items = %.1f %% of the synthetic-fed step time (%.2f ms): %s the 10 %% limit"
                 % (args.colour_ms * per_step / BATCH, per_step, 100 * share, 1e3 * syn, "within" if share <= 0.10 else "ABOVE"))
+
+
+# ---------------------------------------------------------------------------------------------------- 12. JPEG frames on the device
+def write_jpeg_tree(root, n_frames):
+    """write_tree's layout with 4:2:2 JPEG frames at quality 92 (KITTI's own sampling) -> (split lines, frame paths, mean file bytes)."""
+    from PIL import Image
+    lines, _ = write_tree(root, n_frames, ())
+    folder = os.path.join(root, "2011_09_26", "2011_09_26_drive_0001_sync", "image_02/data")
+    paths = []
+    for i in range(n_frames):
+        paths.append(os.path.join(folder, "%010d.jpg" % i))
+        Image.fromarray(frame(1000 + i)).save(paths[-1], quality=92, subsampling=1)
+    return lines, paths, sum(os.path.getsize(p) for p in paths) / n_frames
+
+
+def _spread(v):
+    return "median %.2f, %.2f .. %.2f" % (float(np.median(v)), min(v), max(v))
+
+
+def step_jpeg(args):
+    """[12] ``data_ops.decode_jpeg_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
+    builder and the trainer fed by either route.  The routes alternate inside this one run."""
+    import concurrent.futures
+    import ctypes
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import _lib, data_ops
+    from fusiondepth_amd.datasets import KITTIRAWBatches, pil_loader
+    N = 36
+    with tempfile.TemporaryDirectory() as root:
+        lines, paths, mean_size = write_jpeg_tree(root, N + 14)
+        batch_paths = paths[:N]
+        say("[12] JPEG frames: %d frames of %dx%d, 4:2:2, quality 92, written by Pillow from textured synthetic content; %.0f KB per file "
+            "(entropy-decode time follows the file size; not a KITTI frame)" % (N, W0, H0, mean_size / 1e3))
+        pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
+
+        def route_device():
+            frames, stats = data_ops.decode_jpeg_batch(batch_paths, pool=pool)
+            torch.cuda.synchronize()
+            assert stats["fallback"] == 0, stats
+            return frames
+
+        def route_pil():
+            stack = torch.from_numpy(np.stack(list(pool.map(pil_loader, batch_paths)))).to("cuda", non_blocking=True)
+            torch.cuda.synchronize()
+            return stack
+
+        got, want = route_device(), route_pil()
+        assert all(torch.equal(g, w) for g, w in zip(got, want)), "the routes disagree"
+        t = {"device": [], "pil": []}
+        for _ in range(args.iters):
+            for name, fn in (("device", route_device), ("pil", route_pil)):
+                t0 = time.perf_counter()
+                fn()
+                t[name].append(1e3 * (time.perf_counter() - t0))
+        for name, label in (("device", "decode_jpeg_batch (host Huffman on %d threads + one upload + fd_jpeg_reconstruct)" % WORKERS),
+                            ("pil", "pil_loader on %d threads + np.stack + upload (the parent's route)" % WORKERS)):
+            med = float(np.median(t[name]))
+            say("    %-88s %7.1f frames/s, ms per batch of %d: %s  (%d alternating runs)" % (label + ":", 1e3 * N / med, N, _spread(t[name]), args.iters))
+
+        # one thread, per frame: the entropy decoder alone against Pillow's whole decode
+        datas = [open(p, "rb").read() for p in batch_paths]
+        info = data_ops.jpeg_probe(datas[0])[1]
+        coef, qt = np.empty(info.coef_count, np.int16), np.empty(192, np.uint16)
+        one = {"entropy": [], "pillow": []}
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for d in datas:
+                assert data_ops.jpeg_entropy_decode(d, coef, qt)[0] == 0
+            one["entropy"].append(1e3 * (time.perf_counter() - t0) / N)
+            t0 = time.perf_counter()
+            for p in batch_paths:
+                pil_loader(p)
+            one["pillow"].append(1e3 * (time.perf_counter() - t0) / N)
+        e1, p1 = min(one["entropy"]), min(one["pillow"])
+        say("    one thread, per frame: fd_jpeg_entropy_decode %.2f ms, Pillow's whole decode %.2f ms -> the hand-written entropy decoder is %s "
+            "than Pillow's whole decode (%.2fx)" % (e1, p1, "SLOWER" if e1 > p1 else "faster", p1 / e1))
+
+        # inside the batch
+        host_ms, up_ms, k_ms = [], [], []
+        for _ in range(args.iters):
+            t0 = time.perf_counter()
+            job = data_ops.JpegBatchJob(batch_paths, pool)
+            lay = job.wait_host()
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+            job.finish("cuda")                                   # writes the descriptor table into the staging buffer
+            torch.cuda.synchronize()
+            total = lay["total_bytes"]
+            dev = torch.empty((total,), dtype=torch.uint8, device="cuda")
+            out = torch.empty((N * 3 * H0 * W0 + 64,), dtype=torch.uint8, device="cuda")
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            dev[:lay["upload_bytes"]].copy_(lay["staging"], non_blocking=True)
+            ev[1].record()
+            ev[2].record()
+            _lib.call("fd_jpeg_reconstruct", dev.data_ptr(), total, dev.data_ptr(), N, out.data_ptr(), N * 3 * H0 * W0, _lib.stream())
+            ev[3].record()
+            torch.cuda.synchronize()
+            up_ms.append(ev[0].elapsed_time(ev[1]))
+            k_ms.append(ev[2].elapsed_time(ev[3]))
+        up_bytes, rgb_bytes = lay["upload_bytes"], N * 3 * H0 * W0
+        coef_bytes, plane_bytes = 2 * N * info.coef_count, N * info.coef_count
+        traffic = coef_bytes + 2 * plane_bytes + rgb_bytes
+        bound_ms = 1e3 * traffic / HBM_BPS
+        km = float(np.median(k_ms))
+        say("    inside the batch: host phase (read + probe + Huffman, %d threads) %s ms" % (WORKERS, _spread(host_ms)))
+        say("                      upload %.1f MB (int16 coefficients = %.2fx the RGB bytes) %s ms = %.1f GB/s"
+            % (up_bytes / 1e6, coef_bytes / rgb_bytes, _spread(up_ms), up_bytes / 1e6 / float(np.median(up_ms))))
+        say("                      the two kernels (device events around fd_jpeg_reconstruct) %s ms; traffic bound %.1f MB (coefficients in, "
+            "planes out and in, RGB out) at %.1f TB/s = %.4f ms -> %.1fx the bound" % (_spread(k_ms), traffic / 1e6, HBM_BPS / 1e12, bound_ms, km / bound_ms))
+
+        # the builder from the JPEG tree, both routes, alternating
+        opt = _opt(BATCH)
+
+        def run(decoder, epochs=2):
+            b = KITTIRAWBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".jpg", opt=opt, batch_size=BATCH, shuffle=True,
+                                seed=1, workers=WORKERS, decoder=decoder)
+            for _ in b:
+                pass
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 0
+            for _ in range(epochs):
+                for batch in b:
+                    n += batch[("color", 0, 0)].shape[0]
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            b.close()
+            return n / dt
+
+        rates = {"pil": [], "device": []}
+        for _ in range(5):
+            for name in ("pil", "device"):
+                rates[name].append(run(name, epochs=6))
+        sp = {k: max(v) - min(v) for k, v in rates.items()}
+        mp, md = float(np.median(rates["pil"])), float(np.median(rates["device"]))
+        say("    KITTIRAWBatches from the JPEG tree, batch %d, %d items per epoch, 5 alternating runs of 6 epochs each:" % (BATCH, len(lines)))
+        say("        decoder='pil':    %7.1f items/s (runs %s; spread %.1f)" % (mp, " ".join("%.1f" % v for v in rates["pil"]), sp["pil"]))
+        say("        decoder='device': %7.1f items/s (runs %s; spread %.1f)" % (md, " ".join("%.1f" % v for v in rates["device"]), sp["device"]))
+        say("        difference %+.1f items/s against the larger spread %.1f: the device route %s"
+            % (md - mp, max(sp.values()), "WINS" if md - mp > max(sp.values()) else ("LOSES" if mp - md > max(sp.values()) else "is within the spread")))
+        pool.shutdown()
+
+        if args.windows > 0:
+            from fusiondepth_amd.trainer import Trainer
+            torch.manual_seed(1)
+            tr = Trainer(opt, verbose=False)
+            per_step = tr.batch_size * tr.accumulate_step
+            feeds = {}
+            for name in ("pil", "device"):
+                b = KITTIRAWBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".jpg", opt=opt, batch_size=tr.batch_size,
+                                    shuffle=True, seed=1, workers=WORKERS, decoder=name)
+
+                def endless(b=b):
+                    while True:
+                        for batch in b:
+                            yield batch
+                feeds[name] = (b, endless())
+            res = {"pil": [], "device": []}
+            for name in feeds:
+                for _ in range(3):
+                    tr.train_step([next(feeds[name][1]) for _ in range(tr.accumulate_step)])
+            for _ in range(args.windows):
+                for name in ("pil", "device"):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        tr.train_step([next(feeds[name][1]) for _ in range(tr.accumulate_step)])
+                    torch.cuda.synchronize()
+                    res[name].append((time.perf_counter() - t0) / args.steps)
+            for name in feeds:
+                feeds[name][0].close()
+                m = float(np.median(res[name]))
+                say("    Trainer (ResNet-18, %dx%d, %d images / step) fed by decoder='%s': %s %.1f images/s (%.2f ms / step; windows %s)"
+                    % (WIDTH, HEIGHT, per_step, name, " " * (6 - len(name)), per_step / m, 1e3 * m, " ".join("%.2f" % (1e3 * v) for v in res[name])))
+        say("    not measured: a real KITTI tree; JPEG files written by other encoders")
+
+
+def step_jpeg_kernels(args):
+    """3 + ``--iters`` batches of 36 frames through ``decode_jpeg_batch``, for ``rocprofv3 --kernel-trace --stats -d DIR -- ...``."""
+    import torch
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import data_ops
+    with tempfile.TemporaryDirectory() as root:
+        _, paths, _ = write_jpeg_tree(root, 36)
+        for _ in range(3 + args.iters):
+            data_ops.decode_jpeg_batch(paths)
+            torch.cuda.synchronize()
+
+
+def step_jpeg_trace_report(args):
+    """The two kernels' own times from the rocprofv3 results database of a traced ``--step jpeg_kernels`` run."""
+    import sqlite3
+    files = sorted(glob.glob(os.path.join(args.trace_dir, "**", "*_results.db"), recursive=True))
+    if not files:
+        sys.exit("no rocprofv3 results database under %s" % args.trace_dir)
+    db = sqlite3.connect(files[-1])
+    rows = list(db.execute("select name, count(*), sum(end-start)/1e3, avg(end-start)/1e3 from kernels group by name order by 3 desc"))
+    say("    rocprofv3 --kernel-trace --stats, %d batches of 36 frames (a run of its own):" % (3 + args.iters))
+    for r in rows:
+        if "k_jpeg" in r[0]:
+            say("      %-30s %6d calls, %8.1f us / batch" % (r[0].replace("(anonymous namespace)::", "").split("(")[0], r[1], r[3]))
 
 
 # ---------------------------------------------------------------------------------------------------- 5-8. raw Velodyne scans
@@ -920,7 +1129,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
                                                       "raw_builder", "raw_trainer", "offline", "offline_worker", "refiner", "inf_gdc_key", "gdc_trace_report",
-                                                      "refiner_trainer", "completion", "completion_keys", "completion_trace_report"])
+                                                      "refiner_trainer", "completion", "completion_keys", "completion_trace_report", "jpeg", "jpeg_kernels",
+                                                      "jpeg_trace_report"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default="")
     ap.add_argument("--split_file", default="")
@@ -940,7 +1150,8 @@ def main():
      "refiner_trainer": step_refiner_trainer, "raw": drive_raw, "sparsify": step_sparsify, "raw_builder": step_raw_builder,
      "raw_trainer": step_raw_trainer, "offline": step_offline, "offline_worker": step_offline_worker, "all": drive, "colour": step_colour,
      "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker, "builder": step_builder,
-     "trainer": step_trainer}[args.step](args)
+     "trainer": step_trainer, "jpeg": step_jpeg, "jpeg_kernels": step_jpeg_kernels,
+     "jpeg_trace_report": step_jpeg_trace_report}[args.step](args)
 
 
 if __name__ == "__main__":
