@@ -119,6 +119,20 @@ class JpegDesc(ctypes.Structure):
 assert ctypes.sizeof(JpegInfo) == 64 and ctypes.sizeof(JpegDesc) == 64
 
 
+class PngInfo(ctypes.Structure):
+    """Mirror of ``fd_png_info``."""
+    _fields_ = [(n, _I) for n in ("width", "height", "bit_depth", "colour_type", "interlace", "covered", "bpp", "reserved")] + \
+               [("row_bytes", _L), ("raw_bytes", _L), ("reserved2", _L * 2)]
+
+
+class PngDesc(ctypes.Structure):
+    """Mirror of ``fd_png_desc``."""
+    _fields_ = [("raw_off", _L), ("out_off", _L)] + [(n, _I) for n in ("kind", "width", "height", "bpp", "mode")] + [("reserved", _I * 3)]
+
+
+assert ctypes.sizeof(PngInfo) == 64 and ctypes.sizeof(PngDesc) == 48
+
+
 class LogCfg(ctypes.Structure):
     """Mirror of ``fd_log_cfg``."""
     _fields_ = [("Hs", _I), ("Ws", _I), ("n_rows", _I), ("n_disp", _I), ("row_y", _I * 8), ("row_h", _I * 8), ("row_first", _I * 8),
@@ -266,6 +280,10 @@ SIGNATURES = {
     "fd_jpeg_probe": ("plp", "i"),
     "fd_jpeg_entropy_decode": ("pl" "pl" "pp", "i"),
     "fd_jpeg_reconstruct": ("pl" "pi" "pl" "p", "i"),
+    "fd_png_probe": ("plp", "i"),
+    "fd_png_inflate": ("pl" "pl" "p", "i"),
+    "fd_png_band_rows": ("", "i"),
+    "fd_png_unfilter": ("pl" "pi" "pl" "p", "i"),
 }
 
 _lock = threading.Lock()

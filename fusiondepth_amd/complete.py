@@ -1,7 +1,7 @@
 """The reference's ``python completor.py`` as a command: options -> loaders -> ``Completor.train`` with in-training validation.
 
     python -m fusiondepth_amd.complete [reference flags] [--seed N] [--val_limit N] [--no_val] [--val_route fused|per_batch]
-                                       [--image_decoder pil|device]
+                                       [--image_decoder pil|device] [--png_decoder pil|device]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.complete ...       # data parallel, one rank per GPU
 
   * ``build_loaders(opt, rank, world_size, ...)``  completor.py:132-152: both loaders are ``KITTICompletionBatches`` over
@@ -40,7 +40,7 @@ from .evaluate_depth import split_off_flags
 from .train import decode_workers, take_image_decoder, write_summary
 
 DEFAULT_VAL_ROUTE = "fused"            # decided by profiles/completion_val_time.log
-EXTRA_VALUED = {"seed": "0", "val_limit": None, "val_route": DEFAULT_VAL_ROUTE, "image_decoder": None}
+EXTRA_VALUED = {"seed": "0", "val_limit": None, "val_route": DEFAULT_VAL_ROUTE, "image_decoder": None, "png_decoder": None}
 EXTRA_SWITCHES = ("no_val",)
 
 
@@ -48,7 +48,9 @@ def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({seed, val_limit, val_route, no_val,
     load_weights_given}, the remaining arguments).  ``load_weights_given``: ``--load_weights_folder`` is spelled out in ``argv`` (it
     stays among the remaining arguments).  ``image_decoder`` ('pil' or 'device') joins the dict only where ``--image_decoder`` is
-    given; the completion tree's colour frames are PNG files, so both values decode with Pillow."""
+    given; the completion tree's colour frames are PNG files, so both values decode with Pillow.  ``png_decoder`` likewise joins only
+    where ``--png_decoder`` is given: 'device' unfilters the 16-bit depth PNGs of every batch on the device (the colour frames, whose
+    crop, pad and mirror run on the host threads, stay with Pillow)."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     take_image_decoder(found)
     found["seed"] = int(found["seed"])
@@ -63,13 +65,14 @@ def split_off_extra(argv):
 
 
 def build_loaders(opt, rank=0, world_size=1, seed=0, val_limit=None, no_val=False, local_world_size=None, device="cuda",
-                  image_decoder="pil"):
+                  image_decoder="pil", png_decoder="pil"):
     """completor.py:132-152 -> ``(train_loader, val_loader)``; the second is None with ``no_val``.  ``opt`` should be the
     ``Completor``'s own options (its constructor sets the full-resolution size).  The validation loader is never sharded."""
     from .completion_data import KITTICompletionBatches
     tree = os.path.join(opt.data_path, "completion")
     workers = decode_workers(opt.num_workers, world_size if local_world_size is None else local_world_size)
-    common = dict(val_split=opt.completion_val_split, opt=opt, seed=seed, device=device, workers=workers, decoder=image_decoder)
+    common = dict(val_split=opt.completion_val_split, opt=opt, seed=seed, device=device, workers=workers, decoder=image_decoder,
+                  png_decoder=png_decoder)
     train_loader = KITTICompletionBatches(tree, opt.height, opt.width, list(opt.frame_ids), 4, is_train=True, batch_size=opt.batch_size,
                                           shuffle=True, drop_last=True, rank=rank, world_size=world_size, **common)
     val_loader = None
@@ -103,7 +106,8 @@ def main(argv=None):
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader = build_loaders(completor.opt, rank, world, seed=extra["seed"], val_limit=extra["val_limit"],
                                              no_val=extra["no_val"] or rank != 0, local_world_size=local_world, device=completor.device,
-                                             image_decoder=extra.get("image_decoder", "pil"))
+                                             image_decoder=extra.get("image_decoder", "pil"),
+                                             png_decoder=extra.get("png_decoder", "pil"))
     if val_loader is not None and extra["val_route"] == "fused":
         completor.val_scorer = val_scorer_for(completor.opt, val_loader, completor.device)
     try:

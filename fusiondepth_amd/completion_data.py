@@ -209,11 +209,14 @@ class KITTICompletionBatches(KITTIRAWBatches):
     """See the module docstring.  The first eight arguments are ``KITTICompletion``'s (``data_path`` is the completion tree);
     the others are ``KITTIRAWBatches``'.  The split is ``train`` if ``is_train`` else ``val`` (``val_split`` = "select" / "full"), and
     ``test_completion`` when ``opt.completion_test``.  ``decoder="device"`` is accepted and changes nothing: the colour frames of
-    the completion tree are PNG files, which stay with Pillow."""
+    the completion tree are PNG files.  ``png_decoder="device"`` moves the 16-bit depth PNGs of every batch (beam planes, ``depth_gt``,
+    ``full_res_4beam``) to ``data_ops.PngBatchJob``: inflated on the pool, unfiltered by ``fd_png_unfilter`` straight into the planes
+    ``fd_depth_png_keys`` reads, every key bit for bit the ``pil`` route's; the reference's 16-bit assertion then costs one small
+    download per batch.  The colour frames stay with Pillow either way: their crop, pad and mirror run on the host threads."""
 
     def __init__(self, data_path, height, width, frame_idxs, num_scales, is_train=False, val_split="select", opt=None, batch_size=1,
                  shuffle=False, seed=0, device="cuda", workers=8, draws=None, loader=None, prefetch=True, drop_last=True,
-                 rank=0, world_size=1, decoder="pil"):
+                 rank=0, world_size=1, decoder="pil", png_decoder="pil"):
         if opt is None:
             raise ValueError("KITTICompletionBatches: opt is required (completion_not_full_res, completion_test, ...)")
         self.full_res = not getattr(opt, "completion_not_full_res", False)
@@ -227,7 +230,8 @@ class KITTICompletionBatches(KITTIRAWBatches):
         self.paths = completion_paths(data_path, self.split, val_split)
         super().__init__(data_path, self.paths["rgb"], height, width, frame_idxs, num_scales, is_train=is_train, img_ext=".png", opt=opt,
                          batch_size=batch_size, shuffle=shuffle, seed=seed, device=device, workers=workers, draws=draws, loader=loader,
-                         prefetch=prefetch, drop_last=drop_last, rank=rank, world_size=world_size, decoder=decoder)
+                         prefetch=prefetch, drop_last=drop_last, rank=rank, world_size=world_size, decoder=decoder,
+                         png_decoder=png_decoder)
         self.frames = list(self.frame_idxs) if self.is_train else [0]
         self.eval_gdc = bool(self._opt("eval_gdc"))
 
@@ -316,13 +320,20 @@ class KITTICompletionBatches(KITTIRAWBatches):
         plan = self._plan_depth(items)
         if not plan["tables"]:
             return None
-        staging = torch.empty((plan["bytes"],), dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        on_device = self.png_decoder == "device"
+        size = plan["data"][0] if on_device else plan["bytes"]   # the device route uploads the tables alone from here
+        staging = torch.empty((max(size, 16),), dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         host = staging.numpy()
         for name, descs in plan["tables"].items():
             host[plan[name][0]:plan[name][1]] = np.frombuffer(data_ops.depth_png_desc_table(descs), dtype=np.uint8)
+        plan["staging"] = staging
+        if on_device:
+            plan["paths"] = list(plan["planes"])
+            plan["job"] = data_ops.PngBatchJob(plan["paths"], pool, mode="gray16")
+            plan["futures"] = []
+            return plan
         data = host[plan["data"][0]:plan["data"][1]].view(np.uint16)
         plan["futures"] = [pool.submit(_depth_into, path, data[off:off + h * w].reshape(h, w)) for path, (off, h, w) in plan["planes"].items()]
-        plan["staging"] = staging
         return plan
 
     def __iter__(self):
@@ -368,6 +379,31 @@ class KITTICompletionBatches(KITTIRAWBatches):
                 for name in ("color", "color_aug"):
                     batch[(name, f, s)] = pyr[(name, s)][fi * B:(fi + 1) * B]
 
+    def _unfilter_depth(self, plan):
+        """The device route of the depth planes: the tables are uploaded, ``fd_png_unfilter`` writes the host-order uint16 planes
+        at the offsets ``_plan_depth`` chose, and the reference's 16-bit assertion reads one byte per plane back."""
+        job = plan["job"]
+        job.wait_host()
+        table = job.layout()[0]
+        for d, path, (_, _, h, w) in zip(table, plan["paths"], job._slots):
+            off, ph, pw = plan["planes"][path]
+            if (h, w) != (ph, pw):
+                raise RuntimeError("KITTICompletionBatches: %s changed size while it was read (%s, planned %s)" % (path, (h, w), (ph, pw)))
+            d.out_off = 2 * off
+        lo, hi = plan["data"]
+        dev = torch.empty((max(plan["bytes"], 16),), dtype=torch.uint8, device=self.device)
+        dev[:lo].copy_(plan["staging"][:lo], non_blocking=True)
+        with torch.cuda.device(self.device):
+            stats = job.run(self.device, dev[lo:hi], table)
+        for name in stats:
+            self.decode_stats[name] += stats[name]
+        planes = [dev[lo + 2 * off:lo + 2 * (off + h * w)] for off, h, w in (plan["planes"][p] for p in plan["paths"])]
+        high = torch.stack([p[1::2].amax() for p in planes]).cpu()              # a 16-bit map has a value above 255
+        for path, p, top in zip(plan["paths"], planes, high.tolist()):
+            if not top > 0:                                      # make sure we have a proper 16bit depth map here.. not 8bit!
+                raise AssertionError("np.max(depth_png)={}, path={}".format(int(p[0::2].amax()), path))
+        return dev
+
     def _depth_keys(self, items, batch):
         """One upload, then ``fd_depth_png_keys`` per key and at most one scatter (module docstring)."""
         plan = items[0]["depth_plan"]
@@ -375,7 +411,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
             return
         for f in plan["futures"]:
             f.result()                                           # the 16-bit assertion raises here, with the path
-        dev = _upload(plan["staging"], self.device)
+        dev = self._unfilter_depth(plan) if "job" in plan else _upload(plan["staging"], self.device)
         B = len(items)
         packed = dev[plan["data"][0]:plan["data"][1]].view(torch.int16)
         pool = 1 if self.full_res else 2

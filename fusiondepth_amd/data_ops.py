@@ -546,14 +546,15 @@ class JpegBatchJob:
     worker that finishes the last probe lays out ONE pinned staging buffer (descriptors, then per frame its tables and coefficients
     or, for a frame Pillow decodes, its RGB bytes) and submits the entropy decoders, each writing straight into its slice.
     ``finish(device)`` waits, uploads the buffer once and calls ``fd_jpeg_reconstruct`` once."""
+    NAME = "decode_jpeg_batch"
 
     def __init__(self, files, pool=None):
         import threading
         self.files = list(files)
         if not self.files:
-            raise ValueError("decode_jpeg_batch: no files")
+            raise ValueError("%s: no files" % self.NAME)
         if len(self.files) > 65535:
-            raise ValueError("decode_jpeg_batch: %d files in one call; the kernel takes 65535" % len(self.files))
+            raise ValueError("%s: %d files in one call; the kernel takes 65535" % (self.NAME, len(self.files)))
         self.pool = pool if pool is not None else jpeg_pool()
         self._lock, self._ready, self._error = threading.Lock(), threading.Event(), None
         self._left = len(self.files)
@@ -570,11 +571,7 @@ class JpegBatchJob:
             else:
                 with open(f, "rb") as fh:
                     data = fh.read()
-            st, info = jpeg_probe(data)
-            if st == 0 and info.covered:
-                self._probed[i] = (data, info, None)
-            else:                                                # not covered, or not a JPEG at all: Pillow decides
-                self._probed[i] = (data, None, _pil_rgb(data))
+            self._probed[i] = self._probe_one(data)
         except BaseException as e:                               # noqa: B902 - handed to finish()
             with self._lock:
                 self._error = self._error or e
@@ -583,6 +580,13 @@ class JpegBatchJob:
             last = self._left == 0
         if last:
             self._plan()
+
+    def _probe_one(self, data):
+        """-> (data, info of a frame the device half takes, or None with the frame Pillow decoded)."""
+        st, info = jpeg_probe(data)
+        if st == 0 and info.covered:
+            return data, info, None
+        return data, None, _pil_rgb(data)                        # not covered, or not a JPEG at all: Pillow decides
 
     def _plan(self):
         try:
@@ -650,7 +654,7 @@ class JpegBatchJob:
         self.wait_host()
         device = torch.device(device)
         if device.type != "cuda":
-            raise RuntimeError("decode_jpeg_batch runs on the GPU only (got %s); there is no CPU path" % device)
+            raise RuntimeError("%s runs on the GPU only (got %s); there is no CPU path" % (self.NAME, device))
         with torch.cuda.device(device):
             return self._finish_on(device)
 
@@ -700,6 +704,175 @@ def decode_jpeg_batch(files, device="cuda", pool=None):
     by ``fd_jpeg_reconstruct``; everything else - progressive, CMYK, a PNG, a damaged stream - is decoded by Pillow into the same
     staging buffer and copied by the same call.  One host-to-device copy and one library call whatever the number of files."""
     groups, stats = JpegBatchJob(files, pool).finish(device)
+    frames = [None] * len(files)
+    for stack, idx in groups.values():
+        for k, i in enumerate(idx):
+            frames[i] = stack[k]
+    return frames, stats
+
+
+# ------------------------------------------------------------------------------------------------ PNG frames -------
+# Pillow's decode of a PNG, split as include/fdhip.h ("PNG frames") describes: the chunk walk and the inflate on a host pool behind
+# the C ABI (ctypes releases the interpreter lock), the scanline filters in csrc/png.hip.  tests/png_ref.py restates it.
+PNG_BAND_ROWS = 512          # FD_PNG_BAND_ROWS: the rows one workgroup of k_png_unfilter holds at a time
+PNG_MODES = {"rgb": 0, "gray16": 1}
+
+
+def png_probe(data):
+    """``fd_png_probe`` of a bytes-like object -> (status, PngInfo).  Host only."""
+    info = _lib.PngInfo()
+    buf = (ctypes.c_ubyte * len(data)).from_buffer_copy(data) if not isinstance(data, bytes) else data
+    return _lib.load().fd_png_probe(buf, len(data), ctypes.byref(info)), info
+
+
+def png_inflate(data, dst):
+    """``fd_png_inflate`` into ``dst`` (a contiguous uint8 numpy array; its size is ``dst_cap``) -> (status, PngInfo).  Host only; the
+    reason of a non-zero status is ``_lib.last_error()`` on the calling thread."""
+    info = _lib.PngInfo()
+    buf = (ctypes.c_ubyte * len(data)).from_buffer_copy(data) if not isinstance(data, bytes) else data
+    return _lib.load().fd_png_inflate(buf, len(data), dst.ctypes.data, dst.size, ctypes.byref(info)), info
+
+
+def _pil_gray16(data, name="<bytes>"):
+    """``np.asarray(Image.open(f))`` as uint16, with the completion loader's single-channel-integer check."""
+    import io
+    import numpy as np
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as img:
+        a = np.asarray(img)
+    if a.ndim != 2 or a.dtype.kind not in "ui":
+        raise RuntimeError("decode_png_batch: %s decoded to %s %s, expected a single-channel integer depth map" % (name, a.dtype, a.shape))
+    if a.size and (int(a.max()) > 65535 or int(a.min()) < 0):
+        raise RuntimeError("decode_png_batch: %s holds values outside 16 bits" % name)
+    return a.astype(np.uint16)
+
+
+class PngBatchJob(JpegBatchJob):
+    """The host side of ``decode_png_batch``; ``JpegBatchJob``'s structure: every file is read and probed on ``pool``; the worker
+    that finishes the last probe lays out ONE pinned staging buffer (descriptors, then per frame its filtered scanlines or, for a frame
+    Pillow decodes, its finished bytes) and submits the inflates, each writing straight into its slice with the interpreter lock
+    released.  ``finish(device)`` waits, uploads the buffer once and calls ``fd_png_unfilter`` once.  ``mode``: ``"rgb"`` (8-bit RGB
+    and grey files on the device, uint8 [H, W, 3] frames) or ``"gray16"`` (16-bit grey files on the device, uint16 [H, W] frames);
+    every other file is Pillow's."""
+    NAME = "decode_png_batch"
+
+    def __init__(self, files, pool=None, mode="rgb"):
+        if mode not in PNG_MODES:
+            raise ValueError("decode_png_batch: mode must be 'rgb' or 'gray16', got %r" % (mode,))
+        self.mode = mode
+        self._elem = 2 if mode == "gray16" else 3                # output bytes per pixel
+        super().__init__(files, pool)
+
+    def _pil(self, data, i):
+        name = self.files[i] if isinstance(self.files[i], str) else "<bytes %d>" % i
+        return _pil_gray16(data, name) if self.mode == "gray16" else _pil_rgb(data)
+
+    def _probe_one(self, data):
+        st, info = png_probe(data)
+        if st == 0 and info.covered and (info.bpp == 2) == (self.mode == "gray16"):
+            return data, info, None
+        return data, None, False                                 # Pillow decodes it in _decode, straight into the buffer
+
+    def _plan(self):
+        try:
+            if self._error is not None:
+                return
+            import io
+            from PIL import Image
+            n = len(self.files)
+            at = _round16(n * ctypes.sizeof(_lib.PngDesc))
+            self._slots = []
+            for data, info, _ in self._probed:
+                if info is not None:
+                    h, w, need = info.height, info.width, info.raw_bytes
+                else:                                            # the size from the header alone; Pillow raises for what it cannot open
+                    with Image.open(io.BytesIO(data)) as img:
+                        w, h = img.size
+                    need = 0
+                size = _round16(max(need, self._elem * h * w))   # a frame whose inflate fails gets Pillow's bytes instead
+                self._slots.append((at, size, h, w))
+                at += size
+            self._upload_bytes, self._plane_bytes = at, 0
+            self._staging = torch.empty((at,), dtype=torch.uint8, pin_memory=True)
+            self._host = self._staging.numpy()
+            self._kinds = [1] * n
+            self._futures = [self.pool.submit(self._decode, i) for i in range(n)]
+        except BaseException as e:                               # noqa: B902
+            self._error = e
+        finally:
+            self._ready.set()
+
+    def _decode(self, i):
+        import numpy as np
+        data, info, _ = self._probed[i]
+        at, size, h, w = self._slots[i]
+        if info is not None:
+            st, _ = png_inflate(data, self._host[at:at + info.raw_bytes])
+            if st == 0:
+                self._kinds[i] = 0
+                return
+        px = self._pil(data, i)                                  # not covered, or damaged: as tolerant, or as strict, as Pillow is
+        if px.shape[:2] != (h, w):
+            raise RuntimeError("decode_png_batch: Pillow decoded %s, the header says %s" % (px.shape[:2], (h, w)))
+        self._host[at:at + self._elem * h * w] = np.ascontiguousarray(px).reshape(-1).view(np.uint8)
+
+    def descriptors(self):
+        """A copy of the ``fd_png_desc`` table ``finish`` wrote (a ctypes array of ``_lib.PngDesc``)."""
+        n = len(self.files)
+        return (_lib.PngDesc * n).from_buffer_copy(self._host[:n * ctypes.sizeof(_lib.PngDesc)].tobytes())
+
+    def layout(self, out_base=0):
+        """-> (table, out_off per frame, {(h, w): first byte}, {(h, w): indices}, out bytes): same-size frames contiguous, in order of
+        first appearance, the groups 16-byte aligned from ``out_base`` on."""
+        n = len(self.files)
+        members = {}
+        for i, (_, _, h, w) in enumerate(self._slots):
+            members.setdefault((h, w), []).append(i)
+        out_off, at, spans = [0] * n, out_base, {}
+        for (h, w), idx in members.items():
+            spans[(h, w)] = at
+            for i in idx:
+                out_off[i] = at
+                at += self._elem * h * w
+            at = _round16(at)
+        table = (_lib.PngDesc * n)()
+        for i, (d, (slot, _, h, w)) in enumerate(zip(table, self._slots)):
+            info = self._probed[i][1]
+            d.kind, d.width, d.height, d.raw_off, d.out_off, d.mode = self._kinds[i], w, h, slot, out_off[i], PNG_MODES[self.mode]
+            d.bpp = info.bpp if self._kinds[i] == 0 else 0
+        return table, out_off, spans, members, max(at, 16)
+
+    def run(self, device, out, table):
+        """Upload the staging buffer (with ``table`` at its head) and make the one library call into ``out``, a uint8 device tensor."""
+        import numpy as np
+        n = len(self.files)
+        self._host[:n * ctypes.sizeof(_lib.PngDesc)] = np.frombuffer(table, dtype=np.uint8)
+        dev = torch.empty((self._upload_bytes,), dtype=torch.uint8, device=device)
+        dev.copy_(self._staging, non_blocking=True)              # the batch's one host-to-device copy
+        call("fd_png_unfilter", dev.data_ptr(), self._upload_bytes, ctypes.addressof(table), n, out.data_ptr(), out.numel(), stream())
+        device_n = sum(1 for k in self._kinds if k == 0)
+        return {"device": device_n, "fallback": n - device_n}
+
+    def _finish_on(self, device):
+        table, _, spans, members, out_bytes = self.layout()
+        out = torch.empty((out_bytes,), dtype=torch.uint8, device=device)
+        stats = self.run(device, out, table)
+        groups = {}
+        for (h, w), idx in members.items():
+            flat = out[spans[(h, w)]:spans[(h, w)] + len(idx) * self._elem * h * w]
+            groups[(h, w)] = (flat.view(torch.uint16).view(len(idx), h, w) if self.mode == "gray16" else flat.view(len(idx), h, w, 3), idx)
+        return groups, stats
+
+
+def decode_png_batch(files, device="cuda", pool=None, mode="rgb"):
+    """``np.asarray(Image.open(f).convert("RGB"))`` of every file (``mode="rgb"``: uint8 [H, W, 3]) or ``np.asarray(Image.open(f))`` of
+    every 16-bit depth map (``mode="gray16"``: uint16 [H, W]), value for value, on the device.  ``files``: paths or ``bytes``.
+    Returns ``(frames, stats)``: a list of device tensors - views into one buffer, same-size frames contiguous - and ``{"device": n,
+    "fallback": n}``.  Covered files (include/fdhip.h: non-interlaced 8-bit RGB and 8-bit grey in ``rgb`` mode, 16-bit grey in
+    ``gray16`` mode) are inflated on the host pool and unfiltered by ``fd_png_unfilter``; everything else - palette, alpha, tRNS,
+    Adam7, other depths, a damaged file, a JPEG - is decoded by Pillow into the same staging buffer and copied by the same call.
+    One host-to-device copy and one library call whatever the number of files."""
+    groups, stats = PngBatchJob(files, pool, mode).finish(device)
     frames = [None] * len(files)
     for stack, idx in groups.values():
         for k, i in enumerate(idx):

@@ -128,12 +128,15 @@ class KITTIRAWBatches:
     ``sparsify_grid`` = (H, W) of its angular grid, ``rank`` / ``world_size`` = this process's shard of every epoch (data-parallel
     training; the defaults give the whole epoch, exactly as before), ``decoder`` = ``"pil"`` (Pillow on the pool, the default) or
     ``"device"`` (``data_ops.JpegBatchJob``: Huffman decoding on the pool, the rest in HIP, byte for byte Pillow's frames;
-    ``decode_stats`` counts the frames each way; a ``.png`` tree keeps Pillow, ``loader=`` with it raises)."""
+    ``decode_stats`` counts the frames each way; it is for JPEG frames and changes nothing for a ``.png`` tree, ``loader=`` with it
+    raises), ``png_decoder`` = the same choice for a ``.png`` tree (``data_ops.PngBatchJob``: the inflate on the pool, the scanline
+    filters in HIP, byte for byte Pillow's frames, counted in ``decode_stats`` too; it changes nothing for a JPEG tree, ``loader=``
+    with it raises)."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext=".jpg", opt=None,
                  batch_size=1, shuffle=False, seed=0, device="cuda", workers=8, jitter_per_image=False, draws=None, loader=None,
                  prefetch=True, lidar_source="files", line_spec=None, sparsify_grid=(64, 1024), drop_last=True, rank=0, world_size=1,
-                 decoder="pil"):
+                 decoder="pil", png_decoder="pil"):
         self.data_path, self.filenames = data_path, list(filenames)
         self.height, self.width, self.num_scales = int(height), int(width), int(num_scales)
         self.frame_idxs = list(frame_idxs)
@@ -148,8 +151,13 @@ class KITTIRAWBatches:
             raise ValueError("KITTIRAWBatches: decoder must be 'pil' or 'device', got %r" % (decoder,))
         if decoder == "device" and loader is not None:
             raise ValueError("KITTIRAWBatches: decoder='device' decodes the files itself; it cannot be combined with loader=")
-        # a .png tree stays with Pillow (inflate is serial): the device route is for JPEG frames
+        if png_decoder not in ("pil", "device"):
+            raise ValueError("KITTIRAWBatches: png_decoder must be 'pil' or 'device', got %r" % (png_decoder,))
+        if png_decoder == "device" and loader is not None:
+            raise ValueError("KITTIRAWBatches: png_decoder='device' decodes the files itself; it cannot be combined with loader=")
+        # each argument speaks for its own kind of tree: decoder= for JPEG frames, png_decoder= for PNG frames
         self.decoder = decoder if str(img_ext).lower() in (".jpg", ".jpeg") else "pil"
+        self.png_decoder = png_decoder if str(img_ext).lower() == ".png" else "pil"
         self.decode_stats = {"device": 0, "fallback": 0}
         if self.batch_size < 1:
             raise ValueError("KITTIRAWBatches: batch_size must be positive")
@@ -349,10 +357,12 @@ class KITTIRAWBatches:
         """Submit the file work of a batch to the pool."""
         items = self.plan_batch(epoch, indices)
         pool = self._workers()
-        if self.decoder == "device":                             # frame-major, the order of every colour key
-            items[0]["jpeg_job"] = data_ops.JpegBatchJob([it["images"][fi] for fi in range(len(self.frame_idxs)) for it in items], pool)
+        on_device = self.decoder == "device" or self.png_decoder == "device"
+        if on_device:                                            # frame-major, the order of every colour key
+            job = data_ops.JpegBatchJob if self.decoder == "device" else data_ops.PngBatchJob
+            items[0]["decode_job"] = job([it["images"][fi] for fi in range(len(self.frame_idxs)) for it in items], pool)
         for it in items:
-            if self.decoder != "device":
+            if not on_device:
                 it["image_futures"] = [pool.submit(self.loader, p) for p in it["images"]]
             if self.lidar_source == "raw":
                 continue
@@ -372,8 +382,8 @@ class KITTIRAWBatches:
     def _colour_keys(self, items, batch):
         B, F = len(items), len(self.frame_idxs)
         groups, stacks = {}, {}                                  # native size -> [(frame slot, item)]: drives differ in size
-        if "jpeg_job" in items[0]:                               # decoded on the device: the stacks are views of one buffer
-            decoded, stats = items[0]["jpeg_job"].finish(self.device)
+        if "decode_job" in items[0]:                             # decoded on the device: the stacks are views of one buffer
+            decoded, stats = items[0]["decode_job"].finish(self.device)
             for name in stats:
                 self.decode_stats[name] += stats[name]
             for (h, w), (stack, idx) in decoded.items():

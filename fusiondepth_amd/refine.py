@@ -1,7 +1,7 @@
 """The reference's ``python refiner.py`` as a command: options -> loaders -> ``Refiner.train`` with in-training validation.
 
     python -m fusiondepth_amd.refine [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
-                                     [--image_decoder pil|device]
+                                     [--image_decoder pil|device] [--png_decoder pil|device]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.refine ...         # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  refiner.py:168-200: the training lines of
@@ -30,7 +30,7 @@ from .train import _read_lines, decode_workers, split_off_extra, write_summary
 
 
 def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_source="files", val_limit=None, no_val=False,
-                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil"):
+                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil"):
     """refiner.py:168-200 -> ``(train_loader, val_loader, gt_depths)``; the last two are None with ``no_val``.  The arguments are
     ``train.build_loaders``'.  ``opt`` should be the ``Refiner``'s own options (its constructor sets ``clone_gdc``, which makes the
     training loader add ``inf_gdc``)."""
@@ -47,7 +47,7 @@ def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_
     train_lines = _read_lines(os.path.join(splits_dir, opt.split, "train_files.txt"))
     workers = decode_workers(opt.num_workers, world_size if local_world_size is None else local_world_size)
     common = dict(img_ext=".png" if opt.png else ".jpg", opt=opt, seed=seed, device=device, workers=workers, lidar_source=lidar_source,
-                  decoder=image_decoder)
+                  decoder=image_decoder, png_decoder=png_decoder)
     train_loader = KITTIRefinerBatches(opt.data_path, train_lines, opt.height, opt.width, list(opt.frame_ids), 4, is_train=True,
                                        batch_size=opt.batch_size if batch_size is None else batch_size, shuffle=True, drop_last=True,
                                        rank=rank, world_size=world_size, **common)
@@ -80,7 +80,8 @@ def main(argv=None):
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],
                                                         no_val=extra["no_val"] or rank != 0, batch_size=refiner.batch_size,
                                                         local_world_size=local_world, device=refiner.device,
-                                                        image_decoder=extra.get("image_decoder", "pil"))
+                                                        image_decoder=extra.get("image_decoder", "pil"),
+                                                        png_decoder=extra.get("png_decoder", "pil"))
     if val_loader is not None:
         from .validation import ValGroundTruth
         refiner.val_gt = ValGroundTruth(gt_depths, device=refiner.device)

@@ -1,7 +1,7 @@
 """The reference's ``python trainer.py`` as a command: options -> loaders -> ``Trainer.train`` with in-training validation.
 
     python -m fusiondepth_amd.train [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
-                                    [--log_images] [--image_decoder pil|device]
+                                    [--log_images] [--image_decoder pil|device] [--png_decoder pil|device]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.train ...          # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  trainer.py:142-174: the training lines of
@@ -20,7 +20,8 @@ Deviations from the reference, on purpose
     ``evaluate_depth``; ``--seed`` (default 0) seeds the networks, the epoch order and the per-item draws, so that a run can be
     repeated; ``--lidar_source raw`` sparsifies the Velodyne scans in the loader instead of reading ``{n}beam/`` files;
     ``--image_decoder device`` decodes the JPEG frames on the device (datasets.py, ``decoder=``; same batches bit for bit; with
-    ``--png`` it changes nothing).
+    ``--png`` it changes nothing); ``--png_decoder device`` does the same for the PNG frames of a ``--png`` tree (``png_decoder=``;
+    without ``--png`` it changes nothing).
   * ``--val_limit N`` validates on the first N test lines (the reference validates on all 697 at every log event), ``--no_val``
     not at all.
   * the reference overwrites ``--num_epochs`` with ``(8 * 17) // batch_size`` (trainer.py:28).  So does ``Trainer`` - unless the
@@ -42,14 +43,14 @@ import torch
 from . import dp
 from .evaluate_depth import split_off_flags
 
-EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None}
+EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None, "png_decoder": None}
 EXTRA_SWITCHES = ("no_val", "log_images")
 
 
 def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({splits_dir, seed, lidar_source, val_limit,
     no_val}, the remaining arguments); ``log_images: True`` joins the dict where ``--log_images`` is given, and only there, and so
-    does ``image_decoder`` ('pil' or 'device')."""
+    do ``image_decoder`` and ``png_decoder`` ('pil' or 'device')."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     if not found["log_images"]:
         del found["log_images"]
@@ -65,11 +66,13 @@ def split_off_extra(argv):
 
 
 def take_image_decoder(found):
-    """``--image_decoder pil|device``: validated where given, dropped from ``found`` where not (the default is 'pil')."""
-    if found.get("image_decoder") is None:
-        found.pop("image_decoder", None)
-    elif found["image_decoder"] not in ("pil", "device"):
-        raise ValueError("--image_decoder must be 'pil' or 'device', got %r" % (found["image_decoder"],))
+    """``--image_decoder pil|device`` and ``--png_decoder pil|device``: validated where given, dropped from ``found`` where not (the
+    default of both is 'pil')."""
+    for name in ("image_decoder", "png_decoder"):
+        if found.get(name) is None:
+            found.pop(name, None)
+        elif found[name] not in ("pil", "device"):
+            raise ValueError("--%s must be 'pil' or 'device', got %r" % (name, found[name]))
 
 
 def _read_lines(path):
@@ -83,7 +86,7 @@ def decode_workers(num_workers, local_world_size):
 
 
 def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_source="files", val_limit=None, no_val=False,
-                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil"):
+                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil"):
     """trainer.py:142-174 -> ``(train_loader, val_loader, gt_depths)``; the last two are None with ``no_val``.  ``batch_size``: the
     per-process micro-batch (``Trainer.batch_size``; default ``opt.batch_size``).  ``local_world_size``: ranks on this host (default
     ``world_size``).  The validation loader is never sharded: rank 0 walks all of it."""
@@ -104,7 +107,8 @@ def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_
         frame_ids.append("s")
     builder = KITTIStereoBatches if opt.use_stereo else KITTIRAWBatches
     workers = decode_workers(opt.num_workers, world_size if local_world_size is None else local_world_size)
-    common = dict(img_ext=img_ext, opt=opt, seed=seed, device=device, workers=workers, lidar_source=lidar_source, decoder=image_decoder)
+    common = dict(img_ext=img_ext, opt=opt, seed=seed, device=device, workers=workers, lidar_source=lidar_source, decoder=image_decoder,
+                  png_decoder=png_decoder)
     train_loader = builder(opt.data_path, train_lines, opt.height, opt.width, frame_ids, 4, is_train=True,
                            batch_size=opt.batch_size if batch_size is None else batch_size, shuffle=True, drop_last=True, rank=rank,
                            world_size=world_size, **common)
@@ -162,7 +166,8 @@ def main(argv=None):
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],
                                                         no_val=extra["no_val"] or rank != 0, batch_size=trainer.batch_size,
                                                         local_world_size=local_world, device=trainer.device,
-                                                        image_decoder=extra.get("image_decoder", "pil"))
+                                                        image_decoder=extra.get("image_decoder", "pil"),
+                                                        png_decoder=extra.get("png_decoder", "pil"))
     if val_loader is not None:
         from .validation import ValGroundTruth
         trainer.val_gt = ValGroundTruth(gt_depths, device=trainer.device)

@@ -1144,6 +1144,110 @@ typedef struct fd_jpeg_desc {
 int fd_jpeg_reconstruct(void* staging, long staging_bytes, const fd_jpeg_desc* desc, int N, unsigned char* out, long out_bytes,
                         void* stream);
 
+/* ------------------------------------------------------------------------------ PNG frames --
+ * Pillow's `Image.open(f).convert("RGB")` of an 8-bit PNG and `np.asarray(Image.open(f))` of a 16-bit grey one, split like the JPEG
+ * decoder above: the serial half - the chunk walk and the inflate of the IDAT stream - on the host (csrc/png_inflate.h: plain C++, no
+ * zlib, no GPU call, no globals, no allocation, thread-safe, usable on a machine without a GPU), the scanline filters on the device
+ * (csrc/png.hip).  Every step is integer arithmetic on bytes, so the result is held to Pillow's bytes (tests/png_ref.py restates the
+ * chunk walk and the filters in numpy; zlib.decompress restates the inflate).
+ *
+ * Covered files: non-interlaced; colour type 2 at bit depth 8 (RGB, bpp 3), colour type 0 at bit depth 8 (grey, bpp 1) and colour type
+ * 0 at bit depth 16 (depth maps, bpp 2), none of them with a tRNS chunk.  NOT covered: palette, alpha (colour types 4 and 6), tRNS,
+ * Adam7, bit depths 1 / 2 / 4, 16-bit RGB, animated PNG (an acTL chunk), more than 2^31 - 1 scanline bytes.  For those `covered` is 0,
+ * the probe still returns 0 once it has read IHDR, and fd_png_inflate returns FD_PNG_UNCOVERED: a status, never a guess.
+ *
+ * fd_png_inflate treats the payloads of the consecutive IDAT chunks as ONE zlib stream - a payload may end at any byte, inside a code
+ * or inside a stored block's LEN, and may be empty - and writes exactly raw_bytes = height * (1 + row_bytes) FILTERED bytes to dst:
+ * per scanline its filter-type byte, then row_bytes = width * bpp bytes.  Stored, fixed and dynamic blocks; `dst` is its own window.
+ * Neither function reads outside [file, file + n) or writes outside dst[0 .. dst_cap), whatever the bytes are.  A status other than 0
+ * leaves its reason in fd_last_error() (thread-local).  What is checked, and the status of a miss:
+ *   FD_PNG_NOT_PNG     the 8-byte signature.
+ *   FD_PNG_CORRUPT     IHDR: first chunk, 13 bytes, its CRC-32, non-zero size, compression and filter method 0, a colour type and bit
+ *                      depth that go together.  zlib header: CM = 8, CINFO <= 7, FCHECK, no FDICT.  Deflate: block type 3; LEN against
+ *                      NLEN; more than 286 literal/length or 30 distance codes; a code-length repeat with nothing before it or past the
+ *                      last code; no end-of-block code; an over-subscribed code, or an incomplete one other than at most one code of
+ *                      length 1 (zlib's rule: the one-code distance tree is a code, an incomplete code-length code is not); a symbol
+ *                      no code stands for (an unused pattern, lengths 286 / 287, distances 30 / 31); a distance beyond the bytes written;
+ *                      MORE than raw_bytes of output.  After the stream: its Adler-32 against the bytes written; a filter-type byte
+ *                      above 4; an IEND chunk that is not the twelve bytes it has to be (its CRC with them).
+ *   FD_PNG_TRUNCATED   a file that ends inside a chunk header, an IDAT payload or its CRC field, inside the stream, or before a whole
+ *                      IEND; a stream that ends with FEWER than raw_bytes of output.  Only the whole file returns 0.
+ *   FD_PNG_CAPACITY    dst_cap < raw_bytes (nothing is written).
+ * CRCs: IHDR's and IEND's are verified.  The IDAT chunks' are NOT - Pillow does not verify them either; the stream's Adler-32, which
+ * is verified, covers the same bytes - and neither are those of the ancillary chunks, which are skipped unread.  Bytes behind the end
+ * of the zlib stream inside the IDAT run are ignored, as zlib ignores them. */
+#define FD_PNG_OK 0
+#define FD_PNG_BAD_ARGS 1
+#define FD_PNG_NOT_PNG 2
+#define FD_PNG_UNCOVERED 3
+#define FD_PNG_TRUNCATED 4
+#define FD_PNG_CORRUPT 5
+#define FD_PNG_CAPACITY 6
+typedef struct fd_png_info {
+    int width, height;
+    int bit_depth, colour_type, interlace;    /* as IHDR says */
+    int covered;
+    int bpp;                         /* bytes per pixel: 3, 1 or 2; 0 when not covered */
+    int reserved;
+    long row_bytes;                  /* width * bpp; 0 when not covered */
+    long raw_bytes;                  /* height * (1 + row_bytes); 0 when not covered */
+    long reserved2[2];
+} fd_png_info;
+int fd_png_probe(const unsigned char* file, long n, fd_png_info* info);
+int fd_png_inflate(const unsigned char* file, long n, unsigned char* dst, long dst_cap, fd_png_info* info);
+
+/* The device half: one chunk of 1 <= N <= 65535 frames of different sizes and formats in TWO launches whatever N and the sizes are, no
+ * atomics, no workspace.
+ *   staging   the device copy of the chunk's staging buffer, 16-byte aligned, staging_bytes long; every raw_off is in bytes from it.
+ *             Its first N * sizeof(fd_png_desc) bytes hold a copy of `desc`: the caller uploads table and scanlines as ONE buffer.
+ *   desc      HOST array of the N descriptors.  Every one is checked here before anything is launched; the first bad one refuses the
+ *             whole call with a non-zero status and its index and reason in fd_last_error().  The kernels read the copy inside staging and
+ *             apply the same check again, skipping what fails it, so a copy that differs from `desc` cannot take them outside the
+ *             two buffers.
+ *   out       16-byte aligned; frame n is written at out + out_off: mode 0 (rgb) uint8 [height][width][3], a grey sample written to
+ *             all three channels as convert("RGB") does; mode 1 (gray16) host-order uint16 [height][width], the big-endian sample
+ *             swapped on the store (out_off even).  16-byte stores at the address's 16-byte boundaries, single bytes before the first
+ *             and after the last boundary of a frame.
+ * kind 0 (scanlines): raw_off -> the height * (1 + width * bpp) filtered bytes as fd_png_inflate writes them; (bpp, mode) is (3, rgb),
+ *   (1, rgb) or (2, gray16).  kind 1 (raw): raw_off -> the frame's bytes exactly as they go to `out` (a host decoder wrote them; bpp
+ *   is ignored); launch B copies them.
+ * The check: kind 0 or 1, mode 0 or 1, a (bpp, mode) pair from the list; width and height in 1 .. 65535 with at most 2^31 - 1 output
+ *   and scanline bytes; raw_off at or behind the table, and the frame's source, rounded up to a multiple of 16 bytes for kind 0 (the
+ *   kernel loads aligned 16-byte pieces), inside staging_bytes; out_off >= 0 and the frame inside out_bytes.  Regions of different
+ *   descriptors must not overlap; this is not checked, and an overlap cannot take the kernels outside the two buffers.
+ * Launch A (k_png_unfilter) reconstructs the scanlines IN PLACE, one workgroup per frame.  With a = the byte bpp to the left, b = the
+ *   byte above, c = the byte above-left (each 0 outside the picture), mod 256: None adds nothing, Sub a, Up b, Average (a + b) >> 1 on
+ *   the 9-bit sum, Paeth the one of a, b, c nearest to p = a + b - c, ties in the order a, b, c.  FD_PNG_BAND_ROWS lanes walk as many
+ *   rows as a skewed wavefront: lane r is one pixel behind lane r - 1 and takes b (and, a step later, c) from it through LDS; a frame
+ *   taller than that goes band after band in the same workgroup, the lane before a band's first row re-reading the reconstructed row
+ *   above it as an unfiltered one.  Width + rows - 1 steps per band.  Each lane streams its row through registers in aligned 16-byte
+ *   loads issued three pieces ahead, and writes whole aligned words except at the row's two ends.  Every reconstructed row's filter
+ *   byte is set to 0 (None): STAGING IS OVERWRITTEN, and a second call on the same two buffers gives the same bytes.
+ * Launch B (k_png_store) writes `out` in 16-byte pieces from the reconstructed rows (or the raw bytes of kind 1).
+ *
+ * Measured on one MI355X, twice (profiles/png_decode_time.log; 36 frames of 1242x375 written by Pillow with default settings from
+ * textured synthetic content, 1122 KB per file, rows filtered Sub and Up only): a batch through data_ops.decode_png_batch 15.12 /
+ * 14.92 ms against 38.46 / 37.13 ms for Pillow on 16 threads + np.stack + upload; KITTIRAWBatches from the PNG tree 836.6 / 784.0
+ * against 319.4 / 281.4 items/s (the larger run-to-run spread 264.4 / 121.3), the trainer fed by it 414.2 / 416.2 against 254.0 /
+ * 250.0 images/s.  One host thread, per frame: fd_png_inflate 2.84 / 2.86 ms, zlib.decompress (1.2.11) of the same stream 3.57 /
+ * 3.58 ms, Pillow's whole decode 4.51 / 4.57 ms - the inflate beats zlib's by 1.25x.  Host phase 12.0 / 12.5 ms, upload 50.3 MB in
+ * 1.0 / 0.9 ms, the two launches 1.68 ms = 105x their traffic bound (100.6 MB at 6.3 TB/s) and 11 % of the batch: the compiler waits
+ * for each lane's row load where it is issued, so a wavefront step costs a memory latency (open).  NOT
+ * measured: a real KITTI tree (another encoder: other filter choices and compression), more than one rank sharing the host's 16
+ * threads, the completion loader end to end. */
+#define FD_PNG_BAND_ROWS 512
+typedef struct fd_png_desc {
+    long raw_off;                    /* kind 0: the filtered scanlines; kind 1: the finished bytes */
+    long out_off;                    /* into `out` */
+    int kind;                        /* 0 scanlines, 1 raw */
+    int width, height;
+    int bpp;                         /* kind 0: 3 (RGB), 1 (grey), 2 (16-bit grey) */
+    int mode;                        /* 0 rgb, 1 gray16 */
+    int reserved[3];
+} fd_png_desc;
+int fd_png_band_rows(void);
+int fd_png_unfilter(void* staging, long staging_bytes, const fd_png_desc* desc, int N, unsigned char* out, long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,13 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
                           The kernels' own times: ``rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_loader.py --step
                           jpeg_kernels``, then ``--step jpeg_trace_report --trace_dir DIR``.
 
+ 13. ``png``              ``--step png`` (a run of its own, ``| tee profiles/png_decode_time.log``): step 12's workload as PNG files written by
+                          Pillow with its default settings, through ``data_ops.decode_png_batch`` and through pil_loader on 16 threads +
+                          np.stack + upload, alternating; the host inflate phase, the upload and the two kernels against their traffic bound
+                          and as a share of the batch; ``fd_png_inflate`` against ``zlib.decompress`` and Pillow's whole decode on one
+                          thread; the completion loader's 16 depth planes by either route; ``KITTIRAWBatches`` items/s and Trainer
+                          images/s fed by either ``png_decoder=``.
+
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
 import argparse
@@ -549,6 +556,226 @@ def step_jpeg_trace_report(args):
     for r in rows:
         if "k_jpeg" in r[0]:
             say("      %-30s %6d calls, %8.1f us / batch" % (r[0].replace("(anonymous namespace)::", "").split("(")[0], r[1], r[3]))
+
+
+# ---------------------------------------------------------------------------------------------------- 13. PNG frames on the device
+def write_png_tree(root, n_frames):
+    """write_tree's layout with PNG frames written by Pillow with its default settings -> (split lines, frame paths, mean file bytes)."""
+    lines, _ = write_tree(root, n_frames, (".png",))
+    folder = os.path.join(root, "2011_09_26", "2011_09_26_drive_0001_sync", "image_02/data")
+    paths = [os.path.join(folder, "%010d.png" % i) for i in range(n_frames)]
+    return lines, paths, sum(os.path.getsize(p) for p in paths) / n_frames
+
+
+def step_png(args):
+    """[13] ``data_ops.decode_png_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
+    inflate alone against zlib and Pillow on one thread, the builder and the trainer fed by either route, and the completion loader's
+    depth planes.  The routes alternate inside this one run."""
+    import concurrent.futures
+    import ctypes
+    import zlib
+    import torch
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from fusiondepth_amd import _lib, completion_data as CD, data_ops
+    from fusiondepth_amd.datasets import KITTIRAWBatches, pil_loader
+    import png_ref
+    N = 36
+    with tempfile.TemporaryDirectory() as root:
+        lines, paths, mean_size = write_png_tree(root, N + 14)
+        batch_paths = paths[:N]
+        datas = [open(p, "rb").read() for p in batch_paths]
+        filters = np.bincount(np.concatenate([png_ref.scanlines(d)[1][:, 0] for d in datas[:4]]), minlength=5)
+        say("[13] PNG frames: %d frames of %dx%d, 8-bit RGB, written by Pillow with its default settings from textured synthetic content; "
+            "%.0f KB per file; filter types of the first four files' rows (None Sub Up Average Paeth): %s (not a KITTI frame: KITTI's own "
+            "PNGs come from another encoder)" % (N, W0, H0, mean_size / 1e3, " ".join(str(int(v)) for v in filters)))
+        pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
+
+        def route_device():
+            frames, stats = data_ops.decode_png_batch(batch_paths, pool=pool)
+            torch.cuda.synchronize()
+            assert stats["fallback"] == 0, stats
+            return frames
+
+        def route_pil():
+            stack = torch.from_numpy(np.stack(list(pool.map(pil_loader, batch_paths)))).to("cuda", non_blocking=True)
+            torch.cuda.synchronize()
+            return stack
+
+        got, want = route_device(), route_pil()
+        assert all(torch.equal(g, w) for g, w in zip(got, want)), "the routes disagree"
+        t = {"device": [], "pil": []}
+        for _ in range(args.iters):
+            for name, fn in (("device", route_device), ("pil", route_pil)):
+                t0 = time.perf_counter()
+                fn()
+                t[name].append(1e3 * (time.perf_counter() - t0))
+        for name, label in (("device", "decode_png_batch (host inflate on %d threads + one upload + fd_png_unfilter)" % WORKERS),
+                            ("pil", "pil_loader on %d threads + np.stack + upload (the parent's route)" % WORKERS)):
+            med = float(np.median(t[name]))
+            say("    %-88s %7.1f frames/s, ms per batch of %d: %s  (%d alternating runs)" % (label + ":", 1e3 * N / med, N, _spread(t[name]), args.iters))
+
+        # one thread, per frame: the inflate alone against zlib's and against Pillow's whole decode
+        info = data_ops.png_probe(datas[0])[1]
+        dst = np.empty(info.raw_bytes, np.uint8)
+        streams = [png_ref.idat(d) for d in datas]
+        one = {"inflate": [], "zlib": [], "pillow": []}
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for d in datas:
+                assert data_ops.png_inflate(d, dst)[0] == 0
+            one["inflate"].append(1e3 * (time.perf_counter() - t0) / N)
+            t0 = time.perf_counter()
+            for s in streams:
+                zlib.decompress(s)
+            one["zlib"].append(1e3 * (time.perf_counter() - t0) / N)
+            t0 = time.perf_counter()
+            for p in batch_paths:
+                pil_loader(p)
+            one["pillow"].append(1e3 * (time.perf_counter() - t0) / N)
+        i1, z1, p1 = min(one["inflate"]), min(one["zlib"]), min(one["pillow"])
+        say("    one thread, per frame: fd_png_inflate (chunk walk, inflate, Adler-32, filter bytes) %.2f ms, zlib.decompress of the joined "
+            "IDAT data (zlib %s) %.2f ms, Pillow's whole decode %.2f ms -> the inflate written here is %s than zlib's (%.2fx) and %.2fx "
+            "Pillow's whole decode" % (i1, zlib.ZLIB_RUNTIME_VERSION, z1, p1, "SLOWER" if i1 > z1 else "faster", z1 / i1, p1 / i1))
+
+        # inside the batch
+        host_ms, up_ms, k_ms = [], [], []
+        rgb_bytes = N * 3 * H0 * W0
+        for _ in range(args.iters):
+            t0 = time.perf_counter()
+            job = data_ops.PngBatchJob(batch_paths, pool)
+            lay = job.wait_host()
+            host_ms.append(1e3 * (time.perf_counter() - t0))
+            table, _, _, _, out_bytes = job.layout()
+            lay["staging"].numpy()[:N * ctypes.sizeof(_lib.PngDesc)] = np.frombuffer(table, dtype=np.uint8)
+            dev = torch.empty((lay["upload_bytes"],), dtype=torch.uint8, device="cuda")
+            out = torch.empty((out_bytes,), dtype=torch.uint8, device="cuda")
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            dev.copy_(lay["staging"], non_blocking=True)
+            ev[1].record()
+            ev[2].record()
+            _lib.call("fd_png_unfilter", dev.data_ptr(), lay["upload_bytes"], ctypes.addressof(table), N, out.data_ptr(), out_bytes, _lib.stream())
+            ev[3].record()
+            torch.cuda.synchronize()
+            up_ms.append(ev[0].elapsed_time(ev[1]))
+            k_ms.append(ev[2].elapsed_time(ev[3]))
+        up_bytes, raw_bytes = lay["upload_bytes"], N * info.raw_bytes
+        traffic = raw_bytes + rgb_bytes                          # the filtered bytes read once, the RGB bytes written once
+        bound_ms = 1e3 * traffic / HBM_BPS
+        km, batch_ms = float(np.median(k_ms)), float(np.median(t["device"]))
+        say("    inside the batch: host phase (read + probe + inflate, %d threads) %s ms" % (WORKERS, _spread(host_ms)))
+        say("                      upload %.1f MB (filtered scanlines = %.3fx the RGB bytes) %s ms = %.1f GB/s"
+            % (up_bytes / 1e6, raw_bytes / rgb_bytes, _spread(up_ms), up_bytes / 1e6 / float(np.median(up_ms))))
+        say("                      the two kernels (device events around fd_png_unfilter) %s ms = %.1f %% of the batch; traffic bound %.1f MB "
+            "(filtered bytes in, RGB out) at %.1f TB/s = %.4f ms -> %.1fx the bound"
+            % (_spread(k_ms), 100 * km / batch_ms, traffic / 1e6, HBM_BPS / 1e12, bound_ms, km / bound_ms))
+
+        # the completion loader's depth planes: --step completion's workload (batch 4 x 3 frames + 4 ground-truth maps, 5 % dense)
+        rng = np.random.default_rng(5)
+        from PIL import Image
+        depth_paths = []
+        for k in range(COMPLETION_BATCH * FRAMES + COMPLETION_BATCH):
+            codes = rng.integers(256, 80 * 256, (H0, W0)).astype(np.uint16)
+            codes[rng.random(codes.shape) >= 0.05] = 0
+            depth_paths.append(os.path.join(root, "depth_%02d.png" % k))
+            Image.fromarray(codes).save(depth_paths[-1])
+        plane = (H0 * W0 + 3) // 4 * 4
+
+        def depth_pil():
+            staging = torch.empty((2 * plane * len(depth_paths),), dtype=torch.uint8, pin_memory=True)
+            data = staging.numpy().view(np.uint16)
+            for f in [pool.submit(CD._depth_into, p, data[k * plane:k * plane + H0 * W0].reshape(H0, W0)) for k, p in enumerate(depth_paths)]:
+                f.result()
+            dev = staging.to("cuda", non_blocking=True)
+            torch.cuda.synchronize()
+            return dev.view(torch.int16).view(len(depth_paths), plane)[:, :H0 * W0]
+
+        def depth_device():
+            frames, stats = data_ops.decode_png_batch(depth_paths, pool=pool, mode="gray16")
+            high = torch.stack([f.view(torch.uint8).view(-1)[1::2].amax() for f in frames]).cpu()          # the loader's 16-bit assertion
+            assert stats["fallback"] == 0 and bool((high > 0).all())
+            return frames
+
+        a, b = depth_pil(), depth_device()
+        assert all(torch.equal(x.view(torch.int16).view(-1), y) for x, y in zip(b, a)), "the depth routes disagree"
+        td = {"device": [], "pil": []}
+        for _ in range(args.iters):
+            for name, fn in (("device", depth_device), ("pil", depth_pil)):
+                t0 = time.perf_counter()
+                fn()
+                td[name].append(1e3 * (time.perf_counter() - t0))
+        say("    completion depth planes (%d 16-bit PNGs of %dx%d, 5 %% dense, %.0f KB per file), ms per batch until the planes are on the device:"
+            % (len(depth_paths), W0, H0, sum(os.path.getsize(p) for p in depth_paths) / len(depth_paths) / 1e3))
+        say("        png_decoder='device' (inflate + upload + fd_png_unfilter + the 16-bit check's download): %s" % _spread(td["device"]))
+        say("        png_decoder='pil'    (Pillow + copy into the pinned buffer + upload):                   %s" % _spread(td["pil"]))
+
+        # the builder from the PNG tree, both routes, alternating
+        opt = _opt(BATCH)
+
+        def run(decoder, epochs=2):
+            b = KITTIRAWBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".png", opt=opt, batch_size=BATCH, shuffle=True,
+                                seed=1, workers=WORKERS, png_decoder=decoder)
+            for _ in b:
+                pass
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 0
+            for _ in range(epochs):
+                for batch in b:
+                    n += batch[("color", 0, 0)].shape[0]
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            b.close()
+            return n / dt
+
+        rates = {"pil": [], "device": []}
+        for _ in range(5):
+            for name in ("pil", "device"):
+                rates[name].append(run(name, epochs=4))
+        sp = {k: max(v) - min(v) for k, v in rates.items()}
+        mp, md = float(np.median(rates["pil"])), float(np.median(rates["device"]))
+        say("    KITTIRAWBatches from the PNG tree, batch %d, %d items per epoch, 5 alternating runs of 4 epochs each:" % (BATCH, len(lines)))
+        say("        png_decoder='pil':    %7.1f items/s (runs %s; spread %.1f)" % (mp, " ".join("%.1f" % v for v in rates["pil"]), sp["pil"]))
+        say("        png_decoder='device': %7.1f items/s (runs %s; spread %.1f)" % (md, " ".join("%.1f" % v for v in rates["device"]), sp["device"]))
+        say("        difference %+.1f items/s against the larger spread %.1f: the device route %s"
+            % (md - mp, max(sp.values()), "WINS" if md - mp > max(sp.values()) else ("LOSES" if mp - md > max(sp.values()) else "is within the spread")))
+        pool.shutdown()
+
+        if args.windows > 0:
+            from fusiondepth_amd.trainer import Trainer
+            torch.manual_seed(1)
+            tr = Trainer(opt, verbose=False)
+            per_step = tr.batch_size * tr.accumulate_step
+            feeds = {}
+            for name in ("pil", "device"):
+                b = KITTIRAWBatches(root, lines, HEIGHT, WIDTH, [0, -1, 1], SCALES, is_train=True, img_ext=".png", opt=opt, batch_size=tr.batch_size,
+                                    shuffle=True, seed=1, workers=WORKERS, png_decoder=name)
+
+                def endless(b=b):
+                    while True:
+                        for batch in b:
+                            yield batch
+                feeds[name] = (b, endless())
+            res = {"pil": [], "device": []}
+            for name in feeds:
+                for _ in range(3):
+                    tr.train_step([next(feeds[name][1]) for _ in range(tr.accumulate_step)])
+            for _ in range(args.windows):
+                for name in ("pil", "device"):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        tr.train_step([next(feeds[name][1]) for _ in range(tr.accumulate_step)])
+                    torch.cuda.synchronize()
+                    res[name].append((time.perf_counter() - t0) / args.steps)
+            for name in feeds:
+                feeds[name][0].close()
+                m = float(np.median(res[name]))
+                say("    Trainer (ResNet-18, %dx%d, %d images / step) fed by png_decoder='%s': %s %.1f images/s (%.2f ms / step; windows %s)"
+                    % (WIDTH, HEIGHT, per_step, name, " " * (6 - len(name)), per_step / m, 1e3 * m, " ".join("%.2f" % (1e3 * v) for v in res[name])))
+        say("    not measured: a real KITTI tree (another encoder: other filter choices and compression); more than one rank sharing the "
+            "host's %d threads; the completion loader end to end" % WORKERS)
 
 
 # ---------------------------------------------------------------------------------------------------- 5-8. raw Velodyne scans
@@ -1130,7 +1357,7 @@ def main():
     ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
                                                       "raw_builder", "raw_trainer", "offline", "offline_worker", "refiner", "inf_gdc_key", "gdc_trace_report",
                                                       "refiner_trainer", "completion", "completion_keys", "completion_trace_report", "jpeg", "jpeg_kernels",
-                                                      "jpeg_trace_report"])
+                                                      "jpeg_trace_report", "png"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default="")
     ap.add_argument("--split_file", default="")
@@ -1151,7 +1378,7 @@ def main():
      "raw_trainer": step_raw_trainer, "offline": step_offline, "offline_worker": step_offline_worker, "all": drive, "colour": step_colour,
      "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker, "builder": step_builder,
      "trainer": step_trainer, "jpeg": step_jpeg, "jpeg_kernels": step_jpeg_kernels,
-     "jpeg_trace_report": step_jpeg_trace_report}[args.step](args)
+     "jpeg_trace_report": step_jpeg_trace_report, "png": step_png}[args.step](args)
 
 
 if __name__ == "__main__":
