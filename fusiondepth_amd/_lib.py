@@ -133,6 +133,28 @@ class PngDesc(ctypes.Structure):
 assert ctypes.sizeof(PngInfo) == 64 and ctypes.sizeof(PngDesc) == 48
 
 
+class PngEncDesc(ctypes.Structure):
+    """Mirror of ``fd_png_enc_desc``."""
+    _fields_ = [("src", ctypes.c_void_p)] + [(n, _L) for n in ("ws_off", "out_off", "out_bytes", "stream_bits")] + \
+               [(n, _I) for n in ("width", "height", "bpp", "first_row", "first_block", "first_group")] + \
+               [("adler", ctypes.c_uint), ("reserved", _I * 3)]
+
+
+class PngEncSizes(ctypes.Structure):
+    """Mirror of ``fd_png_enc_sizes``."""
+    _fields_ = [(n, _L) for n in ("rows", "blocks", "groups", "raw_bytes", "stat_off", "stat_bytes", "rowbits_off", "table_off", "ws_off",
+                                  "work_bytes")]
+
+
+class PngEncBlock(ctypes.Structure):
+    """Mirror of ``fd_png_enc_block``."""
+    _fields_ = [("bit_off", ctypes.c_ulonglong), ("bits", ctypes.c_ulonglong), ("header_bits", ctypes.c_uint), ("dist_len", ctypes.c_uint),
+                ("header", ctypes.c_uint * 128), ("code", ctypes.c_ushort * 288), ("len", ctypes.c_ubyte * 288), ("reserved", ctypes.c_uint * 2)]
+
+
+assert ctypes.sizeof(PngEncDesc) == 80 and ctypes.sizeof(PngEncSizes) == 80 and ctypes.sizeof(PngEncBlock) == 1408
+
+
 class LogCfg(ctypes.Structure):
     """Mirror of ``fd_log_cfg``."""
     _fields_ = [("Hs", _I), ("Ws", _I), ("n_rows", _I), ("n_disp", _I), ("row_y", _I * 8), ("row_h", _I * 8), ("row_first", _I * 8),
@@ -284,6 +306,12 @@ SIGNATURES = {
     "fd_png_inflate": ("pl" "pl" "p", "i"),
     "fd_png_band_rows": ("", "i"),
     "fd_png_unfilter": ("pl" "pi" "pl" "p", "i"),
+    "fd_png_enc_block_rows": ("", "i"),
+    "fd_png_enc_layout": ("pip", "i"),
+    "fd_png_enc_filter": ("pl" "pi" "p", "i"),
+    "fd_png_enc_plan": ("pi" "pp" "p", "i"),
+    "fd_png_enc_emit": ("pl" "pi" "p" "pl" "p", "i"),
+    "fd_png_enc_finish": ("pl" "p", "i"),
 }
 
 _lock = threading.Lock()

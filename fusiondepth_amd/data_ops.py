@@ -878,3 +878,158 @@ def decode_png_batch(files, device="cuda", pool=None, mode="rgb"):
         for k, i in enumerate(idx):
             frames[i] = stack[k]
     return frames, stats
+
+
+# ------------------------------------------------------------------------------------------------ PNG outputs ------
+# The encoder of include/fdhip.h ("PNG outputs"): filter, token counts, bit placement and the file's bytes in csrc/png_enc.hip, the
+# Huffman plan and the CRC-32s on the host behind the C ABI (csrc/png_deflate.h).  tests/png_enc_ref.py restates the stream.
+PNG_ENC_BLOCK_ROWS = 64      # FD_PNG_ENC_BLOCK_ROWS
+PNG_ENCODERS = ("pil", "device")
+
+
+def check_png_encoder(name, who="png_encoder"):
+    if name not in PNG_ENCODERS:
+        raise ValueError("%s must be 'pil' or 'device', got %r" % (who, name))
+    return name
+
+
+def png_enc_layout(shapes):
+    """``fd_png_enc_layout`` of [(width, height, bpp)] -> (a ctypes array of ``_lib.PngEncDesc``, ``_lib.PngEncSizes``).  Host only;
+    a shape the encoder does not cover is a ValueError."""
+    table = (_lib.PngEncDesc * max(len(shapes), 1))()
+    for d, (w, h, bpp) in zip(table, shapes):
+        d.width, d.height, d.bpp = min(int(w), 1 << 30), min(int(h), 1 << 30), int(bpp)      # the library refuses what is too large
+    sizes = _lib.PngEncSizes()
+    if _lib.load().fd_png_enc_layout(table, len(shapes), ctypes.byref(sizes)) != 0:
+        raise ValueError(_lib.last_error())
+    return table, sizes
+
+
+def png_enc_plan(table, n, stats, blocks=None):
+    """``fd_png_enc_plan``: ``stats`` = the contiguous uint32 numpy array launch A leaves (histograms, then Adler pairs) -> (blocks, total
+    bytes); ``table`` gets every file's offset, size and Adler-32.  ``blocks``: the address of room for the batch's ``_lib.PngEncBlock``
+    table, else one is allocated.  Host only."""
+    keep = None
+    if blocks is None:
+        keep = (_lib.PngEncBlock * int(table[n - 1].first_block + (table[n - 1].height + PNG_ENC_BLOCK_ROWS - 1) // PNG_ENC_BLOCK_ROWS))()
+        blocks = ctypes.addressof(keep)
+    total = ctypes.c_long(0)
+    if _lib.load().fd_png_enc_plan(table, n, stats.ctypes.data, blocks, ctypes.byref(total)) != 0:
+        raise RuntimeError("fd_png_enc_plan failed: %s" % _lib.last_error())
+    return keep, total.value
+
+
+def png_enc_finish(files, desc):
+    """``fd_png_enc_finish``: the three CRC-32s of ``desc``'s file inside ``files`` (a contiguous uint8 numpy array), in place.  Host
+    only; the interpreter lock is released while it runs."""
+    if _lib.load().fd_png_enc_finish(files.ctypes.data, files.size, ctypes.byref(desc)) != 0:
+        raise RuntimeError("fd_png_enc_finish failed: %s" % _lib.last_error())
+
+
+def _png_enc_kind(x, i):
+    """-> (height, width, bpp) of one image of ``encode_png_batch``; ValueError for a dtype or rank the encoder does not cover."""
+    import numpy as np
+    shape, dt = tuple(x.shape), x.dtype
+    u8 = dt in (torch.uint8, np.dtype(np.uint8))
+    u16 = dt in (torch.uint16, np.dtype(np.uint16))
+    if u8 and len(shape) == 3 and shape[2] == 3:
+        bpp = 3
+    elif u8 and len(shape) == 2:
+        bpp = 1
+    elif u16 and len(shape) == 2:
+        bpp = 2
+    else:
+        raise ValueError("encode_png_batch: image %d is %s %s, none of uint8 [H,W,3], uint8 [H,W], uint16 [H,W]" % (i, dt, list(shape)))
+    h, w = shape[0], shape[1]                                    # their limits are fd_png_enc_layout's to check
+    return h, w, bpp
+
+
+class PngEncodeJob:
+    """``encode_png_batch`` in its two halves, so that a caller can put work between them: the constructor checks the images, uploads
+    the host ones in one copy and issues launch A and the download of its statistics; ``finish()`` waits for them, plans, issues
+    launches B and C and the download of the files, waits, and fills the CRC-32s on ``pool``."""
+
+    def __init__(self, images, pool=None, device=None):
+        import numpy as np
+        images = list(images)
+        if not images:
+            raise ValueError("encode_png_batch: no images")
+        kinds = []
+        for i, x in enumerate(images):
+            if not isinstance(x, (torch.Tensor, np.ndarray)):
+                raise ValueError("encode_png_batch: image %d is a %s, not a tensor or an array" % (i, type(x).__name__))
+            kinds.append(_png_enc_kind(x, i))
+        self.pool = pool if pool is not None else jpeg_pool()
+        self.n = n = len(images)
+        self.table, self.sizes = png_enc_layout([(w, h, bpp) for h, w, bpp in kinds])
+        dev = [x.device for x in images if isinstance(x, torch.Tensor) and x.is_cuda]
+        self.device = torch.device(device) if device is not None else (dev[0] if dev else torch.device("cuda", torch.cuda.current_device()))
+        if self.device.type != "cuda":
+            raise RuntimeError("encode_png_batch runs on the GPU only (got %s); there is no CPU path" % self.device)
+        host = [(i, x.numpy() if isinstance(x, torch.Tensor) else x) for i, x in enumerate(images)
+                if not (isinstance(x, torch.Tensor) and x.is_cuda)]
+        self._keep = []
+        with torch.cuda.device(self.device):
+            src = [None] * n
+            if host:                                             # the host images: one pinned buffer, one upload
+                at, slots = 0, []
+                for i, a in host:
+                    slots.append(at)
+                    at += _round16(a.nbytes)
+                pinned = torch.empty((at,), dtype=torch.uint8, pin_memory=True)
+                flat = pinned.numpy()
+                for (i, a), s in zip(host, slots):
+                    flat[s:s + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                up = torch.empty((at,), dtype=torch.uint8, device=self.device)
+                up.copy_(pinned, non_blocking=True)
+                self._keep += [pinned, up]
+                for (i, _), s in zip(host, slots):
+                    src[i] = up.data_ptr() + s
+            for i, x in enumerate(images):
+                if src[i] is None:
+                    if x.device != self.device:
+                        raise ValueError("encode_png_batch: image %d lives on %s, the batch on %s" % (i, x.device, self.device))
+                    x = x.contiguous()
+                    self._keep.append(x)
+                    src[i] = x.data_ptr()
+            for d, p in zip(self.table, src):
+                d.src = p
+            sz = self.sizes
+            self.work = torch.empty((sz.work_bytes,), dtype=torch.uint8, device=self.device)
+            call("fd_png_enc_filter", self.work.data_ptr(), sz.work_bytes, ctypes.addressof(self.table), n, stream())
+            self._stats = torch.empty((sz.stat_bytes,), dtype=torch.uint8, pin_memory=True)
+            self._stats.copy_(self.work[sz.stat_off:sz.stat_off + sz.stat_bytes], non_blocking=True)
+            self._event = torch.cuda.Event()
+            self._event.record()
+
+    def finish(self):
+        """-> (files, stats) of ``encode_png_batch``."""
+        import numpy as np
+        sz, n = self.sizes, self.n
+        with torch.cuda.device(self.device):
+            self._event.synchronize()
+            blocks = torch.empty((sz.blocks * ctypes.sizeof(_lib.PngEncBlock),), dtype=torch.uint8, pin_memory=True)
+            _, total = png_enc_plan(self.table, n, self._stats.numpy().view(np.uint32), blocks.data_ptr())
+            room = (total + 3) // 4 * 4 + 4
+            out = torch.empty((room,), dtype=torch.uint8, device=self.device)
+            call("fd_png_enc_emit", self.work.data_ptr(), sz.work_bytes, ctypes.addressof(self.table), n, blocks.data_ptr(),
+                 out.data_ptr(), room, stream())
+            pinned = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+            pinned.copy_(out[:total], non_blocking=True)         # exactly the sum of the file sizes
+            torch.cuda.current_stream().synchronize()
+        flat = pinned.numpy()
+        for f in [self.pool.submit(png_enc_finish, flat, self.table[i]) for i in range(n)]:
+            f.result()
+        view = memoryview(flat)
+        files = [view[d.out_off:d.out_off + d.out_bytes] for d in list(self.table)[:n]]
+        self._keep = self.work = None
+        return files, {"bytes": int(total), "raw_bytes": int(sz.raw_bytes)}
+
+
+def encode_png_batch(images, pool=None):
+    """PNG files of ``images`` - device tensors, or host tensors / numpy arrays (uploaded in one copy), each uint8 [H, W, 3], uint8
+    [H, W] or uint16 [H, W]; sizes and kinds may differ - that decode to the input value for value.  Returns ``(files, stats)``: one
+    ``memoryview`` per image into ONE pinned buffer, complete files ready to be written, and ``{"bytes": their total size,
+    "raw_bytes": the scanline bytes they hold}``.  Three launches, three small uploads and two downloads whatever the number of images;
+    anything else is a ValueError before the GPU is touched."""
+    return PngEncodeJob(images, pool).finish()

@@ -161,7 +161,8 @@ def pack_export_sizes(sizes):
     return desc, at
 
 
-def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, want_depth=False, chunk=64, want_packed=False):
+def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, want_depth=False, chunk=64, want_packed=False,
+                 want_device=False):
     """export_detection.py:322-325, 344-348, 388 for N images, ``chunk`` of them per ``fd_depth_export`` call: the disparity resized to
     ``sizes[i] = (H_i, W_i)`` by OpenCV's float32 INTER_LINEAR rule, ``1 / .``, ``* pred_depth_scale_factor``, ``* ratios[i]`` (when
     given), ``* 256`` and the cast to ``uint16`` - each step one float32 rounding, the cast as the module docstring defines it.
@@ -169,7 +170,9 @@ def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, wa
     Returns a list of N ``uint16`` [H_i,W_i] arrays, views into one pinned download per chunk; with ``want_depth`` also the float32
     maps before the ``* 256`` (what the scorer clamps and scores) as device tensors: ``(u16 list, depth list)``.  ``want_packed``
     (with ``want_depth``) adds a third element: per chunk, ``(packed float32 device tensor, EXPORT_DESC array)`` - what the depth list
-    is made of views of, in the form ``points_export(packed=...)`` takes without another launch or copy."""
+    is made of views of, in the form ``points_export(packed=...)`` takes without another launch or copy.  ``want_device``: the uint16
+    maps stay on the device - N ``torch.uint16`` [H_i,W_i] tensors, views into one buffer per chunk, and no download - for
+    ``data_ops.encode_png_batch``."""
     if want_packed and not want_depth:
         raise ValueError("depth_export: want_packed needs want_depth")
     if not torch.cuda.is_available():
@@ -201,9 +204,12 @@ def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, wa
         _lib.call("fd_depth_export", disp.data_ptr(), disp.shape[0], disp.shape[1], disp.shape[2], desc_d.data_ptr(), b - a, total,
                   int(desc["H"].max()), int(desc["W"].max()), float(pred_depth_scale_factor),
                   None if ratio_d is None else ratio_d.data_ptr(), None if depth is None else depth.data_ptr(), out.data_ptr(), _lib.stream())
-        host = torch.empty((total,), dtype=torch.int16, pin_memory=True)
-        host.copy_(out)                                          # synchronises: desc_d and ratio_d are free to go afterwards
-        flat = host.numpy().view(np.uint16)                      # keeps the pinned tensor alive
+        if want_device:                                          # desc_d and ratio_d go back to the allocator in stream order
+            flat = out.view(torch.uint16)
+        else:
+            host = torch.empty((total,), dtype=torch.int16, pin_memory=True)
+            host.copy_(out)                                      # synchronises: desc_d and ratio_d are free to go afterwards
+            flat = host.numpy().view(np.uint16)                  # keeps the pinned tensor alive
         for d in desc:
             o, n = int(d["offset"]), int(d["H"]) * int(d["W"])
             maps.append(flat[o:o + n].reshape(int(d["H"]), int(d["W"])))
@@ -327,13 +333,16 @@ def points_export(depth_maps, calibs, max_high=1.0, chunk=16, packed=None):
     return clouds
 
 
-def quantize_u16(depth):
+def quantize_u16(depth, want_device=False):
     """``(depth * 256.0).astype(np.uint16)`` of export_detection.py:388 for one dense device map (the one GDC returns), with the
     product in float64 as numpy computes it for the reference's float64 map and the out-of-range rule of the module docstring
-    (``fd_depth_quantize_u16``) -> ``uint16`` host array of the same shape."""
+    (``fd_depth_quantize_u16``) -> ``uint16`` host array of the same shape; with ``want_device`` a ``torch.uint16`` device tensor and
+    no download."""
     _lib._need_cuda(depth)
     x = depth.detach().to(torch.float64).contiguous()
     out = torch.empty(x.shape, device=x.device, dtype=torch.int16)
     if x.numel():
         _lib.call("fd_depth_quantize_u16", x.data_ptr(), out.data_ptr(), x.numel(), _lib.stream())
+    if want_device:
+        return out.view(torch.uint16)
     return out.cpu().numpy().view(np.uint16)

@@ -16,7 +16,10 @@ disparities, ground truth ``<splits_dir>/detection/gt_depths.npz`` (``detection.
     from ``<data_path>/<date>/calib_cam_to_cam.txt``; scoring goes through ``evaluate_depth.evaluate_predictions`` and its ``on_depth``
     callback quantises each corrected map (``detection.quantize_u16``).
   * the maps go to ``<data_path>/<folder of the line>/<det_name>/{:06d}.png``, written with PIL on a pool of at most 16 host threads
-    while the next chunk runs on the device.  As in the reference (:388), the map is saved BEFORE the [1e-3, 80] clamp of the scorer.
+    while the next chunk runs on the device.  ``--png_encoder device`` (this script's flag; ``evaluate(..., png_encoder="device")``;
+    default ``pil``): the uint16 payload stays on the device and ``data_ops.encode_png_batch`` encodes it there, chunk by chunk (one
+    map at a time with ``--eval_gdc``); the pool writes the files from the encoder's pinned buffer.  The files differ from Pillow's in
+    their bytes, not in a single decoded value; maps, scores and clouds are untouched.  As in the reference (:388), the map is saved BEFORE the [1e-3, 80] clamp of the scorer.
 
   * ``--pl_name NAME [--pl_max_high F]`` (this script's flags, taken off the command line like ``--splits_dir``): next to each PNG a
     pseudo-LiDAR cloud ``<data_path>/<folder of the line>/<pl_name>/{:06d}.bin`` (float32 x, y, z, 1 in the Velodyne frame, the input
@@ -73,8 +76,17 @@ def _save_png(path, depth_u16):
     return path
 
 
-def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0):
+def _save_bytes(path, data):
+    with open(path, "wb") as fh:
+        fh.write(data)                                           # a view into the encoder's pinned buffer
+    return path
+
+
+def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0, png_encoder="pil"):
     """See the module docstring."""
+    from . import data_ops
+    data_ops.check_png_encoder(png_encoder, "export_detection: --png_encoder")
+    on_device = png_encoder == "device"
     ED._refuse_uncovered(opt)
     if not opt.det_name:
         raise ValueError("export_detection: --det_name is required (the folder the depth PNGs are written to)")
@@ -166,7 +178,11 @@ def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0):
             calibs = [kitti_utils.Calibration(os.path.join(opt.data_path, d, "calib_cam_to_cam.txt")) for d in dates]
 
             def on_depth(i, depth):                              # after scaling and GDC, before the clamp (:388)
-                writes.append(pool.submit(_save_png, paths[i], detection.quantize_u16(depth)))
+                if on_device:
+                    (data,), _ = data_ops.encode_png_batch([detection.quantize_u16(depth, want_device=True)], pool)
+                    writes.append(pool.submit(_save_bytes, paths[i], data))
+                else:
+                    writes.append(pool.submit(_save_png, paths[i], detection.quantize_u16(depth)))
                 if pl_name:                                      # the corrected map, rounded to float32 once (as --visualize does)
                     cloud, = detection.points_export([depth.detach().to(torch.float32)], [pl_calibs[i]], pl_max_high)
                     writes.append(pool.submit(_save_bin, pl_paths[i], cloud))
@@ -184,13 +200,19 @@ def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0):
                 b = min(a + EXPORT_CHUNK, N)
                 chunk_ratios = None if opt.disable_median_scaling else ratios[a:b]
                 if not pl_name:
-                    maps = detection.depth_export(pred_disps[a:b], sizes[a:b], chunk_ratios, opt.pred_depth_scale_factor, chunk=EXPORT_CHUNK)
+                    maps = detection.depth_export(pred_disps[a:b], sizes[a:b], chunk_ratios, opt.pred_depth_scale_factor, chunk=EXPORT_CHUNK,
+                                                  want_device=on_device)
                 else:                                            # the cloud from the float32 map the PNG is quantised from
                     maps, _, (pack,) = detection.depth_export(pred_disps[a:b], sizes[a:b], chunk_ratios, opt.pred_depth_scale_factor,
-                                                              want_depth=True, chunk=EXPORT_CHUNK, want_packed=True)
+                                                              want_depth=True, chunk=EXPORT_CHUNK, want_packed=True,
+                                                              want_device=on_device)
                     clouds = detection.points_export(None, pl_calibs[a:b], pl_max_high, packed=pack)
                     writes += [pool.submit(_save_bin, pl_paths[a + k], c) for k, c in enumerate(clouds)]
-                writes += [pool.submit(_save_png, paths[a + k], m) for k, m in enumerate(maps)]
+                if on_device:                                    # the payload never leaves the device unencoded
+                    files, _ = data_ops.encode_png_batch(maps, pool)
+                    writes += [pool.submit(_save_bytes, paths[a + k], f) for k, f in enumerate(files)]
+                else:
+                    writes += [pool.submit(_save_png, paths[a + k], m) for k, m in enumerate(maps)]
         for w in writes:
             w.result()                                           # a failed write raises here
     print("-> Saved {} depth maps to <data_path>/<folder>/{}".format(N, opt.det_name))
@@ -208,16 +230,17 @@ def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0):
 
 
 # the flags of this script that are not among the reference's options (``evaluate_depth.split_off_flags``), with their defaults
-SCRIPT_FLAGS = {"splits_dir": "splits", "pl_name": None, "pl_max_high": "1.0"}
+SCRIPT_FLAGS = {"splits_dir": "splits", "pl_name": None, "pl_max_high": "1.0", "png_encoder": "pil"}
 
 
 def main(argv=None):
     from .options import MonodepthOptions
     found, rest = ED.split_off_flags(sys.argv[1:] if argv is None else argv, SCRIPT_FLAGS)
     opt = MonodepthOptions().parse(rest)
+    extra = {} if found["png_encoder"] == "pil" else {"png_encoder": found["png_encoder"]}
     if found["pl_name"] is None:                                 # the call of a command line without the new flags, as before
-        return evaluate(opt, found["splits_dir"])
-    return evaluate(opt, found["splits_dir"], pl_name=found["pl_name"], pl_max_high=float(found["pl_max_high"]))
+        return evaluate(opt, found["splits_dir"], **extra)
+    return evaluate(opt, found["splits_dir"], pl_name=found["pl_name"], pl_max_high=float(found["pl_max_high"]), **extra)
 
 
 if __name__ == "__main__":

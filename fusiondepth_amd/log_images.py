@@ -146,7 +146,7 @@ def _plane(t, shape, what, dtype=torch.float32):
 
 
 def render(inputs, outputs, frame_ids, scales, J, Ts=None, first=0, automask=True, predictive_mask=False, val=False, min_depth=0.1,
-           max_depth=100.0, v1_multiscale=False, want_stats=False):
+           max_depth=100.0, v1_multiscale=False, want_stats=False, encode=False):
     """trainer.py:656-681 for the items ``first .. first + J - 1`` of a batch: one ``fd_log_sheets`` call, one pinned download.
     ``inputs`` / ``outputs``: the reference's dicts on the device - ``("color", f, s)`` [B,3,h_s,w_s] for every frame id and scale,
     ``("K", 0)`` / ``("inv_K", 0)`` [B,4,4], ``("disp", s)`` [B,1,h_s,w_s], ``("sel", s)`` (the pair the loss leaves: the uint8 argmin
@@ -157,7 +157,11 @@ def render(inputs, outputs, frame_ids, scales, J, Ts=None, first=0, automask=Tru
     checked: a missing key, a mismatched size or ``J < 1`` is a ValueError.
     Returns ``(sheets, tiles)``: the uint8 array [J,Hs,Ws,3] (a view of the pinned download) and ``{tag: view into its sheet}``, [h,w,3]
     each; with ``want_stats`` also ``{disparity tag: (mi, ma)}`` as float32, the minimum and maximum the call used (NaN, NaN where
-    the tile holds a NaN)."""
+    the tile holds a NaN).  ``encode`` (not with ``want_stats``): the sheets are encoded on the device
+    (``data_ops.encode_png_batch``) and what comes down is their PNG files - ``(files, None)``, one ``memoryview`` per sheet into one
+    pinned buffer, each decoding to the sheet the call without ``encode`` returns."""
+    if encode and want_stats:
+        raise ValueError("render: encode and want_stats cannot be combined")
     if not torch.cuda.is_available():
         raise RuntimeError("fusiondepth_amd.log_images.render needs an MI355X: there is no CPU path (tests/log_images_ref.py restates it)")
     frame_ids, scales, J, first = list(frame_ids), list(scales), int(J), int(first)
@@ -252,6 +256,10 @@ def render(inputs, outputs, frame_ids, scales, J, Ts=None, first=0, automask=Tru
     with torch.cuda.device(dev):
         _lib.call("fd_log_sheets", ctypes.addressof(table), table_d.data_ptr(), J, NT, ctypes.addressof(cfg), sheets.data_ptr(),
                   ws.data_ptr(), _lib.stream())
+        if encode:                                               # the sheets leave the device as PNG files: no pixel download
+            from . import data_ops
+            files, _ = data_ops.encode_png_batch([sheets[j] for j in range(J)])
+            return files, None
         host = torch.empty(sheets.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(sheets)                                       # the one download; synchronises, the sources are free to go afterwards
     arr = host.numpy()                                           # keeps the pinned tensor alive
@@ -287,10 +295,18 @@ def write_png(path, sheet):
     os.replace(tmp, path)
 
 
+def write_file(path, data):
+    """An already encoded PNG (``render(encode=True)``), written under the same temporary name and moved into place."""
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as fh:
+        fh.write(data)
+    os.replace(tmp, path)
+
+
 class PngSink:
     """The default ``Trainer.image_sink``: ``sink(mode, step, sheets, tiles)`` writes ``<log_path>/<mode>/images/{step:07d}_{j}.png``,
-    one sheet per item.  The encoding runs on ONE background thread, started with the first event after a ``join`` and gone after the
-    next: ``join()`` waits until everything handed in is on disk and re-raises what the thread ran into; ``close`` is ``join``."""
+    one sheet per item; a sheet that arrives as encoded bytes (``Trainer.png_encoder = "device"``) is written as it is.
+    The encoding and writing run on ONE background thread, started with the first event after a ``join`` and gone after the next: ``join()`` waits until everything handed in is on disk and re-raises what the thread ran into; ``close`` is ``join``."""
 
     def __init__(self, log_path):
         self.log_path = log_path
@@ -317,7 +333,8 @@ class PngSink:
                 mode, step, sheets = job
                 os.makedirs(os.path.join(self.log_path, mode, "images"), exist_ok=True)
                 for j in range(len(sheets)):
-                    write_png(self.path(self.log_path, mode, step, j), sheets[j])
+                    write = write_file if isinstance(sheets[j], (bytes, bytearray, memoryview)) else write_png
+                    write(self.path(self.log_path, mode, step, j), sheets[j])
             except Exception as e:                                # handed to the caller of join
                 self._error = self._error or e
 

@@ -2,6 +2,7 @@
 
     python -m fusiondepth_amd.train [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
                                     [--log_images] [--image_decoder pil|device] [--png_decoder pil|device]
+                                    [--png_encoder pil|device]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.train ...          # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  trainer.py:142-174: the training lines of
@@ -31,7 +32,10 @@ Deviations from the reference, on purpose
   * no tensorboard / wandb: the scalars go to ``<log_path>/{train,val}/scalars.jsonl`` (``Trainer.log``).  ``--log_images`` adds the
     reference's image summaries (trainer.py:656-681) at every log event: one contact sheet per item, rendered on the device
     (log_images.py), as ``<log_path>/{train,val}/images/{step:07d}_{j}.png``; ``Trainer.image_sink`` takes a tensorboard or wandb
-    writer instead.  Rank 0 alone logs, so the switch is set on rank 0 alone.
+    writer instead.  Rank 0 alone logs, so the switch is set on rank 0 alone.  ``--png_encoder device`` (default ``pil``) encodes
+    the sheets on the device (``data_ops.encode_png_batch``) instead of with PIL on the sink's thread: the default sink then receives
+    and writes encoded files, which decode to the same pixels; a sink of your own keeps receiving arrays and tiles; the training
+    state is not touched either way.
 """
 import json
 import os
@@ -43,14 +47,15 @@ import torch
 from . import dp
 from .evaluate_depth import split_off_flags
 
-EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None, "png_decoder": None}
+EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None, "png_decoder": None,
+                "png_encoder": None}
 EXTRA_SWITCHES = ("no_val", "log_images")
 
 
 def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({splits_dir, seed, lidar_source, val_limit,
     no_val}, the remaining arguments); ``log_images: True`` joins the dict where ``--log_images`` is given, and only there, and so
-    do ``image_decoder`` and ``png_decoder`` ('pil' or 'device')."""
+    do ``image_decoder``, ``png_decoder`` and ``png_encoder`` ('pil' or 'device')."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     if not found["log_images"]:
         del found["log_images"]
@@ -66,9 +71,9 @@ def split_off_extra(argv):
 
 
 def take_image_decoder(found):
-    """``--image_decoder pil|device`` and ``--png_decoder pil|device``: validated where given, dropped from ``found`` where not (the
-    default of both is 'pil')."""
-    for name in ("image_decoder", "png_decoder"):
+    """``--image_decoder pil|device``, ``--png_decoder pil|device`` and ``--png_encoder pil|device``: validated where given, dropped
+    from ``found`` where not (the default of each is 'pil')."""
+    for name in ("image_decoder", "png_decoder", "png_encoder"):
         if found.get(name) is None:
             found.pop(name, None)
         elif found[name] not in ("pil", "device"):
@@ -161,6 +166,8 @@ def main(argv=None):
         trainer.opt.num_epochs = epochs_given
     if extra.get("log_images") and rank == 0:                    # the other ranks do not log
         trainer.log_images = True
+    if extra.get("png_encoder") == "device":                     # the sheets of --log_images, encoded on the device
+        trainer.png_encoder = "device"
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader, gt_depths = build_loaders(opt, extra["splits_dir"], rank, world, seed=extra["seed"],
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],

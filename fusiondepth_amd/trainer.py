@@ -195,6 +195,7 @@ class Trainer:
     # ---- the image summaries of trainer.py:656-681 (log_pictures); off unless a caller sets the switch ----
     log_images = False         # every log event of run_epoch also renders the pictures of the batch that was due (log_images.py)
     image_sink = None          # callable (mode, step, sheets, tiles); None: log_images.PngSink(log_path), made at the first event
+    png_encoder = "pil"        # "device": the default sink's sheets are encoded on the device (data_ops.encode_png_batch)
     _last_val_io = None        # (inputs, outputs) of the last validation batch, kept only while log_images is on
 
     # ---- the steps of __init__ that the sibling drivers of the reference (completor.py, refiner.py) take differently ----
@@ -512,11 +513,14 @@ class Trainer:
                                                            outputs[("translation", 0, f)][:, 0].detach() * mean_inv_depth[:, None, :], f < 0)
                 else:
                     Ts[f] = outputs[("cam_T_cam", 0, f)]
+            if self.image_sink is None:
+                self.image_sink = log_images.PngSink(self.log_path)
+            # png_encoder "device": the default sink gets encoded files; a sink of the caller's keeps getting arrays and tiles
+            encode = self.png_encoder == "device" and isinstance(self.image_sink, log_images.PngSink)
             sheets, tiles = log_images.render(inputs, outputs, frame_ids, opt.scales, J, Ts=Ts, first=B - n,
                                               automask=not opt.disable_automasking, predictive_mask=bool(opt.predictive_mask), val=val,
-                                              min_depth=opt.min_depth, max_depth=opt.max_depth, v1_multiscale=bool(opt.v1_multiscale))
-        if self.image_sink is None:
-            self.image_sink = log_images.PngSink(self.log_path)
+                                              min_depth=opt.min_depth, max_depth=opt.max_depth, v1_multiscale=bool(opt.v1_multiscale),
+                                              **({"encode": True} if encode else {}))
         self.image_sink(mode, self.step, sheets, tiles)
 
     # ------------------------------------------------------------------------------------------------

@@ -54,7 +54,9 @@ extern "C" {
  *    Likewise the renderer of evaluate_depth --visualize (fd_vis_render_ws_bytes, fd_vis_render; it reuses struct fd_eigen_desc).
  *    Likewise the trainer's image summaries (fd_log_sheets_ws_bytes, fd_log_sheets, struct fd_log_tile, struct fd_log_cfg).
  *    Likewise the pseudo-LiDAR point clouds (fd_points_export_ws_bytes, fd_points_export, struct fd_points_calib; it reuses
- *    struct fd_export_desc). */
+ *    struct fd_export_desc).
+ *    Likewise the PNG encoder (fd_png_enc_layout, fd_png_enc_filter, fd_png_enc_plan, fd_png_enc_emit, fd_png_enc_finish,
+ *    fd_png_enc_block_rows, struct fd_png_enc_desc / _sizes / _block). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -1247,6 +1249,116 @@ typedef struct fd_png_desc {
 } fd_png_desc;
 int fd_png_band_rows(void);
 int fd_png_unfilter(void* staging, long staging_bytes, const fd_png_desc* desc, int N, unsigned char* out, long out_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------ PNG outputs --
+ * The encoder: PNG files that decode to the input value for value in Pillow, zlib and fd_png_inflate + fd_png_unfilter above.  It is
+ * split the other way round than the decoder: filtering has no serial dependency, and a deflate stream of literals and distance-1
+ * runs only (zlib's Z_RLE strategy) needs no match search, so pixels in, file bytes out is all device work; the host builds the
+ * Huffman codes from per-block histograms in between (csrc/png_deflate.h: plain C++, no zlib, no GPU call, usable without a GPU) and
+ * fills the three CRC-32 fields at the end.  tests/png_enc_ref.py restates the whole stream in numpy; the files are held to its bytes.
+ *
+ * Covered inputs: uint8 [H][W][3] (colour type 2, bpp 3), uint8 [H][W] (colour type 0 at depth 8, bpp 1), host-order uint16 [H][W]
+ * (colour type 0 at depth 16, samples big-endian in the file, bpp 2); 1 <= W, H <= 65535, at most 2^31 - 1 scanline bytes a frame;
+ * frames of different sizes and kinds in one batch of 1 <= N <= 65535.  No interlacing, palette, alpha or ancillary chunks.
+ *
+ * THE STREAM.  R = W * bpp, P = 1 + R.
+ *   Filter.   Each row chooses among None, Sub, Up, Average, Paeth (types 0 .. 4) with the decoder's arithmetic: a = the byte bpp to
+ *             the left, b = the byte above, c = above-left, each 0 outside the frame; Average (a + b) >> 1 on the 9-bit sum; Paeth the
+ *             one of a, b, c nearest to a + b - c, ties in the order a, b, c.  Cost = the sum over the row's R bytes of |int8(byte)|;
+ *             the smallest cost wins, a tie goes to the lowest type.
+ *   Tokens.   Each scanline (its filter byte first) is cut into maximal runs of equal bytes; runs never cross a scanline.  A run of
+ *             length L is, in order: one literal; (L - 1) / 258 matches of length 258; the remainder m = (L - 1) % 258 as one match if
+ *             m >= 3, else as m literals.  Every match has distance 1.
+ *   Blocks.   FD_PNG_ENC_BLOCK_ROWS scanlines are one deflate block, BTYPE 2, BFINAL on the frame's last.  Literal/length lengths are
+ *             Huffman lengths of the block's counts plus one end-of-block, at most 15 bits; the code-length code at most 7 bits.  Tree
+ *             rule: merge the two nodes of smallest (weight, id) until one is left - a leaf's id is its symbol, the k-th merged node's
+ *             is 286 (or 19) + k.  Limit rule: while the deepest leaf is deeper than the limit, every weight w becomes (w + 1) >> 1
+ *             and the tree is built again.  Canonical codes.  The distance tree: one code of length 1 (HDIST field 0) when the block
+ *             has a match, one zero length when it has none.  HLIT is trimmed to the last used symbol, at least 257; HCLEN to the
+ *             last used entry of the permuted order, at least 4; a code-length code with one used symbol gets a second code of length
+ *             1 (symbol 0, or 1 if 0 is the used one).  The HLIT + 1 lengths are run-length coded greedily: at a position with value
+ *             v and r equal values from there on - v == 0: r >= 11 -> symbol 18 for min(r, 138); else r >= 3 -> symbol 17 for r; else
+ *             a 0; v != 0: v once, then symbol 16 for min(r, 6) while r >= 3 remain, then the rest one by one.
+ *   Wrapping. Signature; IHDR; ONE IDAT holding 78 01, the blocks, zero bits up to the byte, the Adler-32 of the H * P filtered
+ *             bytes; IEND.  A file takes 57 + 2 + ceil(stream bits / 8) + 4 bytes, known after the plan and before any is written.
+ *
+ * THE CALLS, in order, for one batch:
+ *   fd_png_enc_layout  host.  In: src, width, height, bpp of every descriptor.  Out: their ws_off / first_row / first_block /
+ *                      first_group, and *sizes.  The caller allocates `work` (sizes.work_bytes, 16-byte aligned).
+ *   fd_png_enc_filter  copies the table to work[0 ..), clears the statistics, LAUNCH A (k_png_enc_filter): a workgroup of four waves
+ *                      takes FD_PNG_ENC_GROUP_ROWS = 4 scanlines of one frame, a wave per scanline, a lane per byte, 64 bytes a step.
+ *                      A first walk over the row sums the five costs; a second writes the chosen filter's bytes to the workspace
+ *                      (16-bit samples byte-swapped on the load), counts the row's tokens into LDS (a run is closed by the lane at
+ *                      the next run's first byte, found from the wave's ballot of "differs from the byte before"), and sums the
+ *                      Adler pair (sum d_j, sum (P - j) d_j) mod 65521.  At the end one global integer add per non-zero LDS count.
+ *   (download)         work[stat_off .. stat_off + stat_bytes): uint32 [blocks][FD_PNG_ENC_HIST] - 286 literal/length counts without
+ *                      end-of-block, [286] the matches, [287] unused - then uint32 [rows][2] Adler pairs.
+ *   fd_png_enc_plan    host.  Fills blocks[0 .. sizes.blocks) - lengths, reversed codes, header bits, exact size in bits = header +
+ *                      sum count[s] * (len[s] + extra[s]) + matches, first bit inside the frame's stream - and per descriptor adler,
+ *                      stream_bits, out_off, out_bytes (the files one behind the other from byte 0); *total_bytes = their sum.
+ *   fd_png_enc_emit    `blocks` is HOST memory (pinned for an asynchronous copy); it and the table are checked (every block inside
+ *                      its file) and copied to work; `out` (out_bytes >= total_bytes rounded up to a multiple of 4, plus 4; 4-byte
+ *                      aligned) is cleared.  LAUNCH B (k_png_enc_rowbits): a wave per scanline sums its tokens' bits.  LAUNCH C
+ *                      (k_png_enc_emit): a wave per scanline; its first bit = the block's + the header's + the bits of the block's
+ *                      earlier rows (at most 63 values, one wave reduction); per 64-byte step an exclusive wave scan of the closed
+ *                      runs' bits places each run, whose lane ORs its tokens in.  The wave of a block's first row also ORs the
+ *                      header in, that of its last row the end-of-block, that of the frame's first row the signature, IHDR, chunk
+ *                      lengths and types, 78 01 and the Adler-32.  Every write is an integer atomic OR on a 32-bit word of the
+ *                      cleared buffer, bounds-checked against the frame's file, so writers may share words and two calls give the
+ *                      same bytes.  No float atomics anywhere.
+ *   (download)         out[0 .. total_bytes) into pinned memory.
+ *   fd_png_enc_finish  host, per file: the CRC-32s of IHDR, IDAT and IEND, in place (eight bytes a step).
+ * THREE launches per batch (A, B, C) whatever N, the sizes and the block counts are, plus two clears and three small uploads: the
+ * descriptor table before A, and again with the plan's fields before B, both from the caller's pageable table (staged copies); the
+ * block table before B.
+ *
+ * Measured on one MI355X, twice, routes alternating (profiles/png_encode_time.log; textured synthetic content): 64 maps of 375x1242
+ * uint16 through data_ops.encode_png_batch 14.24 / 14.17 ms against 277.7 / 276.3 ms for Pillow on 16 threads after the download; one
+ * 768x4480 RGB sheet 3.37 / 3.26 against 327.1 / 326.6 ms; files +6 % (maps) and -0.1 % (sheets) against Pillow's.  The three launches:
+ * 1.253 ms for the 64 maps = 25x their traffic bound (DESIGN.md section 25 says why, and what is left open).  export_detection on a
+ * synthetic tree of 32 maps: 262.2 / 261.4 ms with pil, 126.1 / 126.2 ms with device - recommended there; the Trainer with log_images
+ * at the default log frequency: 115.83 / 115.72 against 115.82 / 115.96 steps/s - a tie inside the spread, not recommended there.
+ * NOT measured: a real KITTI tree (real depth maps
+ * and frames compress differently from synthetic content), real detector-side readers of the files, file-system write time. */
+#define FD_PNG_ENC_BLOCK_ROWS 64
+#define FD_PNG_ENC_GROUP_ROWS 4
+#define FD_PNG_ENC_HIST 288
+#define FD_PNG_ENC_HEADER_WORDS 128
+typedef struct fd_png_enc_desc {
+    const void* src;                 /* DEVICE pixels, contiguous; 2-byte aligned for bpp 2 */
+    long ws_off;                     /* layout: the frame's filtered scanlines inside work */
+    long out_off, out_bytes;         /* plan: the file inside out */
+    long stream_bits;                /* plan: the deflate blocks' bits */
+    int width, height;
+    int bpp;                         /* 3 (RGB), 1 (grey), 2 (16-bit grey) */
+    int first_row, first_block, first_group;   /* layout: the batch-wide index of the frame's first scanline / block / row group */
+    unsigned adler;                  /* plan */
+    int reserved[3];
+} fd_png_enc_desc;
+typedef struct fd_png_enc_sizes {
+    long rows, blocks, groups;       /* of the whole batch */
+    long raw_bytes;                  /* sum of H * P */
+    long stat_off, stat_bytes;       /* the download */
+    long rowbits_off, table_off, ws_off;
+    long work_bytes;
+} fd_png_enc_sizes;
+typedef struct fd_png_enc_block {
+    unsigned long long bit_off;      /* the block's first bit inside its frame's deflate stream */
+    unsigned long long bits;         /* header + tokens + end-of-block */
+    unsigned header_bits;
+    unsigned dist_len;               /* 1: the block has matches, each followed by the one-bit distance code 0 */
+    unsigned header[FD_PNG_ENC_HEADER_WORDS];   /* the header's bits, LSB first */
+    unsigned short code[288];        /* canonical, bit-reversed */
+    unsigned char len[288];
+    unsigned reserved[2];
+} fd_png_enc_block;
+int fd_png_enc_block_rows(void);
+int fd_png_enc_layout(fd_png_enc_desc* desc, int N, fd_png_enc_sizes* sizes);
+int fd_png_enc_filter(void* work, long work_bytes, const fd_png_enc_desc* desc, int N, void* stream);
+int fd_png_enc_plan(fd_png_enc_desc* desc, int N, const unsigned* stats, fd_png_enc_block* blocks, long* total_bytes);
+int fd_png_enc_emit(void* work, long work_bytes, const fd_png_enc_desc* desc, int N, const fd_png_enc_block* blocks,
+                    unsigned char* out, long out_bytes, void* stream);
+int fd_png_enc_finish(unsigned char* files, long nbytes, const fd_png_enc_desc* desc);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ disparities, synthetic 375x1242 ground truth with 5 % valid pixels (8 distinct m
     python scripts/bench_eval.py --step visualize [--reps 10] [--out profiles/visualize_time.log]
     python scripts/bench_eval.py --step log_images [--reps 10] [--out profiles/log_images_time.log]
     python scripts/bench_eval.py --step pseudo_lidar [--reps 10] [--out profiles/pseudo_lidar_time.log]
+    python scripts/bench_eval.py --step png_encode [--reps 5] [--out profiles/png_encode_time.log]
 
 Per N: the library call alone between device events with everything resident (median, min, max), the upload of the packed ground
 truth, the whole ``eigen_scores`` (packing on the host, uploads, calls in chunks of 64, the read-back) and the loop, both as wall time
@@ -713,10 +714,217 @@ def completion_val_step(a):
     return lines
 
 
+def png_encode_step(a):
+    """Batch PNG encoding: data_ops.encode_png_batch against Pillow on 16 threads, the routes alternating, after a decode-and-compare
+    of both outputs.  Maps: fd_depth_export's uint16 payload of textured synthetic disparities; sheets: 768x4480 RGB contact sheets
+    with a black background (textured tiles and a flat grey one)."""
+    import concurrent.futures
+    import ctypes
+    import io
+    from PIL import Image
+    from fusiondepth_amd import data_ops as DO
+    from fusiondepth_amd import detection as D
+    H, W, h, w = 375, 1242, 192, 640
+    rng = np.random.RandomState(5)
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=16)
+    lines = ["PNG encoding, data_ops.encode_png_batch (3 launches) against Image.save on 16 threads after the download; median of %d "
+             "(min, max) after one warm-up round, the routes alternating" % a.reps]
+
+    def pil_one(arr):
+        buf = io.BytesIO()
+        Image.fromarray(arr).save(buf, format="PNG")
+        return buf.getvalue()
+
+    def case(name, images):
+        n = len(images)
+        total_px = sum(int(x.numel()) * x.element_size() for x in images)
+
+        def device_all():
+            return DO.encode_png_batch(images, pool)
+
+        def pil_all():
+            host = [x.cpu().numpy() for x in images]
+            return list(pool.map(pil_one, host))
+
+        files, stats = device_all()
+        theirs = pil_all()
+        for x, f, g in zip(images, files, theirs):               # both routes decode to the input
+            want = x.cpu().numpy()
+            assert np.array_equal(np.asarray(Image.open(io.BytesIO(bytes(f)))), want), "the device's file does not decode to its input"
+            assert np.array_equal(np.asarray(Image.open(io.BytesIO(g))), want)
+        back, st = DO.decode_png_batch([bytes(f) for f in files], mode="gray16" if images[0].dim() == 2 else "rgb")
+        assert st["fallback"] == 0 and all(torch.equal(b, x) for b, x in zip(back, images)), "decode_png_batch of the files differs"
+        # the launches alone: the two library calls on resident buffers, with the plan of the first run
+        job = DO.PngEncodeJob(images, pool)
+        job._event.synchronize()
+        blocks = torch.empty((job.sizes.blocks * ctypes.sizeof(DO._lib.PngEncBlock),), dtype=torch.uint8, pin_memory=True)
+        _, total = DO.png_enc_plan(job.table, n, job._stats.numpy().view(np.uint32), blocks.data_ptr())
+        room = (total + 3) // 4 * 4 + 4
+        out = torch.empty((room,), dtype=torch.uint8, device="cuda")
+
+        def launches():
+            call("fd_png_enc_filter", job.work.data_ptr(), job.sizes.work_bytes, ctypes.addressof(job.table), n, stream())
+            call("fd_png_enc_emit", job.work.data_ptr(), job.sizes.work_bytes, ctypes.addressof(job.table), n, blocks.data_ptr(), out.data_ptr(),
+                 room, stream())
+
+        t_k, = alternate([launches], a.reps, _event_ms)
+        for run in (1, 2):
+            t_d, t_p = alternate([device_all, pil_all], a.reps, _wall_ms)
+            lines.append("  %s, run %d: encode_png_batch end to end %.2f ms (%.2f, %.2f) = %.2f ms / image; Pillow on 16 threads (download, "
+                         "Image.save) %.2f ms (%.2f, %.2f) = %.2f ms / image -> %.2fx"
+                         % (name, run, t_d[0], t_d[1], t_d[2], t_d[0] / n, t_p[0], t_p[1], t_p[2], t_p[0] / n, t_p[0] / t_d[0]))
+        raw = stats["raw_bytes"]
+        bound = total_px + 3 * raw + 2 * stats["bytes"]             # pixels read; workspace written, read twice; output cleared, written
+        lines.append("      the three launches with their clears and uploads, resident: %.3f ms (%.3f, %.3f); traffic bound %.1f MB = %.1f us at "
+                     "6.3 TB/s -> %.0fx the bound.  File bytes: device %d, Pillow %d (%+.1f %%), raw scanlines %d"
+                     % (t_k[0], t_k[1], t_k[2], bound / 1e6, 1e6 * bound / HBM, t_k[0] / (1e3 * bound / HBM), stats["bytes"],
+                        sum(len(g) for g in theirs), 100.0 * (stats["bytes"] / sum(len(g) for g in theirs) - 1.0), raw))
+
+    for n in (1, 16, 64):
+        base = rng.uniform(0.02, 0.6, (n, h // 8, w // 8)).astype(np.float32)
+        disp = torch.nn.functional.interpolate(torch.from_numpy(base)[:, None], size=(h, w), mode="bicubic", align_corners=False)[:, 0]
+        disp = (disp + torch.from_numpy(rng.uniform(-0.004, 0.004, (n, h, w)).astype(np.float32))).clamp_(0.01, 1.0).cuda()
+        maps = D.depth_export(disp, [(H, W)] * n, want_device=True)
+        case("%2d maps of %dx%d uint16" % (n, H, W), maps)
+    for n in (1, 4):
+        sheet = np.zeros((n, 768, 4480, 3), np.uint8)
+        for j in range(n):
+            for ty in range(4):
+                for tx in range(6):
+                    tile = rng.randint(0, 256, (24, 80, 3)).astype(np.float32)
+                    big = torch.nn.functional.interpolate(torch.from_numpy(tile).permute(2, 0, 1)[None], size=(192, 640), mode="bilinear")[0]
+                    noise = torch.from_numpy(rng.randint(-6, 7, (3, 192, 640)).astype(np.float32))
+                    sheet[j, 192 * ty:192 * ty + 192, 640 * tx:640 * tx + 640] = (big + noise).clamp(0, 255).permute(1, 2, 0).numpy().astype(np.uint8)
+            sheet[j, 576:768, 1280:1920] = 220
+        sheets = torch.from_numpy(sheet).cuda()
+        case("%d sheets of 768x4480 RGB" % n, [sheets[j] for j in range(n)])
+    pool.shutdown()
+    return lines + png_encode_commands(a)
+
+
+def _verdict(name, unit, runs, higher_is_better):
+    """The recommendation rule: ``--png_encoder device`` is recommended for a command only if its gain exceeds the larger run-to-run
+    spread (max - min of either route) in BOTH runs; otherwise the line says that it lost or tied, and by how much."""
+    gains, spreads = [], []
+    for pil, dev in runs:
+        gains.append((dev[0] - pil[0]) if higher_is_better else (pil[0] - dev[0]))
+        spreads.append(max(pil[2] - pil[1], dev[2] - dev[1]))
+    text = ", ".join("%+.3g against a spread of %.3g" % (g, s) for g, s in zip(gains, spreads))
+    if all(g > s for g, s in zip(gains, spreads)):
+        return "  %s: gain of device over pil per run [%s]: %s -> --png_encoder device is RECOMMENDED" % (name, unit, text)
+    if all(-g > s for g, s in zip(gains, spreads)):
+        return "  %s: gain of device over pil per run [%s]: %s -> --png_encoder device LOST; not recommended" % (name, unit, text)
+    return "  %s: gain of device over pil per run [%s]: %s -> inside the spread in at least one run; NOT recommended" % (name, unit, text)
+
+
+def png_encode_commands(a):
+    """The two commands that write PNGs, each with ``--png_encoder pil`` and ``device``, twice, the routes alternating, after a
+    decode-and-compare of both outputs.  ``export_detection``: wall time of the command on a synthetic object tree (tests/
+    detection_tree.py, 32 images of two KITTI sizes) from saved disparities (``--ext_disp_to_eval``: scoring, export, encoding and
+    writing; the network does not run).  ``Trainer``: ``Trainer.step`` counts per second over one epoch of 250 optimiser steps (500 micro-batches of 6 resident
+    synthetic scene batches, the workload of bench.py) with ``log_images`` at the default ``--log_frequency 250``: two log events of
+    one 768x4480 sheet each."""
+    from PIL import Image
+    sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]      # the synthetic trees the tests use
+    import detection_tree
+    from fusiondepth_amd import detection as D
+    from fusiondepth_amd import export_detection as X
+    from fusiondepth_amd import log_images as L
+    from fusiondepth_amd import synthetic
+    from fusiondepth_amd.options import MonodepthOptions
+    from fusiondepth_amd.trainer import Trainer
+    import contextlib
+    import io
+    lines, reps = [], max(2, min(a.reps, 3))
+    quiet = contextlib.redirect_stdout(io.StringIO())
+    with tempfile.TemporaryDirectory() as tmp, quiet:
+        # ---- export_detection
+        raw_root, obj_root, splits = (os.path.join(tmp, d) for d in ("raw", "object", "splits"))
+        _, obj_lines, _ = detection_tree.make_trees(raw_root, obj_root, frames_per_date=16)
+        os.makedirs(os.path.join(splits, "detection"))
+        with open(os.path.join(splits, "detection", "test.txt"), "w") as f:
+            f.write("\n".join(obj_lines) + "\n")
+        D.export_gt_depths_detec(obj_root, obj_lines, "detec", os.path.join(splits, "detection", D.detec_output_name("detec")))
+        rng = np.random.RandomState(5)
+        n = len(obj_lines)
+        base = torch.from_numpy(rng.uniform(0.02, 0.6, (n, 24, 80)).astype(np.float32))
+        disp = torch.nn.functional.interpolate(base[:, None], size=(192, 640), mode="bicubic", align_corners=False)[:, 0]
+        disp = (disp + torch.from_numpy(rng.uniform(-0.004, 0.004, (n, 192, 640)).astype(np.float32))).clamp_(0.01, 1.0)
+        saved = os.path.join(tmp, "disps.npy")
+        np.save(saved, disp.numpy())
+        flags = ["--splits_dir", splits, "--eval_mono", "--ext_disp_to_eval", saved, "--data_path", obj_root]
+
+        def export_pil():
+            return X.main(flags + ["--det_name", "bench_pil"])
+
+        def export_dev():
+            return X.main(flags + ["--det_name", "bench_dev", "--png_encoder", "device"])
+
+        rp, rd = export_pil(), export_dev()
+        assert np.array_equal(rp[0], rd[0]) and np.array_equal(rp[1], rd[1])
+        sizes = [0, 0]
+        for p, d in zip(rp[3], rd[3]):
+            assert np.array_equal(np.asarray(Image.open(p)), np.asarray(Image.open(d))), "the two encoders' maps differ: %s" % p
+            sizes[0] += os.path.getsize(p)
+            sizes[1] += os.path.getsize(d)
+        runs = [alternate([export_pil, export_dev], reps, _wall_ms) for _ in (1, 2)]
+        for k, (tp, td) in enumerate(runs):
+            lines.append("  export_detection, %d maps (ext_disp_to_eval; scoring + export + encoding + writing), run %d: pil %.1f ms (%.1f, %.1f); "
+                         "device %.1f ms (%.1f, %.1f) -> %.2fx; file bytes pil %d, device %d"
+                         % (n, k + 1, tp[0], tp[1], tp[2], td[0], td[1], td[2], tp[0] / td[0], sizes[0], sizes[1]))
+        lines.append(_verdict("export_detection", "ms", runs, False))
+
+        # ---- Trainer steps per second with log_images
+        opt = MonodepthOptions().parse(["--num_layers", "18", "--weights_init", "scratch", "--batch_size", "12", "--height", "192", "--width",
+                                        "640", "--log_dir", os.path.join(tmp, "logs"), "--save_frequency", "1000"])
+        torch.manual_seed(5)
+        tr = Trainer(opt, verbose=False)
+        tr.opt.num_epochs = 1
+        tr.log_images = True
+        pool_ = []
+        for i in range(8):
+            mb = synthetic.make_scene_batch(tr.batch_size, 192, 640, seed=1234 + i, clutter=0.5)
+            mb.pop("depth_gt", None)
+            for f in (-1, 1):
+                mb.pop(("T_gt", f), None)
+            pool_.append(mb)
+        loader = [pool_[i % 8] for i in range(250 * tr.accumulate_step)]
+        steps = [0]
+
+        def epoch(encoder):
+            def run():
+                tr.png_encoder = encoder
+                tr.train(loader)                                 # one epoch; returns after the sink's thread has written everything
+                steps[0] = tr.step
+            return run
+
+        epoch("pil")()                                           # warm-up, and the decode-and-compare on its last batch
+        caught = []
+        sink, tr.image_sink = tr.image_sink, (lambda mode, step, sheets, tiles: caught.append(sheets))
+        tr.log_pictures("train", *tr._last_io)
+        tr.image_sink, tr.png_encoder = sink, "device"
+        tr.log_pictures("train", *tr._last_io)
+        tr.close()
+        written = np.asarray(Image.open(L.PngSink.path(tr.log_path, "train", tr.step, 0)))
+        assert np.array_equal(written, caught[0][0]), "the device-encoded sheet does not decode to the rendered one"
+        runs = [alternate([epoch("pil"), epoch("device")], reps, _wall_ms) for _ in (1, 2)]
+        rate = lambda ms: 1e3 * steps[0] / ms                    # noqa: E731
+        rates = []
+        for k, (tp, td) in enumerate(runs):
+            rp_, rd_ = (rate(tp[0]), rate(tp[2]), rate(tp[1])), (rate(td[0]), rate(td[2]), rate(td[1]))
+            rates.append((rp_, rd_))
+            lines.append("  Trainer, %d micro-batch steps of 6 images (Trainer.step; 250 optimiser steps of 12) with log_images at --log_frequency 250 (2 events, one %dx%d sheet each), run %d: "
+                         "pil %.2f steps/s (%.2f, %.2f); device %.2f steps/s (%.2f, %.2f) -> %.3fx"
+                         % (steps[0], written.shape[0], written.shape[1], k + 1, rp_[0], rp_[1], rp_[2], rd_[0], rd_[1], rd_[2], rd_[0] / rp_[0]))
+        lines.append(_verdict("train --log_images", "steps/s", rates, True))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar"),
+    ap.add_argument("--step", choices=("eigen", "detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar",
+                                       "png_encode"),
                     default="eigen")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -724,11 +932,12 @@ def main():
         a.out = os.path.join(ROOT, "profiles", {"eigen": "eigen_eval_time.log", "detection": "detection_export_time.log",
                                                 "val": "val_time.log", "completion_val": "completion_val_time.log",
                                                 "semantic": "eigen_class_time.log", "visualize": "visualize_time.log",
-                                                "log_images": "log_images_time.log", "pseudo_lidar": "pseudo_lidar_time.log"}[a.step])
-    if a.step in ("detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar"):
+                                                "log_images": "log_images_time.log", "pseudo_lidar": "pseudo_lidar_time.log",
+                                                "png_encode": "png_encode_time.log"}[a.step])
+    if a.step in ("detection", "val", "completion_val", "semantic", "visualize", "log_images", "pseudo_lidar", "png_encode"):
         text = "\n".join({"detection": detection_step, "val": val_step, "completion_val": completion_val_step,
                           "semantic": semantic_step, "visualize": visualize_step, "log_images": log_images_step,
-                          "pseudo_lidar": pseudo_lidar_step}[a.step](a))
+                          "pseudo_lidar": pseudo_lidar_step, "png_encode": png_encode_step}[a.step](a))
         print(text)
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "a") as fh:
