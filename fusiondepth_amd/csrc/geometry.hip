@@ -515,28 +515,33 @@ __global__ void k_bilinear_fwd(const float* __restrict__ x, float* __restrict__ 
                                ly * (hx * xi[y1 * Win + x0] + lx * xi[y1 * Win + x1]);
     }
 }
-// Adjoint in gather form: each input pixel collects from the output pixels whose 2x2 footprint holds it.  The bilinear
-// weight factorises, w(oy, ox) = wy(oy) * wx(ox): the column weights of the candidate window are computed once per
-// thread (<= MAXW = 24 candidates for upsampling ratios <= 8, the four pyramid scales), then every candidate row costs one weight + a short dot product.
+// Candidate window [lo, hi] of the output indices whose two source taps can include input index i, for n_out >= n_in at any ratio,
+// integer or not.  Before the border clamps, output o touches i only if its source coordinate (o + 0.5) * n_in / n_out - 0.5 lies in
+// (i - 1, i + 1), that is (2i - 1) * n_out < (2o + 1) * n_in < (2i + 3) * n_out: in exact integers the smallest such o is
+// floor(a / d) + 1 and the largest ceil(b / d) - 1 with a = (2i - 1) * n_out - n_in, b = (2i + 3) * n_out - n_in, d = 2 * n_in.  The window
+// is one wider on each side, for the float32 coordinate of fd_bilinear_src.  The clamps send every output below the first / above the last
+// source sample to input 0 / n_in - 1, whose windows therefore reach the border.  (a >= 0 for i >= 1 because n_out >= n_in.)
+__device__ __forceinline__ void bilinear_bwd_window(int i, int n_in, int n_out, int& lo, int& hi) {
+    const long a = (long)(2 * i - 1) * n_out - n_in, b = (long)(2 * i + 3) * n_out - n_in, d = 2L * n_in;
+    const long l = i == 0 ? 0 : a / d, h = i == n_in - 1 ? n_out - 1 : (b + d - 1) / d;
+    lo = (int)l;
+    hi = (int)(h > n_out - 1 ? n_out - 1 : h);
+}
+// Adjoint in gather form, for Hout >= Hin and Wout >= Win: each input pixel collects from the output pixels whose 2x2 footprint holds
+// it.  The bilinear weight factorises, w(oy, ox) = wy(oy) * wx(ox): the column weights of the candidate window are computed once per
+// thread (<= 2 r + 2 <= 18 candidates at upsampling ratios r <= 8, the four pyramid scales; MAXW = 24), then every candidate row costs
+// one weight + a short dot product.  A window wider than MAXW (interior pixels at r > 11) takes the scalar form.
 __global__ void k_bilinear_bwd(const float* __restrict__ gy, float* __restrict__ gx, int Hin, int Win, int Hout,
                                int Wout, float sh, float sw) {
     constexpr int MAXW = 24;
     const int bc = blockIdx.y;
     const int Pi = Hin * Win;
     const float* g = gy + (long)bc * Hout * Wout;
-    const int ry = (Hout + Hin - 1) / Hin, rx = (Wout + Win - 1) / Win;  // upsampling ratio (ceil)
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < Pi; p += gridDim.x * blockDim.x) {
         const int iy = p / Win, ix = p - iy * Win;
-        // output rows whose source interval [y0, y1] contains iy satisfy (iy-0.5)*r - 0.5 <= oy < (iy+1.5)*r - 0.5
-        // (before edge clamping, which only adds rows at the borders handled by the max/min below); one extra on each side
-        int oy_lo = (2 * iy - 1) * ry / 2 - 2, oy_hi = (2 * iy + 3) * ry / 2 + 1;
-        int ox_lo = (2 * ix - 1) * rx / 2 - 2, ox_hi = (2 * ix + 3) * rx / 2 + 1;
-        if (iy == 0) oy_lo = 0;
-        if (ix == 0) ox_lo = 0;
-        if (iy == Hin - 1) oy_hi = Hout - 1;
-        if (ix == Win - 1) ox_hi = Wout - 1;
-        oy_lo = oy_lo < 0 ? 0 : oy_lo; ox_lo = ox_lo < 0 ? 0 : ox_lo;
-        oy_hi = oy_hi > Hout - 1 ? Hout - 1 : oy_hi; ox_hi = ox_hi > Wout - 1 ? Wout - 1 : ox_hi;
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        bilinear_bwd_window(iy, Hin, Hout, oy_lo, oy_hi);
+        bilinear_bwd_window(ix, Win, Wout, ox_lo, ox_hi);
         float acc = 0.f;
         const int nx = ox_hi - ox_lo + 1;
         if (nx <= MAXW) {
@@ -579,6 +584,7 @@ __global__ void k_bilinear_bwd(const float* __restrict__ gy, float* __restrict__
 }
 extern "C" int fd_bilinear_up_fwd(const float* x, float* y, int BC, int Hin, int Win, int Hout, int Wout, void* stream) {
     FD_REQUIRE(x && y && BC > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, "fd_bilinear_up_fwd: bad args");
+    FD_REQUIRE(BC < 65536, "fd_bilinear_up_fwd: %d planes, the grid takes at most 65535", BC);
     hipLaunchKernelGGL(k_bilinear_fwd, dim3(ew_grid((long)Hout * Wout), BC), dim3(256), 0, (hipStream_t)stream, x, y, Hin,
                        Win, Hout, Wout, (float)Hin / (float)Hout, (float)Win / (float)Wout);
     FD_LAUNCH_CHECK("fd_bilinear_up_fwd");
@@ -588,6 +594,7 @@ extern "C" int fd_bilinear_up_bwd(const float* gy, float* gx, int BC, int Hin, i
                                   void* stream) {
     FD_REQUIRE(gy && gx && BC > 0 && Hin > 0 && Win > 0 && Hout >= Hin && Wout >= Win,
                "fd_bilinear_up_bwd: bad args (only upsampling is supported)");
+    FD_REQUIRE(BC < 65536, "fd_bilinear_up_bwd: %d planes, the grid takes at most 65535", BC);
     hipLaunchKernelGGL(k_bilinear_bwd, dim3(ew_grid((long)Hin * Win), BC), dim3(256), 0, (hipStream_t)stream, gy, gx, Hin,
                        Win, Hout, Wout, (float)Hin / (float)Hout, (float)Win / (float)Wout);
     FD_LAUNCH_CHECK("fd_bilinear_up_bwd");

@@ -163,6 +163,19 @@ __device__ __forceinline__ float ssim_from_sums(float Sx, float Sy, float Sxx, f
     const float v = (1.f - fdiv(n, d)) * 0.5f;
     return fminf(fmaxf(v, 0.f), 1.f);
 }
+// The same for the stand-alone map (k_ssim_fwd), with every product rounded before it is added, as the reference's tensor operations
+// round theirs.  Left to contract, the compiler fuses some of these into FMAs and not others, and where the two windows are equal
+// numerator and denominator then differ in the last bit: the loss there must be exactly 0, as the reference's is.  The fused kernels
+// and k_reproj_map keep the contracted form above: their maps feed training runs, which are compared step for step.
+__device__ __forceinline__ float ssim_from_sums_rounded(float Sx, float Sy, float Sxx, float Syy, float Sxy) {
+#pragma clang fp contract(off)
+    const float mx = div9(Sx), my = div9(Sy);
+    const float sx = div9(Sxx) - mx * mx, sy = div9(Syy) - my * my, sxy = div9(Sxy) - mx * my;
+    const float n = (2.f * mx * my + C1) * (2.f * sxy + C2);
+    const float d = (mx * mx + my * my + C1) * (sx + sy + C2);
+    const float v = (1.f - fdiv(n, d)) * 0.5f;
+    return fminf(fmaxf(v, 0.f), 1.f);
+}
 
 // d(SSIM loss)/d(mu_x, E[x^2], E[xy]) at one window; all zero where the clamp is active.
 __device__ __forceinline__ void ssim_coefs(float Sx, float Sy, float Sxx, float Syy, float Sxy, float w, float& ca,
@@ -713,6 +726,9 @@ __global__ void __launch_bounds__(NT) k_ssim_fwd(const float* __restrict__ xg, c
     const int x = x0t + tx;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
+        // no contraction: the compiler made FMA chains of the x*x and y*y sums and multiplied and added for x*y, so that equal windows
+        // had unequal sums; rounded products added in raster order are also what the reference's AvgPool2d sees
+#pragma clang fp contract(off)
         const int y = y0t + ty * PPT + i;
         if (y >= H || x >= W) continue;
         float Sx = 0.f, Sy = 0.f, Sxx = 0.f, Syy = 0.f, Sxy = 0.f;
@@ -723,7 +739,7 @@ __global__ void __launch_bounds__(NT) k_ssim_fwd(const float* __restrict__ xg, c
                 const float xv = s_x[(ty * PPT + i + dy) * W1 + tx + dx], yv = s_y[(ty * PPT + i + dy) * W1 + tx + dx];
                 Sx += xv; Sy += yv; Sxx += xv * xv; Syy += yv * yv; Sxy += xv * yv;
             }
-        out[base + (long)y * W + x] = ssim_from_sums(Sx, Sy, Sxx, Syy, Sxy);
+        out[base + (long)y * W + x] = ssim_from_sums_rounded(Sx, Sy, Sxx, Syy, Sxy);
     }
 }
 

@@ -199,7 +199,9 @@ class _BilinearUp(torch.autograd.Function):
 
 
 def bilinear_upsample(x, size):
-    """F.interpolate(x, size, mode='bilinear', align_corners=False) for upsampling."""
+    """F.interpolate(x, size, mode='bilinear', align_corners=False) of [B, C, Hin, Win], B * C < 65536.  The forward takes any size;
+    the gradient exists for size[0] >= Hin and size[1] >= Win only (any ratio, integer or fractional, per axis) and a backward
+    pass through a smaller size raises."""
     return _BilinearUp.apply(x, int(size[0]), int(size[1]))
 
 

@@ -173,7 +173,9 @@ int fd_project3d_bwd(const float* points, const float* K, const float* T, const 
 /* layers.py:187-201 Cat_xy.forward (refiner.py input channels). out [B,3,H,W]. */
 int fd_cat_xy_fwd(const float* depth, const float* inv_K, float* out, int B, int H, int W, void* stream);
 
-/* F.interpolate(x,[H,W],mode="bilinear",align_corners=False) (trainer.py:434-435,:579), C channels. */
+/* F.interpolate(x,[Hout,Wout],mode="bilinear",align_corners=False) (trainer.py:434-435,:579) on BC = B*C planes, 0 < BC < 65536.
+ * _fwd takes any sizes (ATen's rule, no antialiasing).  _bwd is its adjoint for Hout >= Hin and Wout >= Win only, at any ratio,
+ * integer or fractional, the two axes independently; anything smaller is refused (non-zero return, gx not written). */
 int fd_bilinear_up_fwd(const float* x, float* y, int BC, int Hin, int Win, int Hout, int Wout, void* stream);
 int fd_bilinear_up_bwd(const float* gy, float* gx, int BC, int Hin, int Win, int Hout, int Wout, void* stream);
 

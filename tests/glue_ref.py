@@ -1,6 +1,7 @@
 """float64 references, seeded inputs and the case lists for the memory-bound glue kernels of csrc/geometry.hip and csrc/pool.hip
 (disparity -> depth, pose matrices, projection matrices, back-projection, projection, Cat_xy, max-pool, the decoder's input assembly,
-nearest x2, activation backward, axpby, input normalisation, spatial mean, depth metrics, Adam).
+nearest x2, activation backward, axpby, input normalisation, spatial mean, depth metrics, Adam) and for the stand-alone loss-map kernels
+(bilinear resize and its adjoint, SSIM, the reprojection loss map, the edge-aware smoothness loss, the combination of the loss terms).
 
 Every reference is dtype-generic: called with ``torch.float64`` it is the ground truth, called with ``torch.float32`` it is the CPU
 oracle whose own distance from the ground truth is the *yardstick* of a comparison (``bound``).  ``oracle.layers`` is used wherever it
@@ -42,6 +43,48 @@ MEAN_PLANES = (1, 36)
 DEPTH_ERR_N = (1, 7, 256, 65536 + 13, 375 * 1242 // 3)         # 256 partial sums of 256 threads = 65536
 ADAM_N = (1, 257, 1048576 + 257)
 ADAM_BETAS, ADAM_EPS, ADAM_LR = (0.9, 0.999), 1e-8, 1.5e-4
+# bilinear resize (BC, Hin, Win, Hout, Wout), forward and adjoint; the adjoint runs one thread per input pixel in blocks of 256
+BILINEAR_CASES = (
+    (1, 1, 1, 1, 1), (1, 1, 1, 3, 5),                              # a single input pixel: every output is its copy
+    (2, 1, 7, 4, 7),                                               # one axis only
+    (3, 5, 7, 5, 7),                                               # identity
+    (6, 3, 5, 6, 10), (2, 6, 20, 24, 80), (2, 3, 10, 24, 80),      # integer ratios 2, 4 and 8: the pyramid
+    (2, 2, 3, 24, 36),                                             # ratio 12: interior windows wider than MAXW = 24 (scalar branch), border windows unrolled
+    (1, 6, 6, 7, 7),                                               # fractional ratios; the smallest shape at which the ceiling-ratio window lost a row
+    (2, 8, 12, 9, 13), (2, 5, 7, 8, 11), (1, 16, 20, 24, 31), (1, 7, 9, 9, 16),
+    (1, 4, 6, 8, 7),                                               # integer in y, fractional in x
+    (1, 192, 640, 375, 1242),                                      # the evaluation size, one plane
+    (1, 15, 17, 30, 34), (1, 16, 16, 32, 32), (1, 1, 257, 2, 514),  # input planes of 255, 256 and 257 pixels
+    (1, 257, 1025, 514, 2050),                                     # forward: 1053700 outputs, past ew_grid's 2048 blocks of 256
+    (1, 513, 1025, 513, 1025),                                     # adjoint: 525825 inputs, past ew_grid's 2048 blocks of 256
+)
+BILINEAR_OFFSET_CASE = (2, 5, 7, 8, 11)                            # operands one float off 16-byte alignment
+BILINEAR_DENSE_MAX = 4096                                          # input pixels up to which the CPU test builds the dense matrix
+# SSIM and the reprojection map: tiles of 64 x 16 with a halo of 1 (2 in the backward); the reflect fold acts on rows / columns 1 and n - 2
+SSIM_HW = ((4, 4),                                                 # the minimum: every pixel next to a fold
+           (4, 64), (16, 64),                                      # one tile wide; exactly one tile
+           (15, 63),                                               # one short of a tile both ways
+           (17, 65), (18, 66),                                     # the folded row / column on either side of the tile seam
+           (33, 129),                                              # three tiles each way, the last one pixel deep
+           (5, 130))                                               # the fold in the third tile's second column
+SSIM_PLANES = (1, 7)
+SSIM_UNIFORM_CASE = (7, 33, 129)                                   # independent uniform images: the variance cancellation at its worst
+SSIM_EQUAL_CASE = (1, 18, 66)                                      # x == y on the 8 x 8 block in the bottom right corner, across both tile seams
+REPROJ_B = (1, 3)
+REPROJ_GAP = 5                                                     # floats between the images of `out`
+# smoothness (B, H, W): 1024 pixels per block; k_image_mean takes float4 loads, four in flight (4096 float4s a round), when P % 4 == 0
+SMOOTH_SHAPES = ((2, 2),                                           # the minimum
+                 (3, 341), (2, 512), (5, 205),                     # 1023, 1024 and 1025 pixels (1025: scalar mean)
+                 (96, 128), (4, 3073),                             # n4 = 3072: the last unrolled round is not entered; 3073: it is
+                 (128, 128), (4, 4097))                            # n4 = 4096: one full round, no tail; 4097: a tail of one
+SMOOTH_B = (1, 3)
+SMOOTH_OFFSET_CASE = (1, 128, 128)                                 # off alignment: the scalar mean
+SMOOTH_EXTRA = ((2, 330, 400, False), (2, 330, 400, True),         # 2 x 129 = 258 partial sums for the 256 threads of k_smooth_fin
+                (1, 513, 513, True))                               # 1029 blocks of 256 wanted by k_sub_per_image, 1024 launched
+SMOOTH_COT = 1.7
+COMBINE_N = (1, 2, 3, 4)
+COMBINE_SI = ("all", "none", "scale0")
+COMBINE_WEIGHT, COMBINE_COT = 1e-3, 1.3
 
 
 # ---------------------------------------------------------------------------------------------- error measure
@@ -454,3 +497,165 @@ def adam_torch(sc, dtype, shapes=None):
         opt.step()
     cat = lambda key: torch.cat([opt.state[p][key].reshape(-1) for p in params])
     return {"p": torch.cat([p.detach().reshape(-1) for p in params]), "exp_avg": cat("exp_avg"), "exp_avg_sq": cat("exp_avg_sq")}, opt
+
+
+# ---------------------------------------------------------------------------------------------- bilinear resize and its adjoint
+def smooth_images(rng, *shape):
+    """Uniform noise box-filtered twice (3 x 3, edge-replicated) over the last two axes: values in (0, 1), neighbours ~0.03 apart."""
+    a = rng.rand(*shape)
+    for _ in range(2):
+        p = np.pad(a, [(0, 0)] * (a.ndim - 2) + [(1, 1), (1, 1)], mode="edge")
+        a = sum(p[..., dy:dy + shape[-2], dx:dx + shape[-1]] for dy in range(3) for dx in range(3)) / 9.0
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def bilinear_inputs(BC, Hin, Win, Hout, Wout):
+    """x: a smooth image, as the disparity and depth maps are that the project resizes; cot: white noise.  ATen's float32 rule, which the
+    kernel follows, rounds the source coordinate to float32: at 640 -> 1242 columns that moves a weight by up to ~1e-4, and on a
+    white-noise x (neighbours up to 1 apart) the float32 CPU oracle itself is then 4.8e-5 of scale from float64, above the 1.1e-5 that
+    the forward comparison may allow.  On the smooth x the same coordinate error costs ~30 times less, while a wrong tap or a swapped
+    weight still costs ~0.03 / 0.5 of scale.  The adjoint sees the white-noise cotangent at every shape."""
+    rng = _rng(15, BC, Hin, Win, Hout, Wout)
+    return {"x": _t(smooth_images(rng, 1, BC, Hin, Win)), "cot": _t(rng.randn(1, BC, Hout, Wout)), "size": (Hout, Wout)}
+
+
+def bilinear_ref(inp, dtype):
+    x = inp["x"].to(dtype).clone().requires_grad_(True)
+    y = F.interpolate(x, inp["size"], mode="bilinear", align_corners=False)
+    (gx,) = _grad([y], [inp["cot"]], [x])
+    return {"y": y.detach(), "gx": gx}
+
+
+def bilinear_matrix(Hin, Win, Hout, Wout):
+    """The forward reference as a dense float64 matrix [Hout * Wout, Hin * Win], one unit image per column."""
+    eye = torch.eye(Hin * Win, dtype=F64).view(Hin * Win, 1, Hin, Win)
+    return F.interpolate(eye, (Hout, Wout), mode="bilinear", align_corners=False).reshape(Hin * Win, Hout * Wout).t()
+
+
+# ---------------------------------------------------------------------------------------------- SSIM, reprojection loss map
+SSIM_KINDS = ("smooth", "uniform", "equal")
+
+
+@functools.lru_cache(maxsize=None)
+def ssim_inputs(planes, H, W, kind="smooth"):
+    """``smooth``: a smooth image and the same plus noise of 0.05, clipped to [0, 1] (tests/test_gpu_losspath.py::test_ssim_fwd_bwd);
+    ``uniform``: two independent uniform images; ``equal``: smooth, with y == x on the 8 x 8 block in the bottom right corner."""
+    rng = _rng(16, planes, H, W, SSIM_KINDS.index(kind))
+    if kind == "uniform":
+        x, y = rng.rand(1, planes, H, W), rng.rand(1, planes, H, W)
+    else:
+        x = smooth_images(rng, 1, planes, H, W)
+        y = np.clip(x + 0.05 * rng.randn(1, planes, H, W), 0, 1)
+    x, y = _t(x), _t(y)
+    if kind == "equal":
+        y[..., H - 8:, W - 8:] = x[..., H - 8:, W - 8:]
+    return {"x": x, "y": y, "cot": _t(rng.rand(1, planes, H, W))}
+
+
+def ssim_preclamp(x, y):
+    """(1 - SSIM) / 2 before the clamp to [0, 1] (oracle.layers.ssim without its last step): where this leaves [0, 1] the gradient is cut."""
+    xp, yp = F.pad(x, (1, 1, 1, 1), mode="reflect"), F.pad(y, (1, 1, 1, 1), mode="reflect")
+    mu_x, mu_y = F.avg_pool2d(xp, 3, 1), F.avg_pool2d(yp, 3, 1)
+    sig_x = F.avg_pool2d(xp ** 2, 3, 1) - mu_x ** 2
+    sig_y = F.avg_pool2d(yp ** 2, 3, 1) - mu_y ** 2
+    sig_xy = F.avg_pool2d(xp * yp, 3, 1) - mu_x * mu_y
+    num = (2 * mu_x * mu_y + OL.SSIM_C1) * (2 * sig_xy + OL.SSIM_C2)
+    den = (mu_x ** 2 + mu_y ** 2 + OL.SSIM_C1) * (sig_x + sig_y + OL.SSIM_C2)
+    return (1 - num / den) / 2
+
+
+def ssim_window_difference(inp):
+    """min over the 3 x 3 windows (reflect-padded) of max |x - y| inside the window: > 0 means no window sees two equal images."""
+    d = F.pad((inp["x"].to(F64) - inp["y"].to(F64)).abs(), (1, 1, 1, 1), mode="reflect")
+    return float(F.max_pool2d(d, 3, 1).min())
+
+
+def ssim_ref(inp, dtype, use_gx=True, use_gy=True):
+    """oracle.layers.ssim (dtype-generic) and the gradients of <ssim, cot>; a gradient nobody asks for is left out."""
+    x, y = (inp[k].to(dtype).clone().requires_grad_(True) for k in ("x", "y"))
+    s = OL.ssim(x, y)
+    gx, gy = _grad([s], [inp["cot"]], [x, y])
+    out = {"ssim": s.detach()}
+    if use_gx:
+        out["gx"] = gx
+    if use_gy:
+        out["gy"] = gy
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reproj_inputs(B, H, W):
+    rng = _rng(17, B, H, W)
+    pred = smooth_images(rng, B, 3, H, W)
+    return {"pred": _t(pred), "target": _t(np.clip(pred + 0.05 * rng.randn(B, 3, H, W), 0, 1))}
+
+
+def reproj_ref(inp, dtype, use_ssim):
+    """trainer.py:476-488: 0.85 * ssim.mean(1, True) + 0.15 * |target - pred|.mean(1, True), or the L1 term alone."""
+    pred, target = inp["pred"].to(dtype), inp["target"].to(dtype)
+    l1 = (target - pred).abs().mean(1, True)
+    return {"map": 0.85 * OL.ssim(pred, target).mean(1, True) + 0.15 * l1 if use_ssim else l1}
+
+
+# ---------------------------------------------------------------------------------------------- edge-aware smoothness
+def smooth_step(n):
+    """The spacing 2^-e of n distinct disparities in (0.01, 1): the largest power of two with 0.01 + (n + 1) steps < 1."""
+    return 2.0 ** -math.ceil(math.log2(n / 0.98))
+
+
+@functools.lru_cache(maxsize=None)
+def smooth_inputs(B, H, W):
+    """Disparities: a random permutation of B * H * W consecutive multiples of smooth_step, the first one just above 0.01 - all of them
+    exact in float32, no two equal, so that |d_p - d_q| has no kink and sgn(d_p - d_q) no choice at any edge, in any precision, with or
+    without the division by the image's mean.  Image: uniform noise, so that every edge has its own weight exp(-|dI|)."""
+    n = B * H * W
+    step = smooth_step(n)
+    k0 = int(0.01 / step) + 1
+    assert k0 + n < 2 ** 24 and (k0 + n) * step < 1.0
+    rng = _rng(18, B, H, W)
+    disp = (k0 + rng.permutation(n)).astype(np.float64) * step
+    return {"disp": _t(disp.reshape(B, 1, H, W)), "img": _t(rng.rand(B, 3, H, W)), "step": step}
+
+
+def smooth_min_neighbour_difference(inp):
+    d = inp["disp"].to(F64)
+    return min(float((d[..., :, 1:] - d[..., :, :-1]).abs().min()), float((d[..., 1:, :] - d[..., :-1, :]).abs().min()))
+
+
+def smooth_ref(inp, dtype, normalize):
+    """oracle.layers.get_smooth_loss on d, or on d / (d.mean(2, True).mean(3, True) + 1e-7) (trainer.py:569-571), and SMOOTH_COT times its
+    gradient in d."""
+    d = inp["disp"].to(dtype).clone().requires_grad_(True)
+    n = d / (d.mean(2, True).mean(3, True) + 1e-7) if normalize else d
+    loss = OL.get_smooth_loss(n, inp["img"].to(dtype))
+    (g,) = _grad([loss], [torch.tensor(SMOOTH_COT)], [d])
+    return {"loss": loss.detach(), "g_disp": g}
+
+
+# ---------------------------------------------------------------------------------------------- combination of the loss terms
+def combine_inputs(n, si_mode):
+    """n scales of (photometric, smoothness, SI) scalars of the sizes the trainer sees; SI at every scale, at none or at scale 0 only."""
+    rng = _rng(19, n, COMBINE_SI.index(si_mode))
+    has_si = [si_mode == "all" or (si_mode == "scale0" and s == 0) for s in range(n)]
+    draw = lambda lo, hi: _t(rng.uniform(lo, hi, 1)).reshape(())
+    return {"photo": [draw(0.05, 0.2) for _ in range(n)], "smooth": [draw(1.0, 60.0) for _ in range(n)],
+            "si": [draw(0.01, 0.3) if h else None for h in has_si], "w": COMBINE_WEIGHT, "cot": COMBINE_COT}
+
+
+def combine_ref(inp, dtype):
+    """trainer.py:569-596 in the operation order of k_combine_losses, which is the reference's: loss_s = photo_s + w * smooth_s / 2^s,
+    total += loss_s, total += si_s where there is one, total / n.  The weight and the cotangent reach the kernels as float32.
+    -> loss [n], total, and the gradients of cot * total in photo_s, smooth_s, si_s (the last for every scale, as the kernel writes it)."""
+    n = len(inp["photo"])
+    w, cot = float(np.float32(inp["w"])), float(np.float32(inp["cot"]))
+    total, losses = torch.zeros((), dtype=dtype), []
+    for s in range(n):
+        loss = inp["photo"][s].to(dtype) + w * inp["smooth"][s].to(dtype) / (2 ** s)
+        total = total + loss
+        losses.append(loss)
+        if inp["si"][s] is not None:
+            total = total + inp["si"][s].to(dtype)
+    gt = torch.tensor(cot, dtype=dtype) / n
+    return {"loss": torch.stack(losses), "total": total / n, "g_photo": torch.stack([gt] * n),
+            "g_smooth": torch.stack([gt * w / (2 ** s) for s in range(n)]), "g_si": torch.stack([gt] * n)}

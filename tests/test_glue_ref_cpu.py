@@ -209,3 +209,175 @@ def test_adam_restatement(n):
     if n >= 257:
         split, _ = R.adam_torch(sc, F64, shapes=[(n - 100,), (10, 10)])
         assert R.rel_err(split["p"], R.adam_ref(sc)["p"]) < 1e-12
+
+
+# ================================================================================================ the loss-map kernels' references
+def finite_yardsticks(what, fn, *args):
+    """rel_err of the float32 oracle against the float64 reference per output, reported; it has to be a number, its size is the GPU
+    test's business (the SSIM gradients lose more than AGREE to the cancellation in E[x^2] - mu^2)."""
+    ref, ora = fn(*args[:1], F64, *args[1:]), fn(*args[:1], F32, *args[1:])
+    for k in ref:
+        assert ref[k].dtype == F64 and ora[k].dtype == F32, "%s %s: dtypes %s, %s" % (what, k, ref[k].dtype, ora[k].dtype)
+        assert bool(torch.isfinite(ref[k]).all()) and bool(torch.isfinite(ora[k]).all()), "%s %s is not finite" % (what, k)
+        y = R.rel_err(ora[k], ref[k])
+        report("yardstick %s %s" % (what, k), y, float("inf"), "(must be finite)")
+        assert np.isfinite(y), "%s %s: yardstick %r" % (what, k, y)
+    return ref, ora
+
+
+@pytest.mark.parametrize("BC,Hin,Win,Hout,Wout", R.BILINEAR_CASES)
+def test_bilinear(BC, Hin, Win, Hout, Wout):
+    inp = R.bilinear_inputs(BC, Hin, Win, Hout, Wout)
+    assert inp["x"].shape == (1, BC, Hin, Win) and inp["cot"].shape == (1, BC, Hout, Wout) and Hout >= Hin and Wout >= Win
+    ref, _ = finite_yardsticks("bilinear %dx%dx%d -> %dx%d" % (BC, Hin, Win, Hout, Wout), R.bilinear_ref, inp)
+    assert ref["y"].shape == inp["cot"].shape and ref["gx"].shape == inp["x"].shape
+    if Hin * Win > R.BILINEAR_DENSE_MAX:
+        return
+    # the adjoint, independently of autograd: the forward reference as a dense matrix, transposed
+    M = R.bilinear_matrix(Hin, Win, Hout, Wout)
+    assert R.rel_err((M @ inp["x"].to(F64).reshape(BC, -1).t()).t().reshape(ref["y"].shape), ref["y"]) < 1e-12
+    assert float((M.sum(1) - 1).abs().max()) < 1e-12 and float(M.min()) >= 0
+    want = (M.t() @ inp["cot"].to(F64).reshape(BC, -1).t()).t().reshape(ref["gx"].shape)
+    e = R.rel_err(ref["gx"], want)
+    report("bilinear %dx%dx%d -> %dx%d gradient reference against M^T cot" % (BC, Hin, Win, Hout, Wout), e, 1e-12)
+    assert e <= 1e-12
+
+
+def test_bilinear_cases_cover_their_edges():
+    dense = [c for c in R.BILINEAR_CASES if c[1] * c[2] <= R.BILINEAR_DENSE_MAX]
+    assert len(dense) == len(R.BILINEAR_CASES) - 3
+    assert {c[1] * c[2] for c in R.BILINEAR_CASES} >= {255, 256, 257}
+    assert any(c[3] * c[4] > 2048 * 256 for c in R.BILINEAR_CASES) and any(c[1] * c[2] > 2048 * 256 for c in R.BILINEAR_CASES)
+    frac = [c for c in R.BILINEAR_CASES if c[3] % c[1] or c[4] % c[2]]
+    assert (1, 6, 6, 7, 7) in frac and len(frac) == 7 and R.BILINEAR_OFFSET_CASE in frac
+
+
+def _ssim_cases():
+    return [(p, H, W, "smooth") for H, W in R.SSIM_HW for p in R.SSIM_PLANES] + [R.SSIM_UNIFORM_CASE + ("uniform",)]
+
+
+@pytest.mark.parametrize("planes,H,W,kind", _ssim_cases())
+def test_ssim(planes, H, W, kind):
+    inp = R.ssim_inputs(planes, H, W, kind)
+    what = "ssim %s %dx%dx%d" % (kind, planes, H, W)
+    diff = R.ssim_window_difference(inp)
+    report("%s min over windows of max |x - y|" % what, diff, 1e-3, "(must be >= the bound)")
+    assert diff >= 1e-3, "a 3x3 window in which the two images are all but equal"
+    pre = R.ssim_preclamp(inp["x"].to(F64), inp["y"].to(F64))
+    margin = min(float(pre.min()), 1.0 - float(pre.max()))
+    report("%s distance of the float64 pre-clamp value from 0 and 1" % what, margin, 1e-4, "(must be >= the bound)")
+    assert margin >= 1e-4
+    ref, _ = finite_yardsticks(what, R.ssim_ref, inp)
+    assert torch.equal(ref["ssim"], pre), "no pixel is clamped, so the clamp changes nothing"
+    assert float(ref["gx"].abs().max()) > 0 and float(ref["gy"].abs().max()) > 0
+    only_x, only_y = R.ssim_ref(inp, F64, True, False), R.ssim_ref(inp, F64, False, True)
+    assert "gy" not in only_x and "gx" not in only_y and torch.equal(only_x["gx"], ref["gx"]) and torch.equal(only_y["gy"], ref["gy"])
+
+
+def test_ssim_of_equal_windows_is_zero():
+    planes, H, W = R.SSIM_EQUAL_CASE
+    inp = R.ssim_inputs(planes, H, W, "equal")
+    assert torch.equal(inp["x"][..., H - 8:, W - 8:], inp["y"][..., H - 8:, W - 8:]) and H - 8 < 16 < H and W - 8 < 64 < W
+    for dt in (F64, F32):
+        s = R.ssim_ref(inp, dt)["ssim"]
+        assert bool(torch.isfinite(s).all())
+        assert not s[..., H - 7:, W - 7:].any(), "windows inside the block (the reflection keeps the last row and column inside)"
+        assert float(s[..., :H - 9, :W - 9].min()) > 0
+
+
+@pytest.mark.parametrize("use_ssim", [True, False])
+@pytest.mark.parametrize("B", R.REPROJ_B)
+@pytest.mark.parametrize("H,W", R.SSIM_HW)
+def test_reprojection_map(H, W, B, use_ssim):
+    inp = R.reproj_inputs(B, H, W)
+    ref, _ = finite_yardsticks("reproj map %dx%dx%d ssim=%d" % (B, H, W, use_ssim), R.reproj_ref, inp, use_ssim)
+    assert ref["map"].shape == (B, 1, H, W) and float(ref["map"].min()) > 0
+
+
+def test_reprojection_map_is_the_oracle_trainers():
+    from oracle import trainer as OT
+    inp = R.reproj_inputs(3, 17, 65)
+    for use_ssim in (True, False):
+        want = OT.reprojection_loss(OT.default_opt(no_ssim=not use_ssim), inp["pred"], inp["target"])
+        assert torch.equal(R.reproj_ref(inp, F32, use_ssim)["map"], want)
+
+
+def _smooth_cases():
+    return [(B, H, W, n) for H, W in R.SMOOTH_SHAPES for B in R.SMOOTH_B for n in (False, True)] + list(R.SMOOTH_EXTRA)
+
+
+@pytest.mark.parametrize("B,H,W,normalize", _smooth_cases())
+def test_smooth_loss(B, H, W, normalize):
+    inp = R.smooth_inputs(B, H, W)
+    d = inp["disp"]
+    assert d.shape == (B, 1, H, W) and 0.01 < float(d.min()) and float(d.max()) <= 1.0
+    assert torch.equal(d.to(F64) / inp["step"], (d.to(F64) / inp["step"]).round()) and d.unique().numel() == d.numel()
+    gap = R.smooth_min_neighbour_difference(inp)
+    # one step of 2^-e >= 2^-19 between any two disparities <= 1: at least 16 float32 roundings of either, divided by the mean or not
+    report("smooth %dx%dx%d min |d_p - d_q| over the edges" % (B, H, W), gap, inp["step"], "(must be >= the bound)")
+    assert gap >= inp["step"] >= 2.0 ** -19
+    what = "smooth %dx%dx%d normalize=%d" % (B, H, W, normalize)
+    ref, ora = finite_yardsticks(what, R.smooth_ref, inp, normalize)
+    assert ref["g_disp"].shape == d.shape and float(ref["loss"]) > 0 and float(ref["g_disp"].abs().min()) > 0
+
+
+def test_smooth_cases_cover_their_edges():
+    px = [H * W for H, W in R.SMOOTH_SHAPES]
+    assert px[1:4] == [1023, 1024, 1025] and [p // 4 for p in px[4:]] == [3072, 3073, 4096, 4097] and all(p % 4 == 0 for p in px[4:])
+    assert 2 * -(-330 * 400 // 1024) == 258 and -(-513 * 513 // 256) > 1024
+
+
+@pytest.mark.parametrize("si_mode", R.COMBINE_SI)
+@pytest.mark.parametrize("n", R.COMBINE_N)
+def test_combine_losses(n, si_mode):
+    inp = R.combine_inputs(n, si_mode)
+    assert [s is not None for s in inp["si"]] == [si_mode == "all" or (si_mode == "scale0" and s == 0) for s in range(n)]
+    ref, _ = finite_yardsticks("combine n=%d si=%s" % (n, si_mode), R.combine_ref, inp)
+    # against autograd through the same formula in float64
+    leaves = [t.to(F64).clone().requires_grad_(True) for t in inp["photo"] + inp["smooth"] + [s for s in inp["si"] if s is not None]]
+    photo, smooth, si = leaves[:n], leaves[n:2 * n], iter(leaves[2 * n:])
+    total = sum(photo[s] + float(np.float32(inp["w"])) * smooth[s] / 2 ** s for s in range(n)) + sum(next(si) for s in inp["si"] if s is not None)
+    g = torch.autograd.grad(total / n, leaves, torch.tensor(float(np.float32(inp["cot"])), dtype=F64))
+    assert abs(float((total / n).detach()) - float(ref["total"])) <= 1e-14
+    assert R.rel_err(torch.stack(g[:n]), ref["g_photo"]) < 1e-14 and R.rel_err(torch.stack(g[n:2 * n]), ref["g_smooth"]) < 1e-14
+    for gs in g[2 * n:]:
+        assert abs(float(gs) - float(ref["g_si"][0])) <= 1e-15
+
+
+def test_combine_reference_equals_the_oracle_trainers_totals():
+    """oracle.trainer.compute_losses on one seeded batch: with the smoothness weight 0 its loss/s are the photometric terms alone
+    (x + 0 is x), the smoothness terms are recomputed as it computes them, the SI terms are its own - and the float32 restatement must
+    then give its loss/s and its total bit for bit."""
+    import inputs as gin
+    from oracle import trainer as OT
+    B, H, W = 2, 64, 96
+    inp, rng = gin.batch_inputs(404, B, H, W)
+    disp = gin.disp_pyramid(rng, B, H, W)
+    Ts = {f: OL.transformation_from_parameters(*gin.small_poses(rng, B), invert=(f < 0)) for f in (-1, 1)}
+    noise = [torch.from_numpy(np.random.RandomState(7 + s).randn(B, 2, H, W).astype(np.float32)) for s in range(4)]
+
+    def run(**over):
+        opt = OT.default_opt(height=H, width=W, **over)
+        outputs = dict(disp)
+        for f in (-1, 1):
+            outputs[("cam_T_cam", 0, f)] = Ts[f]
+        OT.generate_images_pred(opt, inp, outputs)
+        return opt, OT.compute_losses(opt, inp, outputs, noise)
+
+    opt, want = run()
+    _, bare = run(disparity_smoothness=0.0)
+    n = len(opt.scales)
+    smooth = []
+    for s in opt.scales:
+        d = disp[("disp", s)]
+        smooth.append(OL.get_smooth_loss(d / (d.mean(2, True).mean(3, True) + 1e-7), inp[("color", 0, s)]))
+    case = {"photo": [bare["loss/%d" % s] for s in opt.scales], "smooth": smooth,
+            "si": [want.get("loss/si_loss%d" % s) for s in opt.scales], "w": opt.disparity_smoothness, "cot": 1.0}
+    assert all(s is not None for s in case["si"]) and n == 4
+    got = R.combine_ref(case, F32)
+    assert got["total"].dtype == F32 and torch.equal(got["total"], want["loss"])
+    for s in opt.scales:
+        assert torch.equal(got["loss"][s], want["loss/%d" % s])
+    case["si"] = [case["si"][0], None, None, None]
+    _, want0 = run(trainer_siloss_all_scale=False)
+    assert "loss/si_loss1" not in want0 and torch.equal(R.combine_ref(case, F32)["total"], want0["loss"])

@@ -1,12 +1,14 @@
 """The memory-bound glue kernels of csrc/geometry.hip and csrc/pool.hip at their launch edges (one element, a ragged last block, exactly
-one block, one element into the next block, past every block cap and into the grid-stride loops), against the float64 references of
-tests/glue_ref.py.
+one block, one element into the next block, past every block cap and into the grid-stride loops), and the stand-alone loss-map kernels
+(bilinear resize and its adjoint, SSIM, the reprojection map, smoothness, the combination of the loss terms) at their tile seams, reflect
+folds, window branches and fractional ratios, against the float64 references of tests/glue_ref.py.
 
 Copies and selections must be exact.  Everything else is held, per output tensor, to ``rel_err <= max(4 x yardstick, 1e-6)``, where the
 yardstick is the float32 CPU oracle's own rel_err against the same float64 reference on the same inputs, computed here on the CPU - and
 never looser than what the older test of the same quantity allows.  Adam is held to the project's 1e-4 of scale.  Outputs written
 through raw pointers sit in sentinel-filled buffers, 64 floats in, and the sentinel must survive on both sides."""
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -507,3 +509,221 @@ def test_flat_adam_against_torch_adam_in_float64(n, tail):
                 c.fixed("%s: %s" % (name, k), got, ref[k], 1e-4)
             for p, o, s in zip(params, flat.offsets, sizes):
                 assert p.data_ptr() == flat.flat_param.data_ptr() + 4 * o and p.numel() == s
+
+
+# ================================================================================================ the stand-alone loss-map kernels
+# fd_bilinear_up_* (geometry.hip), fd_ssim_* and fd_reproj_loss_map (photometric.hip), fd_smooth_* and fd_combine_losses_* (smooth.hip).
+# The caps are what tests/test_gpu_losspath.py allows for the same quantities against the float32 oracle.
+@functools.lru_cache(maxsize=None)
+def _bilinear_refs(case):
+    inp = R.bilinear_inputs(*case)
+    return inp, R.bilinear_ref(inp, F64), R.bilinear_ref(inp, F32)
+
+
+def _case_name(case):
+    return "%dx%dx%d -> %dx%d" % case
+
+
+@pytest.mark.parametrize("case", R.BILINEAR_CASES, ids=_case_name)
+def test_bilinear_forward(L, case):
+    BC, Hin, Win, Hout, Wout = case
+    inp, ref, ora = _bilinear_refs(case)
+    x, y = dev(inp["x"]), Band(BC * Hout * Wout)
+    L.call("fd_bilinear_up_fwd", L.ptr(x), L.ptr(y.t), BC, Hin, Win, Hout, Wout, L.stream())
+    with Checks("bilinear " + _case_name(case)) as c:
+        c.guard("forward", y)
+        c.close("y", y.t.view(ref["y"].shape), ref["y"], ora["y"], cap=cap_of(1e-5, 1e-6, ref["y"]))
+        if (Hin, Win) == (Hout, Wout):
+            c.exact("y is a copy", y.t.view(ref["y"].shape), inp["x"])
+
+
+@pytest.mark.parametrize("case", R.BILINEAR_CASES, ids=_case_name)
+def test_bilinear_adjoint(L, case):
+    """Every input pixel must collect from every output pixel that reads it, at integer and at fractional ratios alike."""
+    BC, Hin, Win, Hout, Wout = case
+    inp, ref, ora = _bilinear_refs(case)
+    cot, gx = dev(inp["cot"]), Band(BC * Hin * Win)
+    L.call("fd_bilinear_up_bwd", L.ptr(cot), L.ptr(gx.t), BC, Hin, Win, Hout, Wout, L.stream())
+    with Checks("bilinear " + _case_name(case)) as c:
+        c.guard("adjoint", gx)
+        c.close("gx", gx.t.view(ref["gx"].shape), ref["gx"], ora["gx"], cap=cap_of(1e-4, 1e-5, ref["gx"]))
+        if (Hin, Win) == (Hout, Wout):
+            c.exact("gx is a copy", gx.t.view(ref["gx"].shape), inp["cot"])
+
+
+def test_bilinear_through_the_wrapper_at_a_fractional_ratio(FD):
+    case = R.BILINEAR_OFFSET_CASE
+    BC, Hin, Win, Hout, Wout = case
+    inp, ref, ora = _bilinear_refs(case)
+    x = dev(inp["x"]).requires_grad_(True)
+    y = FD.bilinear_upsample(x, (Hout, Wout))
+    (gx,) = torch.autograd.grad(y, x, dev(inp["cot"]))
+    with Checks("bilinear wrapper " + _case_name(case)) as c:
+        c.close("y", y, ref["y"], ora["y"], cap=cap_of(1e-5, 1e-6, ref["y"]))
+        c.close("gx", gx, ref["gx"], ora["gx"], cap=cap_of(1e-4, 1e-5, ref["gx"]))
+
+
+def test_bilinear_operands_off_alignment(L):
+    """Every operand one float off 16-byte alignment: bit for bit the aligned call's result."""
+    case = R.BILINEAR_OFFSET_CASE
+    BC, Hin, Win, Hout, Wout = case
+    inp, _, _ = _bilinear_refs(case)
+    x, cot = dev(inp["x"]), dev(inp["cot"])
+    y0, g0 = Band(BC * Hout * Wout), Band(BC * Hin * Win)
+    L.call("fd_bilinear_up_fwd", L.ptr(x), L.ptr(y0.t), BC, Hin, Win, Hout, Wout, L.stream())
+    L.call("fd_bilinear_up_bwd", L.ptr(cot), L.ptr(g0.t), BC, Hin, Win, Hout, Wout, L.stream())
+    y1, g1 = Band(BC * Hout * Wout + 1), Band(BC * Hin * Win + 1)
+    assert y1.t[1:].data_ptr() % 16 == 4 and g1.t[1:].data_ptr() % 16 == 4
+    x1, cot1 = offset_view(x), offset_view(cot)
+    L.call("fd_bilinear_up_fwd", L.ptr(x1), y1.t[1:].data_ptr(), BC, Hin, Win, Hout, Wout, L.stream())
+    L.call("fd_bilinear_up_bwd", L.ptr(cot1), g1.t[1:].data_ptr(), BC, Hin, Win, Hout, Wout, L.stream())
+    with Checks("bilinear off alignment " + _case_name(case)) as c:
+        c.guard("outputs", y0, g0, y1, g1)
+        assert bool((y1.t[:1] == SENTINEL).all()) and bool((g1.t[:1] == SENTINEL).all()), "the float before an output was written"
+        c.exact("y", y1.t[1:], y0.t)
+        c.exact("gx", g1.t[1:], g0.t)
+
+
+def test_bilinear_refuses_what_it_cannot_take(L):
+    gy, gx = torch.rand(2 * 6 * 6, device="cuda"), Band(2 * 6 * 6)
+    with pytest.raises(RuntimeError, match="only upsampling"):
+        L.call("fd_bilinear_up_bwd", L.ptr(gy), L.ptr(gx.t), 2, 6, 6, 5, 6, L.stream())           # Hout < Hin
+    with pytest.raises(RuntimeError, match="only upsampling"):
+        L.call("fd_bilinear_up_bwd", L.ptr(gy), L.ptr(gx.t), 2, 6, 6, 6, 5, L.stream())           # Wout < Win
+    # 65536 planes of one pixel: the plane index is blockIdx.y.  The buffers are real and large enough, the answer must come before any launch
+    n = 65536
+    src, dst = torch.rand(n, device="cuda"), Band(n)
+    for fn in ("fd_bilinear_up_fwd", "fd_bilinear_up_bwd"):
+        with pytest.raises(RuntimeError, match="at most 65535"):
+            L.call(fn, L.ptr(src), L.ptr(dst.t), n, 1, 1, 1, 1, L.stream())
+    torch.cuda.synchronize()
+    assert gx.untouched() and dst.untouched(), "a refused call must launch nothing"
+    L.call("fd_bilinear_up_bwd", L.ptr(src), L.ptr(dst.t), n - 1, 1, 1, 1, 1, L.stream())         # 65535 planes are taken
+    assert dst.intact() and torch.equal(dst.t[:n - 1], src[:n - 1]) and bool((dst.t[n - 1:] == SENTINEL).all())
+
+
+def _ssim_case(L, planes, H, W, kind):
+    inp = R.ssim_inputs(planes, H, W, kind)
+    ref, ora = R.ssim_ref(inp, F64), R.ssim_ref(inp, F32)
+    x, y, cot = dev(inp["x"]), dev(inp["y"]), dev(inp["cot"])
+    n = planes * H * W
+    out = Band(n)
+    L.call("fd_ssim_fwd", L.ptr(x), L.ptr(y), L.ptr(out.t), 1, planes, H, W, L.stream())
+    gcap = lambda k: cap_of(1e-3, 1e-4 * float(ref["gx"].abs().max()), ref[k])
+    with Checks("ssim %s %dx%dx%d" % (kind, planes, H, W)) as c:
+        c.guard("forward", out)
+        c.close("ssim", out.t.view(ref["ssim"].shape), ref["ssim"], ora["ssim"], cap=cap_of(1e-4, 2e-5, ref["ssim"]))
+        both = None
+        for want_x, want_y in ((True, True), (True, False), (False, True)):
+            gx, gy = Band(n), Band(n)
+            L.call("fd_ssim_bwd", L.ptr(x), L.ptr(y), L.ptr(cot), L.ptr(gx.t) if want_x else None, L.ptr(gy.t) if want_y else None,
+                   1, planes, H, W, L.stream())
+            c.guard("backward gx=%d gy=%d" % (want_x, want_y), gx, gy)
+            if both is None:
+                both = (gx, gy)
+                c.close("gx", gx.t.view(ref["gx"].shape), ref["gx"], ora["gx"], cap=gcap("gx"))
+                c.close("gy", gy.t.view(ref["gy"].shape), ref["gy"], ora["gy"], cap=gcap("gy"))
+            elif want_x:
+                assert gy.untouched(), "gy was not asked for"
+                c.exact("gx alone", gx.t, both[0].t)
+            else:
+                assert gx.untouched(), "gx was not asked for"
+                c.exact("gy alone", gy.t, both[1].t)
+
+
+@pytest.mark.parametrize("planes", R.SSIM_PLANES)
+@pytest.mark.parametrize("H,W", R.SSIM_HW)
+def test_ssim(L, H, W, planes):
+    _ssim_case(L, planes, H, W, "smooth")
+
+
+def test_ssim_of_uniform_random_images(L):
+    _ssim_case(L, *R.SSIM_UNIFORM_CASE, "uniform")
+
+
+def test_ssim_of_equal_windows_is_exactly_zero(L):
+    planes, H, W = R.SSIM_EQUAL_CASE
+    inp = R.ssim_inputs(planes, H, W, "equal")
+    ref, ora = R.ssim_ref(inp, F64), R.ssim_ref(inp, F32)
+    x, y, out = dev(inp["x"]), dev(inp["y"]), Band(planes * H * W)
+    L.call("fd_ssim_fwd", L.ptr(x), L.ptr(y), L.ptr(out.t), 1, planes, H, W, L.stream())
+    got = out.t.view(ref["ssim"].shape)
+    with Checks("ssim equal block %dx%dx%d" % (planes, H, W)) as c:
+        c.guard("forward", out)
+        c.close("ssim", got, ref["ssim"], ora["ssim"], cap=cap_of(1e-4, 2e-5, ref["ssim"]))
+        c.exact("windows inside the block", got[..., H - 7:, W - 7:], torch.zeros(1, planes, 7, 7))
+
+
+@pytest.mark.parametrize("B", R.REPROJ_B)
+@pytest.mark.parametrize("H,W", R.SSIM_HW)
+def test_reprojection_loss_map(L, H, W, B):
+    inp = R.reproj_inputs(B, H, W)
+    pred, target = dev(inp["pred"]), dev(inp["target"])
+    P, stride = H * W, H * W + R.REPROJ_GAP
+    with Checks("reproj map %dx%dx%d" % (B, H, W)) as c:
+        for use_ssim in (True, False):
+            ref, ora = R.reproj_ref(inp, F64, use_ssim), R.reproj_ref(inp, F32, use_ssim)
+            out = Band((B - 1) * stride + P)
+            L.call("fd_reproj_loss_map", L.ptr(pred), L.ptr(target), L.ptr(out.t), stride, B, H, W, int(use_ssim), L.stream())
+            c.guard("ssim=%d" % use_ssim, out)
+            for b in range(B - 1):
+                assert bool((out.t[b * stride + P:(b + 1) * stride] == SENTINEL).all()), "the floats between images %d and %d were written" % (b, b + 1)
+            got = torch.stack([out.t[b * stride:b * stride + P] for b in range(B)]).view(B, 1, H, W)
+            c.close("ssim=%d" % use_ssim, got, ref["map"], ora["map"], cap=cap_of(1e-4, 2e-5, ref["map"]))
+
+
+def _smooth_case(L, B, H, W, normalize, wrap=lambda t: t):
+    inp = R.smooth_inputs(B, H, W)
+    ref, ora = R.smooth_ref(inp, F64, normalize), R.smooth_ref(inp, F32, normalize)
+    disp, img = wrap(dev(inp["disp"])), dev(inp["img"])
+    g = torch.tensor([R.SMOOTH_COT], device="cuda")
+    n_ws = L.query("fd_smooth_ws_floats", B, H, W)
+    assert n_ws == 2 * B + 2 * B * (-(-H * W // 1024))
+    out, d_disp = Band(1), Band(B * H * W)
+    ws_f, ws_b = Band(n_ws, fill=float("nan")), Band(n_ws, fill=float("nan"))
+    L.call("fd_smooth_fwd", L.ptr(disp), L.ptr(img), L.ptr(out.t), L.ptr(ws_f.t), B, H, W, int(normalize), L.stream())
+    L.call("fd_smooth_bwd", L.ptr(disp), L.ptr(img), L.ptr(g), L.ptr(d_disp.t), L.ptr(ws_b.t), B, H, W, int(normalize), L.stream())
+    with Checks("smooth %dx%dx%d normalize=%d" % (B, H, W, normalize)) as c:
+        c.guard("outputs and workspaces", out, d_disp, ws_f, ws_b)
+        c.close("loss", out.t.view(()), ref["loss"], ora["loss"], cap=cap_of(1e-5, 1e-8, ref["loss"]))
+        c.close("g_disp", d_disp.t.view(ref["g_disp"].shape), ref["g_disp"], ora["g_disp"], cap=1e-3 + 1e-5)
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+@pytest.mark.parametrize("B", R.SMOOTH_B)
+@pytest.mark.parametrize("H,W", R.SMOOTH_SHAPES)
+def test_smooth_loss(L, H, W, B, normalize):
+    _smooth_case(L, B, H, W, normalize)
+
+
+@pytest.mark.parametrize("B,H,W,normalize", R.SMOOTH_EXTRA)
+def test_smooth_loss_past_its_partial_sum_and_block_caps(L, B, H, W, normalize):
+    _smooth_case(L, B, H, W, normalize)
+
+
+def test_smooth_loss_with_the_disparity_off_alignment(L):
+    """4 bytes off 16-byte alignment k_image_mean must take its scalar loop: the same bound holds."""
+    _smooth_case(L, *R.SMOOTH_OFFSET_CASE, True, wrap=offset_view)
+
+
+@pytest.mark.parametrize("si_mode", R.COMBINE_SI)
+@pytest.mark.parametrize("n", R.COMBINE_N)
+def test_combine_losses(L, n, si_mode):
+    """One thread restating the reference's Python loop: the float32 restatement's values, bit for bit, both ways."""
+    inp = R.combine_inputs(n, si_mode)
+    want = R.combine_ref(inp, F32)
+    terms = [[None if t is None else dev(t).reshape(1) for t in inp[k]] for k in ("photo", "smooth", "si")]
+    P = ctypes.c_void_p * n
+    arr = [P(*[L.ptr(t) for t in group]) for group in terms]
+    out, grads = Band(n + 1), Band(3 * n)
+    g = torch.tensor([inp["cot"]], device="cuda")
+    L.call("fd_combine_losses_fwd", ctypes.addressof(arr[0]), ctypes.addressof(arr[1]), ctypes.addressof(arr[2]), n, inp["w"], L.ptr(out.t), L.stream())
+    L.call("fd_combine_losses_bwd", L.ptr(g), n, inp["w"], L.ptr(grads.t), L.stream())
+    with Checks("combine n=%d si=%s" % (n, si_mode)) as c:
+        c.guard("outputs", out, grads)
+        c.exact("loss/s", out.t[:n], want["loss"])
+        c.exact("total", out.t[n], want["total"])
+        c.exact("d total / d photo", grads.t[:n], want["g_photo"])
+        c.exact("d total / d smooth", grads.t[n:2 * n], want["g_smooth"])
+        c.exact("d total / d si", grads.t[2 * n:], want["g_si"])
+        c.close("total against float64", out.t[n], R.combine_ref(inp, F64)["total"], want["total"])
