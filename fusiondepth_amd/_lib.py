@@ -155,6 +155,26 @@ class PngEncBlock(ctypes.Structure):
 assert ctypes.sizeof(PngEncDesc) == 80 and ctypes.sizeof(PngEncSizes) == 80 and ctypes.sizeof(PngEncBlock) == 1408
 
 
+class JpegEncDesc(ctypes.Structure):
+    """Mirror of ``fd_jpeg_enc_desc``."""
+    _fields_ = [("src", ctypes.c_void_p)] + [(n, _L) for n in ("first_block", "blocks", "raw_off", "raw_cap", "first_tile", "out_cap")] + \
+               [(n, _I) for n in ("width", "height", "hs", "vs", "mcus_w", "mcus_h")] + [("reserved", _I * 4)]
+
+
+class JpegEncSizes(ctypes.Structure):
+    """Mirror of ``fd_jpeg_enc_sizes``."""
+    _fields_ = [(n, _L) for n in ("blocks", "tiles", "tab_off", "coef_off", "bits_off", "pos_off", "tile_off", "tilepos_off", "total_off",
+                                  "result_off", "result_bytes", "raw_off", "raw_bytes", "work_bytes", "out_bytes", "reserved")]
+
+
+class JpegEncResult(ctypes.Structure):
+    """Mirror of ``fd_jpeg_enc_result``."""
+    _fields_ = [(n, _L) for n in ("out_off", "out_bytes", "stream_bits", "stuffed")]
+
+
+assert ctypes.sizeof(JpegEncDesc) == 96 and ctypes.sizeof(JpegEncSizes) == 128 and ctypes.sizeof(JpegEncResult) == 32
+
+
 class LogCfg(ctypes.Structure):
     """Mirror of ``fd_log_cfg``."""
     _fields_ = [("Hs", _I), ("Ws", _I), ("n_rows", _I), ("n_disp", _I), ("row_y", _I * 8), ("row_h", _I * 8), ("row_first", _I * 8),
@@ -312,6 +332,10 @@ SIGNATURES = {
     "fd_png_enc_plan": ("pi" "pp" "p", "i"),
     "fd_png_enc_emit": ("pl" "pi" "p" "pl" "p", "i"),
     "fd_png_enc_finish": ("pl" "p", "i"),
+    "fd_jpeg_enc_quant_tables": ("ip", "i"),
+    "fd_jpeg_enc_header": ("iiiii" "pl", "i"),
+    "fd_jpeg_enc_layout": ("pip", "i"),
+    "fd_jpeg_enc_encode": ("pl" "pi" "i" "pl" "p", "i"),
 }
 
 _lock = threading.Lock()

@@ -1033,3 +1033,158 @@ def encode_png_batch(images, pool=None):
     "raw_bytes": the scanline bytes they hold}``.  Three launches, three small uploads and two downloads whatever the number of images;
     anything else is a ValueError before the GPU is touched."""
     return PngEncodeJob(images, pool).finish()
+
+
+# ------------------------------------------------------------------------------------------------ JPEG outputs -----
+# The encoder of include/fdhip.h ("JPEG outputs"): pixels to stuffed entropy-coded bytes in csrc/jpeg_enc.hip, the tables, the layout
+# and the header bytes on the host behind the C ABI (csrc/jpeg_enc_host.h).  tests/jpeg_enc_ref.py restates the stream.
+JPEG_ENC_HEADER_BYTES = 623  # FD_JPEG_ENC_HEADER_BYTES
+JPEG_SAMPLINGS = {"1x1": (1, 1), "2x1": (2, 1), "2x2": (2, 2)}
+JPEG_SUBSAMPLING = {"1x1": 0, "2x1": 1, "2x2": 2}                # Pillow's name for the same three
+JPEG_ENCODERS = ("pil", "device")
+
+
+def jpeg_enc_quant_tables(quality):
+    """``fd_jpeg_enc_quant_tables`` -> uint16 [2, 64] numpy array in zigzag order.  Host only."""
+    import numpy as np
+    zz = np.zeros((2, 64), np.uint16)
+    if _lib.load().fd_jpeg_enc_quant_tables(int(quality), zz.ctypes.data) != 0:
+        raise ValueError(_lib.last_error())
+    return zz
+
+
+def jpeg_enc_header(width, height, sampling, quality, dst=None):
+    """``fd_jpeg_enc_header`` -> the header bytes of a file (or written at the start of ``dst``, a contiguous uint8 numpy array).  Host only."""
+    import numpy as np
+    hs, vs = JPEG_SAMPLINGS[sampling] if isinstance(sampling, str) else sampling
+    buf = np.zeros((JPEG_ENC_HEADER_BYTES,), np.uint8) if dst is None else dst
+    if _lib.load().fd_jpeg_enc_header(int(width), int(height), int(hs), int(vs), int(quality), buf.ctypes.data, buf.size) != 0:
+        raise ValueError(_lib.last_error())
+    return buf.tobytes() if dst is None else None
+
+
+def jpeg_enc_layout(shapes):
+    """``fd_jpeg_enc_layout`` of [(width, height, hs, vs)] -> (a ctypes array of ``_lib.JpegEncDesc``, ``_lib.JpegEncSizes``).  Host only;
+    a shape the encoder does not cover is a ValueError."""
+    table = (_lib.JpegEncDesc * max(len(shapes), 1))()
+    for d, (w, h, hs, vs) in zip(table, shapes):
+        d.width, d.height, d.hs, d.vs = min(int(w), 1 << 30), min(int(h), 1 << 30), int(hs), int(vs)
+    sizes = _lib.JpegEncSizes()
+    if _lib.load().fd_jpeg_enc_layout(table, len(shapes), ctypes.byref(sizes)) != 0:
+        raise ValueError(_lib.last_error())
+    return table, sizes
+
+
+def _pil_jpeg(a, quality, sampling=None):
+    """The file Pillow writes for a uint8 [H, W] (mode L) or [H, W, 3] array."""
+    import io
+    from PIL import Image
+    f = io.BytesIO()
+    if a.ndim == 2:
+        Image.fromarray(a).save(f, "JPEG", quality=quality)
+    else:
+        Image.fromarray(a).save(f, "JPEG", quality=quality, subsampling=JPEG_SUBSAMPLING[sampling])
+    return f.getvalue()
+
+
+def check_jpeg_params(quality, sampling, n, who="encode_jpeg_batch"):
+    """-> the per-image list of sampling names; ValueError for a bad ``quality`` or ``sampling``."""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("%s: quality must be an int in 1 .. 100, got %r" % (who, quality))
+    names = [sampling] * n if isinstance(sampling, str) else (list(sampling) if isinstance(sampling, (list, tuple)) else [None])
+    if len(names) != n or any(not isinstance(s, str) or s not in JPEG_SAMPLINGS for s in names):
+        raise ValueError("%s: sampling must be '1x1', '2x1' or '2x2' (or one of them per image), got %r" % (who, sampling))
+    return names
+
+
+def encode_jpeg_batch(images, quality=92, sampling="2x2", pool=None):
+    """The JPEG files Pillow writes for ``Image.fromarray(a).save(f, "JPEG", quality=quality, subsampling=...)``, byte for byte, of
+    ``images`` - device tensors, or host tensors / numpy arrays (uploaded in one copy), uint8 [H, W, 3] of any mix of sizes.
+    ``sampling``: '1x1', '2x1' or '2x2' (Pillow's subsampling 0, 1, 2), or a list with one per image.  Returns ``(files, stats)``: one
+    ``memoryview`` per image into ONE pinned buffer, complete files ready to be written, and ``{"device": n, "fallback": n, "bytes":
+    their total size}``.  A uint8 [H, W] image is outside the covered set: Pillow encodes it (mode L) into the same buffer and it is
+    counted as ``fallback``.  One library call of seven launches whatever the number of images; any other dtype or rank, a zero or
+    over-large side, a bad ``quality`` or ``sampling`` is a ValueError before the GPU is touched."""
+    import numpy as np
+    images = list(images)
+    if not images:
+        raise ValueError("encode_jpeg_batch: no images")
+    names = check_jpeg_params(quality, sampling, len(images))
+    colour, grey = [], []
+    for i, x in enumerate(images):
+        if not isinstance(x, (torch.Tensor, np.ndarray)):
+            raise ValueError("encode_jpeg_batch: image %d is a %s, not a tensor or an array" % (i, type(x).__name__))
+        shape = tuple(x.shape)
+        if x.dtype not in (torch.uint8, np.dtype(np.uint8)) or not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+            raise ValueError("encode_jpeg_batch: image %d is %s %s, neither uint8 [H,W,3] nor uint8 [H,W]" % (i, x.dtype, list(shape)))
+        if not (1 <= shape[0] <= 65535 and 1 <= shape[1] <= 65535):
+            raise ValueError("encode_jpeg_batch: image %d is %d x %d, a side outside 1 .. 65535" % (i, shape[0], shape[1]))
+        (colour if len(shape) == 3 else grey).append(i)
+    on = [(i, images[i].device) for i in colour if isinstance(images[i], torch.Tensor) and images[i].is_cuda]
+    for i, dv in on:                                             # one device per batch: the first device image's
+        if dv != on[0][1]:
+            raise ValueError("encode_jpeg_batch: image %d lives on %s, the batch on %s" % (i, dv, on[0][1]))
+    pool = pool if pool is not None else jpeg_pool()
+    grey_jobs = {i: pool.submit(_pil_jpeg, images[i].cpu().numpy() if isinstance(images[i], torch.Tensor) else np.ascontiguousarray(images[i]),
+                                quality) for i in grey}
+    results, out, device = None, None, None
+    if colour:
+        table, sizes = jpeg_enc_layout([(images[i].shape[1], images[i].shape[0]) + JPEG_SAMPLINGS[names[i]] for i in colour])
+        dev = [images[i].device for i in colour if isinstance(images[i], torch.Tensor) and images[i].is_cuda]
+        device = dev[0] if dev else torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(device):
+            keep, src = [], {}
+            host = [(i, images[i].numpy() if isinstance(images[i], torch.Tensor) else images[i]) for i in colour
+                    if not (isinstance(images[i], torch.Tensor) and images[i].is_cuda)]
+            if host:                                             # the host images: one pinned buffer, one upload
+                at, slots = 0, []
+                for i, a in host:
+                    slots.append(at)
+                    at += _round16(a.nbytes)
+                pinned = torch.empty((at,), dtype=torch.uint8, pin_memory=True)
+                flat = pinned.numpy()
+                for (i, a), s in zip(host, slots):
+                    flat[s:s + a.nbytes] = np.ascontiguousarray(a).reshape(-1)
+                up = torch.empty((at,), dtype=torch.uint8, device=device)
+                up.copy_(pinned, non_blocking=True)
+                keep += [pinned, up]
+                for (i, _), s in zip(host, slots):
+                    src[i] = up.data_ptr() + s
+            for i in colour:
+                if i not in src:
+                    x = images[i].contiguous()
+                    keep.append(x)
+                    src[i] = x.data_ptr()
+            for d, i in zip(table, colour):
+                d.src = src[i]
+            n = len(colour)
+            work = torch.empty((sizes.work_bytes,), dtype=torch.uint8, device=device)
+            out = torch.empty((sizes.out_bytes,), dtype=torch.uint8, device=device)
+            call("fd_jpeg_enc_encode", work.data_ptr(), sizes.work_bytes, ctypes.addressof(table), n, quality, out.data_ptr(), sizes.out_bytes,
+                 stream())
+            rows = torch.empty((sizes.result_bytes,), dtype=torch.uint8, pin_memory=True)
+            rows.copy_(work[sizes.result_off:sizes.result_off + sizes.result_bytes], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            results = (_lib.JpegEncResult * n).from_buffer_copy(rows.numpy().tobytes())
+    grey_files = {i: f.result() for i, f in grey_jobs.items()}
+    device_bytes = sum(r.out_bytes for r in results) if results is not None else 0
+    total = device_bytes + sum(len(f) for f in grey_files.values())
+    pinned = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+    flat = pinned.numpy()
+    if colour:
+        if results[len(colour) - 1].out_off + results[len(colour) - 1].out_bytes != device_bytes or device_bytes > sizes.out_bytes:
+            raise RuntimeError("encode_jpeg_batch: the files' sizes do not add up")
+        with torch.cuda.device(device):
+            pinned[:device_bytes].copy_(out[:device_bytes], non_blocking=True)     # exactly the sum of the file sizes
+            torch.cuda.current_stream().synchronize()
+    view, files, at = memoryview(flat), [None] * len(images), device_bytes
+    for k, i in enumerate(colour):
+        r, d = results[k], table[k]
+        jpeg_enc_header(d.width, d.height, (d.hs, d.vs), quality, flat[r.out_off:r.out_off + JPEG_ENC_HEADER_BYTES])
+        files[i] = view[r.out_off:r.out_off + r.out_bytes]
+    for i in grey:
+        data = grey_files[i]
+        flat[at:at + len(data)] = np.frombuffer(data, np.uint8)
+        files[i] = view[at:at + len(data)]
+        at += len(data)
+    return files, {"device": len(colour), "fallback": len(grey), "bytes": int(total)}

@@ -56,7 +56,9 @@ extern "C" {
  *    Likewise the pseudo-LiDAR point clouds (fd_points_export_ws_bytes, fd_points_export, struct fd_points_calib; it reuses
  *    struct fd_export_desc).
  *    Likewise the PNG encoder (fd_png_enc_layout, fd_png_enc_filter, fd_png_enc_plan, fd_png_enc_emit, fd_png_enc_finish,
- *    fd_png_enc_block_rows, struct fd_png_enc_desc / _sizes / _block). */
+ *    fd_png_enc_block_rows, struct fd_png_enc_desc / _sizes / _block).
+ *    Likewise the JPEG encoder (fd_jpeg_enc_quant_tables, fd_jpeg_enc_header, fd_jpeg_enc_layout, fd_jpeg_enc_encode,
+ *    struct fd_jpeg_enc_desc / _sizes / _result). */
 #define FD_ABI_VERSION 8
 
 int fd_abi_version(void);
@@ -1361,6 +1363,94 @@ int fd_png_enc_plan(fd_png_enc_desc* desc, int N, const unsigned* stats, fd_png_
 int fd_png_enc_emit(void* work, long work_bytes, const fd_png_enc_desc* desc, int N, const fd_png_enc_block* blocks,
                     unsigned char* out, long out_bytes, void* stream);
 int fd_png_enc_finish(unsigned char* files, long nbytes, const fd_png_enc_desc* desc);
+
+/* ------------------------------------------------------------------------------ JPEG outputs --
+ * The encoder: uint8 [H][W][3] pixels in, the bytes Pillow (libjpeg's defaults: baseline, standard tables, optimize off, no restart
+ * markers, no smoothing) writes for Image.fromarray(rgb).save(f, "JPEG", quality=q, subsampling=s) out.  Everything from the pixels to
+ * the stuffed entropy-coded bytes and FF D9 is device work; the host lays out the batch, builds the tables and writes the 623 header
+ * bytes in front of each stream (csrc/jpeg_enc_host.h: plain C++, no GPU call, usable without a GPU).  tests/jpeg_enc_ref.py restates
+ * the rules in numpy and is held to Pillow byte for byte; the files are held to both.
+ *
+ * Covered: 1 <= W, H <= 65535; quality 1 .. 100 (one per batch); sampling 1x1, 2x1, 2x2 (luma factors hs x vs; Pillow's subsampling 0, 1,
+ * 2) per image; images of different sizes and samplings in one batch of 1 <= N <= 65535 with at most 2^31 - 1 blocks in all.
+ *
+ * THE RULES.
+ *   1 Colour.   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;
+ *               Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *   2 Edges.    Luma: the last column and row replicated to whole blocks, ceil(W / 8) x ceil(H / 8) of them.  Chroma with hs = 2, in
+ *               this order: the last column replicated at full resolution to 16 ceil(W / 16); for vs = 2 the last row once when H is
+ *               odd; the downsample - 2x1: (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... along the output row, 2x2:
+ *               (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ...; then the last DOWNSAMPLED row replicated to whole blocks.
+ *   3 Transform. Samples minus 128; libjpeg's accurate integer forward DCT (13 constant bits, 2 pass-1 bits, rows then columns, its
+ *               rounding shifts; constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172); output times 8; int32.
+ *   4 Quantisation.  Annex K tables; s = 5000 / q for q < 50, else 200 - 2 q; t = clip((base s + 50) / 100, 1, 255);
+ *               coefficient = sign(v) ((|v| + 4 t) / (8 t)).
+ *   5 Dummy blocks (luma blocks of the MCU grid beyond the component's own blocks; hs = 2 only): all AC terms zero; in a real block
+ *               row the DC of the block to the left; in a dummy row the DC of the LAST block of the row above within the same MCU,
+ *               which may itself be a right-edge dummy.
+ *   6 Scan.     One interleaved scan, MCUs in raster order, inside an MCU the luma blocks row by row, then Cb, then Cr; a DC predictor
+ *               per component; Annex K Huffman tables; a negative value travels as v - 1 in its low bits; F0 for each run of 16 zeros,
+ *               00 ends a block unless its last coefficient is non-zero; bits most significant first; 00 after every FF data byte;
+ *               the last byte filled with one-bits (and stuffed like any other), then FF D9.
+ *   7 Headers.  SOI; APP0 JFIF 1.01, units 0, density 1x1, no thumbnail; two DQT of 67 bytes; SOF0; DHT DC0, AC0, DC1, AC1; SOS:
+ *               FD_JPEG_ENC_HEADER_BYTES bytes whatever the image.
+ *
+ * THE CALLS, in order, for one batch:
+ *   fd_jpeg_enc_layout  host.  In: width, height, hs, vs of every descriptor.  Out: their MCU grid, first block, first tile and the
+ *                       worst-case sizes - a block takes at most FD_JPEG_ENC_BLOCK_BYTES bytes before stuffing (22 bits of DC and 63
+ *                       times 26 bits of AC), a file at most out_cap = header + twice that + 2 - and *sizes.  The caller allocates
+ *                       `work` (sizes.work_bytes, 16-byte aligned) and `out` (sizes.out_bytes).
+ *   fd_jpeg_enc_encode  checks the table against the layout, copies it and the tables (quantisation, Huffman) to work, clears the
+ *                       unstuffed streams, and launches, whatever N and the sizes are:
+ *     A k_jpeg_enc_blocks  rules 1 to 5.  A wave takes 8 blocks, a lane one row of a block: it builds its 8 samples from the pixels
+ *                       (colour, edge replication and the chroma downsample on the load), does the row pass in registers, passes the
+ *                       block through LDS, does the column pass and the quantisation of one column, and the wave stores the int16
+ *                       coefficients in zigzag order, 16 bytes a lane, in scan order, dummy blocks included (a dummy block runs its
+ *                       source block's arithmetic and keeps the DC).
+ *     B k_jpeg_enc_bits    a lane per block: the bits of its tokens, the DC against its predecessor of the same component.
+ *     C k_jpeg_enc_scan    a workgroup per image: the exclusive scan of the bit counts, 64-bit, and the stream's length.
+ *     D k_jpeg_enc_emit    a lane per block packs its tokens, 32 bits at a time, with integer atomic ORs on byte-swapped 32-bit words
+ *                       of the cleared stream, bounds-checked against the image's room.
+ *     E k_jpeg_enc_ffcount, k_jpeg_enc_scan again, k_jpeg_enc_stuff: the FF bytes of every FD_JPEG_ENC_TILE_BYTES tile of the filled
+ *                       stream, their exclusive scan per image, and the stuffed bytes, FF D9 and one fd_jpeg_enc_result per image;
+ *                       the files follow each other from byte 0 of out, each with FD_JPEG_ENC_HEADER_BYTES unwritten bytes in front.
+ *                       SEVEN launches, one clear and two small uploads per batch.  Integer arithmetic and integer atomics only: two
+ *                       calls give the same bytes.
+ *   (download)          work[result_off ..): N fd_jpeg_enc_result; then out[0 .. sum of out_bytes) into pinned memory.
+ *   fd_jpeg_enc_header  host, per file: the header bytes at the file's start. */
+#define FD_JPEG_ENC_HEADER_BYTES 623
+#define FD_JPEG_ENC_BLOCK_BYTES 208
+#define FD_JPEG_ENC_TILE_BYTES 4096
+typedef struct fd_jpeg_enc_desc {
+    const void* src;                 /* DEVICE pixels, uint8 [H][W][3], contiguous */
+    long first_block, blocks;        /* layout: the batch-wide index of the image's first block in scan order; its block count */
+    long raw_off, raw_cap;           /* layout: the image's unstuffed stream inside work; its room (whole tiles) */
+    long first_tile;                 /* layout: the batch-wide index of the image's first tile */
+    long out_cap;                    /* layout: the worst-case size of the file */
+    int width, height;
+    int hs, vs;                      /* luma sampling factors: 1x1, 2x1 or 2x2 */
+    int mcus_w, mcus_h;              /* layout */
+    int reserved[4];
+} fd_jpeg_enc_desc;
+typedef struct fd_jpeg_enc_sizes {
+    long blocks, tiles;              /* of the whole batch */
+    long tab_off, coef_off, bits_off, pos_off, tile_off, tilepos_off, total_off;
+    long result_off, result_bytes;   /* the download */
+    long raw_off, raw_bytes;         /* the clear */
+    long work_bytes;
+    long out_bytes;                  /* the sum of out_cap, rounded up to 16 */
+    long reserved;
+} fd_jpeg_enc_sizes;
+typedef struct fd_jpeg_enc_result {
+    long out_off, out_bytes;         /* the file inside out, header included */
+    long stream_bits;                /* before the fill and the stuffing */
+    long stuffed;                    /* the 00 bytes added */
+} fd_jpeg_enc_result;
+int fd_jpeg_enc_quant_tables(int quality, unsigned short* zigzag /* [2][64]: luminance, chrominance, as a DQT segment holds them */);
+int fd_jpeg_enc_header(int width, int height, int hs, int vs, int quality, unsigned char* dst, long dst_bytes);
+int fd_jpeg_enc_layout(fd_jpeg_enc_desc* desc, int N, fd_jpeg_enc_sizes* sizes);
+int fd_jpeg_enc_encode(void* work, long work_bytes, const fd_jpeg_enc_desc* desc, int N, int quality, unsigned char* out, long out_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,9 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
                           and as a share of the batch; ``fd_png_inflate`` against ``zlib.decompress`` and Pillow's whole decode on one
                           thread; the completion loader's 16 depth planes by either route; ``KITTIRAWBatches`` items/s and Trainer
                           images/s fed by either ``png_decoder=``.
+ 14. ``jpeg_enc``         ``--step jpeg_enc`` (a run of its own, ``| tee -a profiles/jpeg_encode_time.log``): 36 frames of step 12's content
+                          through ``data_ops.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, ``fd_jpeg_enc_encode`` alone against
+                          its traffic bound, and ``convert_frames`` end to end against ``--encoder pil --png_decoder pil``.
 
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
 """
@@ -1352,12 +1355,114 @@ def drive(args):
     sys.exit(subprocess.call(["bash", "-c", cmd], cwd=ROOT))
 
 
+# ---------------------------------------------------------------------------------------------------- 14. JPEG outputs on the device
+def step_jpeg_enc(args):
+    """[14] ``data_ops.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, the library call alone against its traffic bound, and
+    ``convert_frames`` end to end on a synthetic PNG tree against ``--encoder pil --png_decoder pil``.  The routes alternate inside
+    this one run, after a byte comparison; run it twice for the run-to-run spread."""
+    import concurrent.futures
+    import ctypes
+    import io
+    import torch
+    from PIL import Image
+    sys.path.insert(0, ROOT)
+    from fusiondepth_amd import _lib, convert_frames, data_ops
+    N, Q, S = 36, 92, "2x2"
+    note = say
+
+    frames = [frame(1000 + i) for i in range(N)]
+    dev = [torch.from_numpy(f).cuda() for f in frames]
+    pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
+
+    def route_device():
+        return data_ops.encode_jpeg_batch(dev, quality=Q, sampling=S, pool=pool)[0]
+
+    def pil_one(a):
+        f = io.BytesIO()
+        Image.fromarray(a).save(f, "JPEG", quality=Q, subsampling=2)
+        return f.getvalue()
+
+    def route_pil():
+        host = [d.cpu().numpy() for d in dev]                    # the frames are on the device in both routes: Pillow's pays the download
+        return list(pool.map(pil_one, host))
+
+    got, want = route_device(), route_pil()
+    assert [bytes(g) for g in got] == want, "the routes disagree"
+    total = sum(len(w) for w in want)
+    note("[14] JPEG outputs: %d frames of %dx%d, quality %d, %s, textured synthetic content (step 12's); %.0f KB per file; the two routes' "
+         "files are equal byte for byte" % (N, W0, H0, Q, S, total / N / 1e3))
+    iters = max(3, min(args.iters, 15))
+    t = {"device": [], "pil": []}
+    for _ in range(iters):
+        for name, fn in (("device", route_device), ("pil", route_pil)):
+            t0 = time.perf_counter()
+            fn()
+            t[name].append(1e3 * (time.perf_counter() - t0))
+    for name, label in (("device", "encode_jpeg_batch (one library call + two downloads + the headers)"),
+                        ("pil", "download + Pillow's save on %d threads" % WORKERS)):
+        med = float(np.median(t[name]))
+        note("    %-72s %8.1f frames/s, ms per batch of %d: %s  (%d alternating runs)" % (label + ":", 1e3 * N / med, N, _spread(t[name]), iters))
+
+    # the library call alone: the two small uploads, the clear and the seven launches
+    table, sizes = data_ops.jpeg_enc_layout([(W0, H0, 2, 2)] * N)
+    for d, x in zip(table, dev):
+        d.src = x.data_ptr()
+    work = torch.empty((sizes.work_bytes,), dtype=torch.uint8, device="cuda")
+    out = torch.empty((sizes.out_bytes,), dtype=torch.uint8, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = []
+    for k in range(iters + 2):
+        ev[0].record()
+        data_ops.call("fd_jpeg_enc_encode", work.data_ptr(), sizes.work_bytes, ctypes.addressof(table), N, Q, out.data_ptr(), sizes.out_bytes,
+                      _lib.stream())
+        ev[1].record()
+        torch.cuda.synchronize()
+        if k >= 2:
+            ms.append(ev[0].elapsed_time(ev[1]))
+    blocks = sizes.blocks
+    traffic = N * 3 * H0 * W0 + 3 * 128 * blocks + 12 * blocks + sizes.raw_bytes + 3 * total
+    note("    fd_jpeg_enc_encode alone (clear of %.1f MB of worst-case stream room + seven launches): ms per batch %s; its traffic (pixels once, "
+         "coefficients written once and read twice, the clear, the stream written, read and written stuffed) = %.1f MB = %.3f ms at %.1f "
+         "TB/s -> %.1fx the bound" % (sizes.raw_bytes / 1e6, _spread(ms), traffic / 1e6, 1e3 * traffic / HBM_BPS, HBM_BPS / 1e12,
+                                       float(np.median(ms)) / (1e3 * traffic / HBM_BPS)))
+
+    # convert_frames end to end
+    n_tree = 72
+    with tempfile.TemporaryDirectory() as root:
+        src = os.path.join(root, "png", "2011_09_26", "image_02", "data")
+        os.makedirs(src)
+        for i in range(n_tree):
+            Image.fromarray(frame(2000 + i)).save(os.path.join(src, "%010d.png" % i))
+        runs = {"device": [], "pil": []}
+        files = {}
+        for rep in range(-1, 3):                                 # rep -1: one conversion per route that is not timed (library load, first allocations)
+            for enc in ("device", "pil"):
+                dst = os.path.join(root, "out_%s_%d" % (enc, rep))
+                t0 = time.perf_counter()
+                res = convert_frames.convert(os.path.join(root, "png"), dst, encoder=enc, png_decoder=enc, workers=WORKERS)
+                if rep >= 0:
+                    runs[enc].append(n_tree / (time.perf_counter() - t0))
+                assert res["converted"] == n_tree and (res["device"] == n_tree) == (enc == "device"), res
+                files[enc] = [open(os.path.join(dst, "2011_09_26", "image_02", "data", "%010d.jpg" % i), "rb").read() for i in range(n_tree)]
+            assert files["device"] == files["pil"], "convert_frames: the routes disagree"
+        for enc in ("device", "pil"):
+            note("    convert_frames --encoder %s --png_decoder %s on %d PNG frames (temporary directory): files/s %s  (3 alternating runs after one "
+                 "untimed conversion per route)" % (enc, enc, n_tree, _spread(runs[enc])))
+        gain = float(np.median(runs["device"])) / float(np.median(runs["pil"]))
+        diff = float(np.median(runs["device"])) - float(np.median(runs["pil"]))
+        spread = max(max(v) - min(v) for v in runs.values())
+        note("    convert_frames: device over pil = %.2fx by the medians; gain %.1f files/s, larger spread %.1f files/s -> the gain %s the spread"
+             % (gain, diff, spread, "EXCEEDS" if diff > spread else "does NOT exceed"))
+    note("    NOT measured: a real KITTI tree (real frames compress differently from synthetic content), file-system write time on a real "
+         "disk, ImageMagick itself")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", default="all", choices=["all", "colour", "trace_report", "pil", "pil_worker", "builder", "trainer", "raw", "sparsify",
                                                       "raw_builder", "raw_trainer", "offline", "offline_worker", "refiner", "inf_gdc_key", "gdc_trace_report",
                                                       "refiner_trainer", "completion", "completion_keys", "completion_trace_report", "jpeg", "jpeg_kernels",
-                                                      "jpeg_trace_report", "png"])
+                                                      "jpeg_trace_report", "png", "jpeg_enc"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default="")
     ap.add_argument("--split_file", default="")
@@ -1378,7 +1483,7 @@ def main():
      "raw_trainer": step_raw_trainer, "offline": step_offline, "offline_worker": step_offline_worker, "all": drive, "colour": step_colour,
      "trace_report": step_trace_report, "pil": step_pil, "pil_worker": step_pil_worker, "builder": step_builder,
      "trainer": step_trainer, "jpeg": step_jpeg, "jpeg_kernels": step_jpeg_kernels,
-     "jpeg_trace_report": step_jpeg_trace_report, "png": step_png}[args.step](args)
+     "jpeg_trace_report": step_jpeg_trace_report, "png": step_png, "jpeg_enc": step_jpeg_enc}[args.step](args)
 
 
 if __name__ == "__main__":
