@@ -1,7 +1,8 @@
 """The reference's ``python completor.py`` as a command: options -> loaders -> ``Completor.train`` with in-training validation.
 
     python -m fusiondepth_amd.complete [reference flags] [--seed N] [--val_limit N] [--no_val] [--val_route fused|per_batch]
-                                       [--image_decoder pil|device] [--png_decoder pil|device]
+                                       [--image_decoder pil|device] [--png_decoder pil|device] [--resume PATH|latest]
+                                       [--pretrained_path FILE|DIR]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.complete ...       # data parallel, one rank per GPU
 
   * ``build_loaders(opt, rank, world_size, ...)``  completor.py:132-152: both loaders are ``KITTICompletionBatches`` over
@@ -28,6 +29,8 @@ Deviations from the reference, on purpose
     default, both are the reference's mean over batches; at a larger batch the fused route still averages per image.
   * ``--dataset`` is not read: the completion tree has one layout.  ``--completion_amp`` is not covered.
   * no tensorboard / wandb: the scalars go to ``<log_path>/{train,val}/scalars.jsonl`` (``Trainer.log``).
+  * ``--resume PATH|latest`` continues a run from an epoch checkpoint and ``--pretrained_path`` names torchvision's ImageNet file for
+    ``--weights_init pretrained``, both as in ``train.py``; ``--shard_val`` is not offered here (the scorer's chunks are rank 0's).
 """
 import os
 import sys
@@ -37,10 +40,12 @@ import torch
 from . import dp
 from .evaluate_completion import canvas_size
 from .evaluate_depth import split_off_flags
-from .train import decode_workers, take_image_decoder, write_summary
+from . import resume as run_state
+from .train import decode_workers, start_epoch_of, take_image_decoder, write_summary
 
 DEFAULT_VAL_ROUTE = "fused"            # decided by profiles/completion_val_time.log
-EXTRA_VALUED = {"seed": "0", "val_limit": None, "val_route": DEFAULT_VAL_ROUTE, "image_decoder": None, "png_decoder": None}
+EXTRA_VALUED = {"seed": "0", "val_limit": None, "val_route": DEFAULT_VAL_ROUTE, "image_decoder": None, "png_decoder": None,
+                "resume": None, "pretrained_path": None}
 EXTRA_SWITCHES = ("no_val",)
 
 
@@ -53,6 +58,8 @@ def split_off_extra(argv):
     crop, pad and mirror run on the host threads, stay with Pillow)."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     take_image_decoder(found)
+    run_state.take_flags(found)
+    run_state.check_flags(found, rest)
     found["seed"] = int(found["seed"])
     if found["val_limit"] is not None:
         found["val_limit"] = int(found["val_limit"])
@@ -101,6 +108,8 @@ def main(argv=None):
         raise NotImplementedError("fusiondepth_amd.complete: --completion_amp is not covered")
     if extra["load_weights_given"]:
         opt.train_load_weights_folder = opt.load_weights_folder
+    if extra.get("pretrained_path"):
+        opt.pretrained_path = extra["pretrained_path"]
     torch.manual_seed(extra["seed"])
     completor = Completor(opt, rank=rank, world_size=world)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
@@ -111,7 +120,7 @@ def main(argv=None):
     if val_loader is not None and extra["val_route"] == "fused":
         completor.val_scorer = val_scorer_for(completor.opt, val_loader, completor.device)
     try:
-        completor.train(train_loader, val_loader)
+        completor.train(train_loader, val_loader, start_epoch=start_epoch_of(completor, extra, train_loader))
         write_summary(completor, train_loader, rank)
     finally:
         train_loader.close()

@@ -186,6 +186,7 @@ class KITTIRAWBatches:
             line_spec = data_ops.SPARSIFY_LINE_SPEC.get(nbeams)
         self.line_spec = None if line_spec is None else [int(r) for r in line_spec]
         self._epoch = 0
+        self._open = 0                                           # iterations begun and not yet finished or dropped
         self._pool = None
         self._stream = None
         self._K = {}
@@ -522,11 +523,28 @@ class KITTIRAWBatches:
     def _tensors(batch):
         return [v for v in batch.values() if torch.is_tensor(v)]
 
+    def set_epoch(self, n):
+        """The next ``__iter__`` serves ``epoch_order(n)`` with the draws of epoch ``n`` (a continued run, ``Trainer.resume``).
+        Refused while an iteration is open: its batches are being built ahead from the epoch it started with."""
+        if self._open:
+            raise RuntimeError("%s.set_epoch: an iteration is open; finish or drop it first" % type(self).__name__)
+        if int(n) < 0:
+            raise ValueError("%s.set_epoch: the epoch must not be negative, got %r" % (type(self).__name__, n))
+        self._epoch = int(n)
+
     def __iter__(self):
         epoch = self._epoch
         self._epoch += 1
         order = self.epoch_order(epoch)
         self.served.append((epoch, order))
+        self._open += 1
+        try:
+            yield from self._batches(epoch, order)
+        finally:
+            self._open -= 1
+
+    def _batches(self, epoch, order):
+        """The batches of one epoch, in ``order``."""
         B = self.batch_size
         chunks = [order[i * B:(i + 1) * B] for i in range(len(self))]
         if not chunks:

@@ -7,6 +7,9 @@ module tree (so ``state_dict()`` keys/shapes are identical: ``encoder.conv1.weig
 ``nn.BatchNorm2d`` used purely as parameter/buffer holders.  Every forward op is a libfdhip kernel:
 MFMA implicit-GEMM convs, BatchNorm fused with the residual add + ReLU, 3x3/s2 max-pool.
 """
+import glob
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -142,20 +145,94 @@ def stem_channels(num_input_images, cat4beam_to_color, cat2channel, beam_encoder
     return 3 * num_input_images
 
 
+def imagenet_search_path():
+    """Where ``pretrained=True`` looks: torch hub's checkpoint folders, ``$TORCH_HOME`` first."""
+    places = []
+    if os.environ.get("TORCH_HOME"):
+        places.append(os.path.join(os.path.expanduser(os.environ["TORCH_HOME"]), "hub", "checkpoints"))
+    places.append(os.path.join(os.path.expanduser("~"), ".cache", "torch", "hub", "checkpoints"))
+    return places
+
+
+def _match_in_directory(folder, num_layers):
+    """The one ``resnet{n}-*.pth`` / ``resnet{n}.pth`` of ``folder``, None if there is none; two are an error that lists them."""
+    hits = sorted(set(glob.glob(os.path.join(folder, "resnet%d-*.pth" % num_layers)) +
+                      glob.glob(os.path.join(folder, "resnet%d.pth" % num_layers))))
+    if len(hits) > 1:
+        raise RuntimeError("ImageNet weights for ResNet-%d: %s holds more than one candidate: %s" % (num_layers, folder, ", ".join(hits)))
+    return hits[0] if hits else None
+
+
+def find_imagenet_file(num_layers, pretrained=True):
+    """The torchvision ``resnet{num_layers}`` state-dict file that ``pretrained`` names.  A string is a file, or a directory holding
+    one ``resnet{n}-*.pth`` / ``resnet{n}.pth``; ``True`` searches ``imagenet_search_path()``.  Nothing is ever downloaded."""
+    if isinstance(pretrained, (str, os.PathLike)):
+        where = os.path.expanduser(os.fspath(pretrained))
+        if os.path.isfile(where):
+            return where
+        places = [where]
+    else:
+        places = imagenet_search_path()
+    for folder in places:
+        if os.path.isdir(folder):
+            hit = _match_in_directory(folder, num_layers)
+            if hit is not None:
+                return hit
+    raise RuntimeError("ImageNet weights cannot be downloaded here (no network); run with --weights_init scratch, load a checkpoint "
+                       "via load_state_dict, or put torchvision's resnet%d-*.pth where it is looked for (--pretrained_path FILE|DIR); "
+                       "searched: %s" % (num_layers, ", ".join(places)))
+
+
+def load_imagenet_file(trunk, path, num_input_images=1, keep_stem=False):
+    """resnet_encoder.py:33-50, 71-74: torchvision's state dict loaded strictly and in place into ``trunk`` - ``fc``, the BatchNorm
+    buffers and ``num_batches_tracked`` included.  ``num_input_images > 1``: ``conv1.weight = cat([w] * n, 1) / n``.  ``keep_stem``:
+    ``trunk.conv1`` is one of the stems the reference replaces after loading (4, 5, 2 / 2n or 6 input channels); it keeps the
+    values it has, and the file's ``conv1.weight`` is only checked to be a torchvision stem."""
+    loaded = torch.load(path, map_location="cpu")
+    if not isinstance(loaded, dict):
+        raise RuntimeError("%s does not hold a state dict" % path)
+    own = trunk.state_dict()
+    missing = [k for k in own if k not in loaded]
+    if missing:
+        raise RuntimeError("%s: missing key %s (%d in all; is this torchvision's resnet file?)" % (path, missing[0], len(missing)))
+    unexpected = [k for k in loaded if k not in own]
+    if unexpected:
+        raise RuntimeError("%s: unexpected key %s (%d in all; a file for another ResNet depth?)" % (path, unexpected[0], len(unexpected)))
+    values = dict(loaded)
+    stem = values["conv1.weight"]
+    if tuple(stem.shape) != (64, 3, 7, 7):
+        raise RuntimeError("%s: conv1.weight has shape %s, torchvision's stem has (64, 3, 7, 7)" % (path, tuple(stem.shape)))
+    if keep_stem:
+        del values["conv1.weight"]
+    elif num_input_images > 1:
+        values["conv1.weight"] = torch.cat([stem] * num_input_images, 1) / num_input_images
+    for k, v in values.items():
+        if not torch.is_tensor(v) or tuple(v.shape) != tuple(own[k].shape):
+            raise RuntimeError("%s: %s has shape %s, ResNet here has %s (a file for another ResNet depth?)"
+                               % (path, k, tuple(getattr(v, "shape", ())), tuple(own[k].shape)))
+    with torch.no_grad():
+        for k, v in values.items():
+            own[k].copy_(v)
+
+
 class ResnetEncoder(nn.Module):
-    """Same constructor/forward contract as the reference (resnet_encoder.py:56-57,92-103)."""
+    """Same constructor/forward contract as the reference (resnet_encoder.py:56-57,92-103).  ``pretrained``: False, True (ImageNet
+    weights from torch hub's checkpoint folders on disk) or the path of torchvision's file / of a directory that holds it."""
 
     def __init__(self, num_layers, pretrained, num_input_images=1, cat4beam_to_color=False, cat2channel=False,
                  beam_encoder=False, refine_encoder=False):
         super().__init__()
         if num_layers not in _SPEC:
             raise ValueError("{} is not a valid number of resnet layers".format(num_layers))
-        if pretrained:
-            raise RuntimeError("ImageNet weights cannot be downloaded here (no network); run with "
-                               "--weights_init scratch or load a checkpoint via load_state_dict")
         self.num_ch_enc = np.array([64, 64, 128, 256, 512])
         self.encoder = ResNetTrunk(num_layers, stem_channels(num_input_images, cat4beam_to_color, cat2channel,
                                                               beam_encoder, refine_encoder))
+        self.pretrained_file = None
+        if pretrained:                            # True: the hub caches are searched; a string: that file or directory
+            # the stems the reference replaces AFTER loading (resnet_encoder.py:76-87) keep the scratch initialisation
+            self.pretrained_file = find_imagenet_file(num_layers, pretrained)
+            load_imagenet_file(self.encoder, self.pretrained_file, num_input_images,
+                               keep_stem=bool(cat4beam_to_color or cat2channel or beam_encoder or refine_encoder))
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
         self.stem_feature_needed = True       # False: features[0] is None in training mode (nobody reads it; saves its write + re-reads)

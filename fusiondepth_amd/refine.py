@@ -1,7 +1,7 @@
 """The reference's ``python refiner.py`` as a command: options -> loaders -> ``Refiner.train`` with in-training validation.
 
     python -m fusiondepth_amd.refine [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
-                                     [--image_decoder pil|device] [--png_decoder pil|device]
+                                     [--image_decoder pil|device] [--png_decoder pil|device] [--resume PATH|latest] [--shard_val]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.refine ...         # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  refiner.py:168-200: the training lines of
@@ -17,7 +17,8 @@ The Refiner's validation rule is the trainer's (``Trainer.val_metrics`` / ``Trai
 checkpoint names (``weights_best``, ``weights_absrel<N>``) are ``train.py``'s; so are the deviations from the reference listed there:
 ``--splits_dir``, ``--seed``, ``--lidar_source``, ``--val_limit``, ``--no_val``, a ``--num_epochs`` spelled out on the command line
 wins over the derived ``(8 * 17) // batch_size``, ``--dataset`` other than ``kitti`` is refused, scalars go to
-``<log_path>/{train,val}/scalars.jsonl``.
+``<log_path>/{train,val}/scalars.jsonl``.  ``--resume`` and ``--shard_val`` are ``train.py``'s too: a continued run loads every network
+of the epoch checkpoint, the frozen ones included, and ends on the bits of the uninterrupted run.
 """
 import os
 import sys
@@ -26,11 +27,11 @@ import numpy as np
 import torch
 
 from . import dp
-from .train import _read_lines, decode_workers, split_off_extra, write_summary
+from .train import _read_lines, decode_workers, shard_val_lines, split_off_extra, start_epoch_of, write_summary
 
 
 def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_source="files", val_limit=None, no_val=False,
-                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil"):
+                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil", shard_val=False):
     """refiner.py:168-200 -> ``(train_loader, val_loader, gt_depths)``; the last two are None with ``no_val``.  The arguments are
     ``train.build_loaders``'.  ``opt`` should be the ``Refiner``'s own options (its constructor sets ``clone_gdc``, which makes the
     training loader add ``inf_gdc``)."""
@@ -59,6 +60,8 @@ def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_
             raise ValueError("%s holds %d maps for the %d lines of eigen/test_files.txt" % (gt_path, len(gt_depths), len(val_lines)))
         if val_limit is not None:
             val_lines, gt_depths = val_lines[:val_limit], gt_depths[:val_limit]
+        if shard_val:
+            val_lines, gt_depths = shard_val_lines(val_lines, gt_depths, rank, world_size)
         val_loader = KITTIRefinerBatches(opt.data_path, val_lines, opt.height, opt.width, [0], 4, is_train=False,
                                          batch_size=opt.eval_batch_size, shuffle=False, drop_last=False, **common)
     return train_loader, val_loader, gt_depths
@@ -73,20 +76,21 @@ def main(argv=None):
     epochs_given = opt.num_epochs if any(a == "--num_epochs" or a.startswith("--num_epochs=") for a in rest) else None
     torch.manual_seed(extra["seed"])
     refiner = Refiner(opt, rank=rank, world_size=world)
+    refiner.shard_val = bool(extra.get("shard_val")) and world > 1
     if epochs_given is not None:
         refiner.opt.num_epochs = epochs_given
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader, gt_depths = build_loaders(refiner.opt, extra["splits_dir"], rank, world, seed=extra["seed"],
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],
-                                                        no_val=extra["no_val"] or rank != 0, batch_size=refiner.batch_size,
-                                                        local_world_size=local_world, device=refiner.device,
-                                                        image_decoder=extra.get("image_decoder", "pil"),
-                                                        png_decoder=extra.get("png_decoder", "pil"))
+                                                        no_val=extra["no_val"] or (rank != 0 and not refiner.shard_val),
+                                                        batch_size=refiner.batch_size, local_world_size=local_world,
+                                                        device=refiner.device, image_decoder=extra.get("image_decoder", "pil"),
+                                                        png_decoder=extra.get("png_decoder", "pil"), shard_val=refiner.shard_val)
     if val_loader is not None:
         from .validation import ValGroundTruth
         refiner.val_gt = ValGroundTruth(gt_depths, device=refiner.device)
     try:
-        refiner.train(train_loader, val_loader)
+        refiner.train(train_loader, val_loader, start_epoch=start_epoch_of(refiner, extra, train_loader))
         write_summary(refiner, train_loader, rank, loss_scale=1.0)     # the Refiner never accumulates (refiner.py:272-278)
     finally:
         train_loader.close()

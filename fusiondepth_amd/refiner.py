@@ -309,7 +309,10 @@ class Refiner(Trainer):
             t0 = time.time()
             step0 = self.step
             losses = self.train_step(inputs, next_inputs)
-            if self.rank == 0 and self._log_due(batch_idx, step0):
+            due = (self.rank == 0 or self.shard_val) and self._log_due(batch_idx, step0)      # the same decision on every rank
+            if due and self.rank != 0:
+                self._validate_shard()
+            elif due:
                 self.log_time(batch_idx, time.time() - t0, float(losses["loss"]))
                 if "depth_gt" in inputs:
                     self.compute_depth_losses(inputs, self._last_outputs, losses)

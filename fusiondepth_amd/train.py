@@ -2,7 +2,7 @@
 
     python -m fusiondepth_amd.train [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
                                     [--log_images] [--image_decoder pil|device] [--png_decoder pil|device]
-                                    [--png_encoder pil|device]
+                                    [--png_encoder pil|device] [--resume PATH|latest] [--pretrained_path FILE|DIR] [--shard_val]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.train ...          # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  trainer.py:142-174: the training lines of
@@ -14,7 +14,18 @@
     maps), ``trainer.train(train_loader, val_loader)``; on exit every rank writes ``<log_path>/train_summary.rank<k>.json``.
 
 Ranks.  Every rank trains on its own batches; rank 0 alone validates, logs and saves, as ``Trainer`` always did, and the other ranks
-wait for it in the next gradient exchange.  Validation is not sharded.
+wait for it in the next gradient exchange.  ``--shard_val`` (off by default) shares the validation instead: rank r walks test lines
+``r::world_size`` against their own maps, ``Trainer.val_metrics`` gathers the per-image rows of all ranks and puts them back in image
+order, so every rank forms the one-rank mean and the same ``best``; rank 0 alone still logs and saves.
+
+Continuing a run.  ``--resume PATH|latest`` loads every network, ``adam.pth`` and this rank's ``run_state.rank<k>.pth`` of an epoch
+checkpoint (``Trainer.resume``; ``latest``: the highest-numbered complete ``weights_<n>`` under ``<log_path>/models``) and runs the
+remaining epochs; the result is bit for bit the uninterrupted run's (resume.py).  It is refused beside
+``--train_load_weights_folder`` / ``--load_weights_folder`` and for a run that differs in ``world_size``, batch sizes, seed or an
+option that fixes shapes or the data order.  The summary gains ``"resumed_from"`` (the finished epochs of the checkpoint, or null).
+
+``--weights_init pretrained`` reads torchvision's ``resnet{n}-*.pth`` from ``--pretrained_path`` (a file or a directory), then
+``$TORCH_HOME/hub/checkpoints``, then ``~/.cache/torch/hub/checkpoints``; it never downloads (networks/resnet_encoder.py).
 
 Deviations from the reference, on purpose
   * the splits folder is an argument (``--splits_dir``, default ``splits``) instead of a folder beside the script, as in
@@ -45,21 +56,25 @@ import numpy as np
 import torch
 
 from . import dp
+from . import resume as run_state
 from .evaluate_depth import split_off_flags
 
 EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None, "png_decoder": None,
-                "png_encoder": None}
-EXTRA_SWITCHES = ("no_val", "log_images")
+                "png_encoder": None, "resume": None, "pretrained_path": None}
+EXTRA_SWITCHES = ("no_val", "log_images", "shard_val")
 
 
 def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({splits_dir, seed, lidar_source, val_limit,
     no_val}, the remaining arguments); ``log_images: True`` joins the dict where ``--log_images`` is given, and only there, and so
-    do ``image_decoder``, ``png_decoder`` and ``png_encoder`` ('pil' or 'device')."""
+    do ``image_decoder``, ``png_decoder`` and ``png_encoder`` ('pil' or 'device'), ``resume`` ('latest' or a folder),
+    ``pretrained_path`` and ``shard_val: True``.  ``--resume`` beside a weights folder of the command line is a ``ValueError``."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     if not found["log_images"]:
         del found["log_images"]
     take_image_decoder(found)
+    run_state.take_flags(found)
+    run_state.check_flags(found, rest)
     found["seed"] = int(found["seed"])
     if found["val_limit"] is not None:
         found["val_limit"] = int(found["val_limit"])
@@ -91,10 +106,11 @@ def decode_workers(num_workers, local_world_size):
 
 
 def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_source="files", val_limit=None, no_val=False,
-                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil"):
+                  batch_size=None, local_world_size=None, device="cuda", image_decoder="pil", png_decoder="pil", shard_val=False):
     """trainer.py:142-174 -> ``(train_loader, val_loader, gt_depths)``; the last two are None with ``no_val``.  ``batch_size``: the
     per-process micro-batch (``Trainer.batch_size``; default ``opt.batch_size``).  ``local_world_size``: ranks on this host (default
-    ``world_size``).  The validation loader is never sharded: rank 0 walks all of it."""
+    ``world_size``).  The validation loader walks all of the (limited) test lines unless ``shard_val``: then it and ``gt_depths``
+    hold lines ``rank::world_size`` (``shard_val_lines``), for a ``Trainer`` whose ``shard_val`` is set."""
     from .datasets import KITTIRAWBatches, KITTIStereoBatches
     if opt.dataset != "kitti":
         raise NotImplementedError("fusiondepth_amd.train: --dataset %s is not covered (the reference's KITTIOdomDataset has no LiDAR keys, "
@@ -125,9 +141,26 @@ def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_
             raise ValueError("%s holds %d maps for the %d lines of eigen/test_files.txt" % (gt_path, len(gt_depths), len(val_lines)))
         if val_limit is not None:
             val_lines, gt_depths = val_lines[:val_limit], gt_depths[:val_limit]
+        if shard_val:
+            val_lines, gt_depths = shard_val_lines(val_lines, gt_depths, rank, world_size)
         val_loader = builder(opt.data_path, val_lines, opt.height, opt.width, [0], 4, is_train=False, batch_size=opt.eval_batch_size,
                              shuffle=False, drop_last=False, **common)
     return train_loader, val_loader, gt_depths
+
+
+def shard_val_lines(val_lines, gt_depths, rank, world_size):
+    """``--shard_val``: rank r validates lines ``r::world_size`` against their own maps (the shares differ by at most one)."""
+    if len(val_lines) < world_size:
+        raise ValueError("--shard_val: %d validation lines cannot be shared among %d ranks" % (len(val_lines), world_size))
+    return val_lines[rank::world_size], gt_depths[rank::world_size]
+
+
+def start_epoch_of(trainer, extra, train_loader):
+    """``--resume PATH|latest`` -> ``Trainer.resume`` of that folder -> the epoch ``Trainer.train`` starts at (0 without the flag)."""
+    if extra.get("resume") is None:
+        return 0
+    folder = run_state.resolve(extra["resume"], trainer.log_path, list(trainer.models), trainer.world_size)
+    return trainer.resume(folder, train_loader)
 
 
 def param_checksum(trainer):
@@ -144,7 +177,7 @@ def write_summary(trainer, train_loader, rank, loss_scale=None):
     loss = float(last["loss"]) * scale if last is not None else None
     res = {"rank": rank, "world_size": trainer.world_size, "steps": trainer.step, "epochs": len(train_loader.served),
            "batches_per_epoch": len(train_loader), "batch_size": train_loader.batch_size, "last_loss": loss,
-           "param_checksum": param_checksum(trainer), "best": float(trainer.best),
+           "param_checksum": param_checksum(trainer), "best": float(trainer.best), "resumed_from": trainer.resumed_from,
            "items": [order for _, order in train_loader.served]}
     os.makedirs(trainer.log_path, exist_ok=True)
     path = os.path.join(trainer.log_path, "train_summary.rank%d.json" % rank)
@@ -160,8 +193,11 @@ def main(argv=None):
     extra, rest = split_off_extra(sys.argv[1:] if argv is None else argv)
     opt = MonodepthOptions().parse(rest)
     epochs_given = opt.num_epochs if any(a == "--num_epochs" or a.startswith("--num_epochs=") for a in rest) else None
+    if extra.get("pretrained_path"):                             # where --weights_init pretrained looks first (resnet_encoder.py)
+        opt.pretrained_path = extra["pretrained_path"]
     torch.manual_seed(extra["seed"])
     trainer = Trainer(opt, rank=rank, world_size=world)
+    trainer.shard_val = bool(extra.get("shard_val")) and world > 1
     if epochs_given is not None:
         trainer.opt.num_epochs = epochs_given
     if extra.get("log_images") and rank == 0:                    # the other ranks do not log
@@ -171,15 +207,15 @@ def main(argv=None):
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader, gt_depths = build_loaders(opt, extra["splits_dir"], rank, world, seed=extra["seed"],
                                                         lidar_source=extra["lidar_source"], val_limit=extra["val_limit"],
-                                                        no_val=extra["no_val"] or rank != 0, batch_size=trainer.batch_size,
-                                                        local_world_size=local_world, device=trainer.device,
-                                                        image_decoder=extra.get("image_decoder", "pil"),
-                                                        png_decoder=extra.get("png_decoder", "pil"))
+                                                        no_val=extra["no_val"] or (rank != 0 and not trainer.shard_val),
+                                                        batch_size=trainer.batch_size, local_world_size=local_world,
+                                                        device=trainer.device, image_decoder=extra.get("image_decoder", "pil"),
+                                                        png_decoder=extra.get("png_decoder", "pil"), shard_val=trainer.shard_val)
     if val_loader is not None:
         from .validation import ValGroundTruth
         trainer.val_gt = ValGroundTruth(gt_depths, device=trainer.device)
     try:
-        trainer.train(train_loader, val_loader)
+        trainer.train(train_loader, val_loader, start_epoch=start_epoch_of(trainer, extra, train_loader))
         write_summary(trainer, train_loader, rank)
     finally:
         trainer.close()

@@ -23,6 +23,7 @@ import torch
 from . import dp
 from . import functional as FD
 from . import networks
+from . import resume as run_state
 from . import tuning
 from . import weight_layouts
 from .checkpoint import load_state_by_key
@@ -198,6 +199,10 @@ class Trainer:
     png_encoder = "pil"        # "device": the default sink's sheets are encoded on the device (data_ops.encode_png_batch)
     _last_val_io = None        # (inputs, outputs) of the last validation batch, kept only while log_images is on
 
+    # ---- what the commands set: --shard_val, and what --resume continued ----
+    shard_val = False          # every rank validates lines rank::world_size (val_gt holds their maps); val_metrics gathers the rows
+    resumed_from = None        # the finished epochs of the checkpoint ``resume`` loaded
+
     # ---- the steps of __init__ that the sibling drivers of the reference (completor.py, refiner.py) take differently ----
     _SI_CONSTANTS = {}         # FD.PhotoOptions' si_* keywords where they are not the trainer's
 
@@ -225,6 +230,8 @@ class Trainer:
         """trainer.py:66-127 -> (networks by name, their order in ``self.models``, the names of those that are trained; parameters
         of the others are frozen)."""
         pre = self.opt.weights_init == "pretrained" if pretrained is None else pretrained
+        if pre is True and getattr(self.opt, "pretrained_path", None):      # --pretrained_path: before torch hub's folders
+            pre = self.opt.pretrained_path
         depth_layers, pose_layers = self._encoder_layers()
         m = {}
         m["encoder"] = networks.ResnetEncoder(depth_layers, pre, cat4beam_to_color=self.opt.cat_4beam_to_color,
@@ -376,9 +383,12 @@ class Trainer:
         self.lr_scheduler_step()
 
     # ---- driver loop (trainer.py:219-266, 632-642) -----------------------------------------------------------------------
-    def train(self, train_loader=None, val_loader=None):
+    def train(self, train_loader=None, val_loader=None, start_epoch=0):
         """trainer.py:219-228 over ANY iterable of batches in the reference's schema (its DataLoader, a list, a generator
-        factory with ``__iter__``): ``num_epochs`` x ``run_epoch``, a checkpoint every ``save_frequency`` epochs."""
+        factory with ``__iter__``): ``num_epochs`` x ``run_epoch``, a checkpoint every ``save_frequency`` epochs - the networks and
+        ``adam.pth`` by rank 0, then the run state by every rank (``save_run_state``).  ``start_epoch`` > 0 (what ``resume``
+        returned): the counters, the schedule and the generators are left as ``resume`` set them and epochs ``start_epoch ..
+        num_epochs - 1`` are run."""
         if train_loader is not None:
             self.train_loader = train_loader
         if val_loader is not None:
@@ -386,8 +396,9 @@ class Trainer:
         if getattr(self, "train_loader", None) is None:
             raise RuntimeError("Trainer.train: no train_loader (pass one, or set self.train_loader: datasets.KITTIRAWBatches for "
                                "KITTI raw, or any iterable of reference-schema batches)")
-        self.epoch, self.step = 0, 0
-        self.optim.scheduler_epochs = 0        # a second train() on the same object starts its StepLR count afresh
+        if start_epoch == 0:
+            self.epoch, self.step = 0, 0
+            self.optim.scheduler_epochs = 0    # a second train() on the same object starts its StepLR count afresh
         self.start_time = time.time()
         try:
             self.num_total_steps = len(self.train_loader) * self.opt.num_epochs
@@ -396,10 +407,12 @@ class Trainer:
         if self.rank == 0:
             self.save_opts()
         try:
-            for self.epoch in range(self.opt.num_epochs):
+            for self.epoch in range(start_epoch, self.opt.num_epochs):
                 self.run_epoch()
-                if (self.epoch + 1) % self.opt.save_frequency == 0 and self.rank == 0:
-                    self.save_model()
+                if (self.epoch + 1) % self.opt.save_frequency == 0:
+                    if self.rank == 0:
+                        self.save_model()
+                    self.save_run_state(self.checkpoint_folder())          # last: the commit marker of the folder
         finally:
             self.close()                        # the pictures handed to the sink's thread are on disk when train returns
 
@@ -430,7 +443,11 @@ class Trainer:
             step0, first = self.step, batch_idx - self.accumulate_step + 1
             losses = self.train_step(window)
             window = []
-            if self.rank == 0 and any(self._log_due(first + k, step0 + k) for k in range(self.accumulate_step)):
+            # the decision is a function of (batch_idx, step) alone: with shard_val every rank takes it, and enters validation
+            due = (self.rank == 0 or self.shard_val) and any(self._log_due(first + k, step0 + k) for k in range(self.accumulate_step))
+            if due and self.rank != 0:
+                self._validate_shard()
+            elif due:
                 loss = float(losses["loss"]) / self.accumulate_step              # the value trainer.py:243 prints (synchronises)
                 self.log_time(batch_idx, (time.time() - t0) / self.accumulate_step, loss)
                 stacked, outputs = self._last_io
@@ -454,6 +471,13 @@ class Trainer:
     def val_losses(self, batches):
         """What ``run_epoch`` logs under "val": the losses of ``val``.  (``Completor.val`` returns more than the losses.)"""
         return self.val(batches)
+
+    def _validate_shard(self):
+        """A log event on a rank other than 0 with ``shard_val``: its share of the validation, nothing logged or saved."""
+        if getattr(self, "val_loader", None) is not None:
+            self.val_losses(self.val_loader)
+            self._last_val_io = None
+            self.set_train()
 
     def log_time(self, batch_idx, duration, loss):
         """trainer.py:632-642."""
@@ -1079,7 +1103,8 @@ class Trainer:
         gt = self.val_gt
         self.set_eval()
         at = 0
-        with torch.no_grad():
+        sharded = self.shard_val and self.world_size > 1
+        with torch.no_grad(), (self._rank0_statistics() if sharded else contextlib.nullcontext()):
             for inputs in batches:
                 outputs, _ = self.process_batch(inputs, val=True)
                 depth = outputs[("depth", 0, 0)]
@@ -1095,17 +1120,61 @@ class Trainer:
             if at != len(gt):
                 raise ValueError("Trainer.val_metrics: the loader yielded %d images for the %d maps of val_gt" % (at, len(gt)))
             rows = gt.score(self._val_depths).cpu().numpy()          # the one download
-        self.last_val_rows = rows                                    # [N_val, 9]: the seven metrics, ratio, count per image
+        if sharded:
+            rows = self._gather_val_rows(rows)
+        self.last_val_rows = rows                                   # [N_val, 9]: the seven metrics, ratio, count per image
         mean = rows[:, :7].mean(0)
         self.set_train()
         return {m: mean[i] for i, m in enumerate(self.depth_metric_names)}
 
+    @contextlib.contextmanager
+    def _rank0_statistics(self):
+        """``shard_val``: the parameters are the same on every rank, the BatchNorm running statistics are not - each rank updates
+        them from its own batches, and the checkpoint holds rank 0's.  Inside, every rank's networks carry rank 0's floating-point
+        buffers (one broadcast), so that an image is scored as rank 0 would have scored it; on leaving, a rank has its own again."""
+        import torch.distributed as dist
+        bufs = [b for m in self.models.values() for b in m.buffers() if b.is_floating_point()]
+        flat = torch.cat([b.detach().reshape(-1) for b in bufs])
+        mine = flat.clone() if self.rank != 0 else None
+        dist.broadcast(flat, src=0)
+
+        def put(values):
+            at = 0
+            for b in bufs:
+                b.copy_(values[at:at + b.numel()].view(b.shape))
+                at += b.numel()
+
+        if self.rank != 0:
+            put(flat)
+        try:
+            yield
+        finally:
+            if self.rank != 0:
+                put(mine)
+
+    def _gather_val_rows(self, rows):
+        """``shard_val``: rank r scored images ``r::world_size``.  Every rank receives every share (the shares are unequal when
+        ``N % world_size != 0``) and puts the rows back in image order, so the mean is formed over the same array, in the same
+        way, as on one rank - and ``best`` is the same number everywhere."""
+        import numpy as np
+        import torch.distributed as dist
+        shares = [None] * self.world_size
+        dist.all_gather_object(shares, rows)
+        full = np.empty((sum(len(s) for s in shares),) + rows.shape[1:], rows.dtype)
+        for r, share in enumerate(shares):
+            if len(share) != len(full[r::self.world_size]):
+                raise ValueError("Trainer.val_metrics: rank %d scored %d images, its share of %d is %d"
+                                 % (r, len(share), len(full), len(full[r::self.world_size])))
+            full[r::self.world_size] = share
+        return full
+
     def val(self, batches, save_best=True):
         """trainer.py:390-423: validation metrics + best-checkpoint bookkeeping - a new best de/abs_rel is remembered and
         saved as ``weights_best`` and, below 0.080, also as ``weights_absrel<round(1000 * abs_rel)>``.  The folders written
-        are left in ``self.last_saved``."""
+        are left in ``self.last_saved``.  With ``shard_val`` every rank remembers the best, rank 0 alone saves."""
         losses = self.val_metrics(batches)
         self.last_saved = []
+        save_best = save_best and (self.rank == 0 or not self.shard_val)
         if losses["de/abs_rel"] < self.best:
             self.best = float(losses["de/abs_rel"])
             if save_best:
@@ -1119,8 +1188,7 @@ class Trainer:
     def save_model(self, name=None):
         """trainer.py:694-715: one state_dict per network under models/weights_<epoch|name>/ (+ height/width/
         use_stereo in encoder.pth) and adam.pth."""
-        tag = "weights_{}".format(self.epoch if name is None else name)
-        folder = os.path.join(self.log_path, "models", tag)
+        folder = self.checkpoint_folder(name)
         os.makedirs(folder, exist_ok=True)
         for model_name, model in self.models.items():
             to_save = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
@@ -1129,6 +1197,58 @@ class Trainer:
             torch.save(to_save, os.path.join(folder, "{}.pth".format(model_name)))
         torch.save(self.optimizer_state_dict(), os.path.join(folder, "adam.pth"))
         return folder
+
+    def checkpoint_folder(self, name=None):
+        """``<log_path>/models/weights_<epoch|name>``."""
+        return os.path.join(self.log_path, "models", "weights_{}".format(self.epoch if name is None else name))
+
+    # ---- continuing a run (resume.py): what the network files and adam.pth do not hold ---------------------------------------
+    def _run_identity(self, train_loader):
+        """What a continued run must share with the run that wrote the checkpoint (``resume.check_compatible``)."""
+        lines = getattr(train_loader, "filenames", None)
+        return {"world_size": self.world_size, "micro_batch": self.batch_size, "accumulate_step": self.accumulate_step,
+                "seed": getattr(train_loader, "seed", None),
+                "fingerprint": run_state.fingerprint(self.opt, None if lines is None else len(lines))}
+
+    def save_run_state(self, folder):
+        """``<folder>/run_state.rank<k>.pth`` of this rank, written after the networks and ``adam.pth``, through a temporary name:
+        the finished epochs, ``step`` / ``batch_idx`` / ``best``, the StepLR count (``lr`` and the Adam step count are in
+        ``adam.pth``), the train loader's epoch counter and seed, the run's identity (``_run_identity``) and the states of the
+        host generator and of this rank's device generator (the automask tie-break noise is drawn from it)."""
+        loader = getattr(self, "train_loader", None)
+        state = dict(self._run_identity(loader), rank=self.rank, epochs_done=self.epoch + 1, step=self.step, batch_idx=self.batch_idx,
+                     best=float(self.best), scheduler_epochs=self.optim.scheduler_epochs, loader_epoch=getattr(loader, "_epoch", None),
+                     torch_rng=torch.get_rng_state(), cuda_rng=torch.cuda.get_rng_state(self.device))
+        return run_state.write_state(state, folder, self.rank)
+
+    def resume(self, folder, train_loader):
+        """Continue the run whose epoch checkpoint lies in ``folder`` -> the number of finished epochs, for ``train(start_epoch=)``.
+        ALL of ``self.models`` are loaded strictly and in place (the frozen ones of a ``Refiner`` too), ``adam.pth`` is required, and
+        everything ``save_run_state`` wrote is put back, ``train_loader``'s epoch counter included.  A run that differs in
+        ``world_size``, batch sizes, ``accumulate_step``, seed or an option of the fingerprint is refused with a ``ValueError``
+        that names the field, before anything is loaded."""
+        state = run_state.read_state(folder, self.rank)
+        run_state.check_compatible(state, self._run_identity(train_loader))
+        adam = os.path.join(folder, "adam.pth")
+        if not os.path.isfile(adam):
+            raise FileNotFoundError("--resume: %s is missing" % adam)
+        for name, net in self.models.items():
+            path = os.path.join(folder, "{}.pth".format(name))
+            if not os.path.isfile(path):
+                raise FileNotFoundError("--resume: %s is missing" % path)
+            load_state_by_key(net, path)          # strict, in place: parameters stay views of the flat buffer
+        weight_layouts.weights_replaced()
+        FD.refresh_weight_layouts()
+        self.load_optimizer_state_dict(torch.load(adam, map_location="cpu"))       # the device-side [step, lr] pair too
+        self.optim.scheduler_epochs = int(state["scheduler_epochs"])
+        self.step, self.batch_idx, self.best = int(state["step"]), int(state["batch_idx"]), float(state["best"])
+        if state["loader_epoch"] is not None:
+            train_loader.set_epoch(state["loader_epoch"])
+        torch.set_rng_state(state["torch_rng"])
+        torch.cuda.set_rng_state(state["cuda_rng"], self.device)
+        self.resumed_from = int(state["epochs_done"])
+        self.epoch = self.resumed_from - 1
+        return self.resumed_from
 
     def optimizer_state_dict(self):
         """``adam.pth`` in ``torch.optim.Adam.state_dict()`` layout (optim.FlatAdam.state_dict)."""
