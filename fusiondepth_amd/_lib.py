@@ -428,6 +428,11 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def round16(n):
+    """``n`` rounded up to the 16-byte alignment of the staging, arena and output layouts."""
+    return (n + 15) // 16 * 16
+
+
 def f32(t):
     """Contiguous float32 view/copy (plumbing only)."""
     if t.dtype != torch.float32:

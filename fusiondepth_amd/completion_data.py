@@ -48,8 +48,10 @@ import torch
 
 from . import _lib
 from . import data_ops
+from . import image_codecs
 from . import synthetic
-from .datasets import KITTIRAWBatches, _round16, _upload, pil_loader
+from ._lib import round16
+from .datasets import KITTIRAWBatches, _upload, pil_loader
 
 CROP = (352, 1216)                                           # bottom_crop, completion_dataset.py:230-244
 PAD = (384, 1280)                                            # kitti_completion.py:35-40, 71-75
@@ -210,7 +212,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
     the others are ``KITTIRAWBatches``'.  The split is ``train`` if ``is_train`` else ``val`` (``val_split`` = "select" / "full"), and
     ``test_completion`` when ``opt.completion_test``.  ``decoder="device"`` is accepted and changes nothing: the colour frames of
     the completion tree are PNG files.  ``png_decoder="device"`` moves the 16-bit depth PNGs of every batch (beam planes, ``depth_gt``,
-    ``full_res_4beam``) to ``data_ops.PngBatchJob``: inflated on the pool, unfiltered by ``fd_png_unfilter`` straight into the planes
+    ``full_res_4beam``) to ``image_codecs.PngBatchJob``: inflated on the pool, unfiltered by ``fd_png_unfilter`` straight into the planes
     ``fd_depth_png_keys`` reads, every key bit for bit the ``pil`` route's; the reference's 16-bit assertion then costs one small
     download per batch.  The colour frames stay with Pillow either way: their crop, pad and mirror run on the host threads."""
 
@@ -311,7 +313,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
         pos = 0
         for name, descs in tables.items():
             plan[name] = (pos, pos + size * len(descs))
-            pos = _round16(pos + size * len(descs))
+            pos = round16(pos + size * len(descs))
         plan["data"] = (pos, pos + 2 * at)
         plan["bytes"] = max(pos + 2 * at, 16)
         return plan
@@ -329,7 +331,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
         plan["staging"] = staging
         if on_device:
             plan["paths"] = list(plan["planes"])
-            plan["job"] = data_ops.PngBatchJob(plan["paths"], pool, mode="gray16")
+            plan["job"] = image_codecs.PngBatchJob(plan["paths"], pool, mode="gray16")
             plan["futures"] = []
             return plan
         data = host[plan["data"][0]:plan["data"][1]].view(np.uint16)
@@ -385,7 +387,7 @@ class KITTICompletionBatches(KITTIRAWBatches):
         job = plan["job"]
         job.wait_host()
         table = job.layout()[0]
-        for d, path, (_, _, h, w) in zip(table, plan["paths"], job._slots):
+        for d, path, (h, w) in zip(table, plan["paths"], job.sizes()):
             off, ph, pw = plan["planes"][path]
             if (h, w) != (ph, pw):
                 raise RuntimeError("KITTICompletionBatches: %s changed size while it was read (%s, planned %s)" % (path, (h, w), (ph, pw)))

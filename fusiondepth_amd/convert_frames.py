@@ -5,8 +5,8 @@
                                              [--png_decoder device|pil] [--delete_png] [--overwrite] [--batch 36] [--workers 16]
 
     Every ``*.png`` under ``D``, in sorted order, becomes ``<same path>.jpg`` (under ``O`` if given), written through a temporary name
-    and a rename on the host pool.  A batch is decoded with ``data_ops.decode_png_batch(mode="rgb")`` and encoded with
-    ``data_ops.encode_jpeg_batch``: the frames stay on the device between the two codecs.  ``--delete_png`` removes a PNG only after
+    and a rename on the host pool.  A batch is decoded with ``image_codecs.decode_png_batch(mode="rgb")`` and encoded with
+    ``image_codecs.encode_jpeg_batch``: the frames stay on the device between the two codecs.  ``--delete_png`` removes a PNG only after
     its JPEG has been renamed into place.  An existing ``.jpg`` is skipped without ``--overwrite``; a 16-bit PNG (depth ground truth
     under the same root) is skipped, never converted and never deleted, and reported; an 8-bit grey PNG becomes a greyscale JPEG
     through Pillow.  ``--encoder pil --png_decoder pil`` gives the same files from Pillow alone.
@@ -21,7 +21,7 @@ import json
 import os
 import threading
 
-from . import data_ops
+from . import image_codecs
 
 SKIP_MODES = ("I;16", "I;16B", "I;16L", "I;16N", "I", "F")       # Pillow's modes of a 16-bit (or wider) single-channel PNG
 
@@ -60,15 +60,15 @@ def _pil_file(path, kind, quality, sampling):
     from PIL import Image
     with Image.open(path) as img:
         a = np.asarray(img if kind == "grey" else img.convert("RGB"))
-    return data_ops._pil_jpeg(a, quality, sampling)
+    return image_codecs.pil_jpeg(a, quality, sampling)
 
 
 def convert(data_path, out_path=None, quality=92, sampling="2x2", encoder="device", png_decoder="device", delete_png=False, overwrite=False,
             batch=36, workers=16):
     for name, v in (("--encoder", encoder), ("--png_decoder", png_decoder)):
-        if v not in data_ops.JPEG_ENCODERS:
+        if v not in image_codecs.JPEG_ENCODERS:
             raise ValueError("convert_frames: %s must be 'pil' or 'device', got %r" % (name, v))
-    data_ops.check_jpeg_params(quality, sampling, 1, "convert_frames")
+    image_codecs.check_jpeg_params(quality, sampling, 1, "convert_frames")
     if not isinstance(sampling, str):
         raise ValueError("convert_frames: --sampling is one name for the whole tree")
     if batch < 1 or workers < 1:
@@ -96,7 +96,7 @@ def convert(data_path, out_path=None, quality=92, sampling="2x2", encoder="devic
             files = [None] * len(part)
             if encoder == "device" and rgb:
                 if png_decoder == "device":
-                    frames, _ = data_ops.decode_png_batch([part[i][0] for i in rgb], pool=pool, mode="rgb")
+                    frames, _ = image_codecs.decode_png_batch([part[i][0] for i in rgb], pool=pool, mode="rgb")
                 else:
                     import numpy as np
                     from PIL import Image
@@ -105,7 +105,7 @@ def convert(data_path, out_path=None, quality=92, sampling="2x2", encoder="devic
                         with Image.open(path) as img:
                             return np.asarray(img.convert("RGB"))
                     frames = list(pool.map(load, [part[i][0] for i in rgb]))
-                enc, stats = data_ops.encode_jpeg_batch(frames, quality=quality, sampling=sampling, pool=pool)
+                enc, stats = image_codecs.encode_jpeg_batch(frames, quality=quality, sampling=sampling, pool=pool)
                 for i, f in zip(rgb, enc):
                     files[i] = f
                 res["device"] += stats["device"]

@@ -75,9 +75,11 @@ import torch
 
 from . import _lib
 from . import data_ops
+from . import image_codecs
 from . import kitti_utils
 from . import sparsify as SP
 from . import synthetic
+from ._lib import round16
 
 SIDE_MAP = {"2": 2, "3": 3, "l": 2, "r": 3}                  # kitti_dataset.py:42
 JITTER_RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))     # mono_dataset.py:65-68
@@ -89,10 +91,6 @@ def pil_loader(path):
     with open(path, "rb") as f:
         with Image.open(f) as img:
             return np.asarray(img.convert("RGB"))
-
-
-def _round16(n):
-    return (n + 15) // 16 * 16
 
 
 def _read_into(path, dst):
@@ -127,9 +125,9 @@ class KITTIRAWBatches:
     ``velodyne_points``), ``line_spec`` = the rows raw mode keeps (default: the reference's list for ``opt.nbeams``),
     ``sparsify_grid`` = (H, W) of its angular grid, ``rank`` / ``world_size`` = this process's shard of every epoch (data-parallel
     training; the defaults give the whole epoch, exactly as before), ``decoder`` = ``"pil"`` (Pillow on the pool, the default) or
-    ``"device"`` (``data_ops.JpegBatchJob``: Huffman decoding on the pool, the rest in HIP, byte for byte Pillow's frames;
+    ``"device"`` (``image_codecs.JpegBatchJob``: Huffman decoding on the pool, the rest in HIP, byte for byte Pillow's frames;
     ``decode_stats`` counts the frames each way; it is for JPEG frames and changes nothing for a ``.png`` tree, ``loader=`` with it
-    raises), ``png_decoder`` = the same choice for a ``.png`` tree (``data_ops.PngBatchJob``: the inflate on the pool, the scanline
+    raises), ``png_decoder`` = the same choice for a ``.png`` tree (``image_codecs.PngBatchJob``: the inflate on the pool, the scanline
     filters in HIP, byte for byte Pillow's frames, counted in ``decode_stats`` too; it changes nothing for a JPEG tree, ``loader=``
     with it raises)."""
 
@@ -324,7 +322,7 @@ class KITTIRAWBatches:
         at = 0
         for name, nbytes in (("offsets", 4 * (S + 1)), ("keys", 8 * S), ("descs", ctypes.sizeof(_lib.RasterDesc) * S)):
             plan[name] = (at, at + nbytes)
-            at = _round16(at + nbytes)
+            at = round16(at + nbytes)
         plan["points"] = (at, at + 16 * sum(lengths))
         plan["bytes"] = max(plan["points"][1], 16)
         return plan
@@ -360,7 +358,7 @@ class KITTIRAWBatches:
         pool = self._workers()
         on_device = self.decoder == "device" or self.png_decoder == "device"
         if on_device:                                            # frame-major, the order of every colour key
-            job = data_ops.JpegBatchJob if self.decoder == "device" else data_ops.PngBatchJob
+            job = image_codecs.JpegBatchJob if self.decoder == "device" else image_codecs.PngBatchJob
             items[0]["decode_job"] = job([it["images"][fi] for fi in range(len(self.frame_idxs)) for it in items], pool)
         for it in items:
             if not on_device:
@@ -671,7 +669,7 @@ class KITTIRefinerBatches(KITTIRAWBatches):
         image size (``inf_gdc`` writes its maps at the size of camera 2's rectified image, whatever the side)."""
         B = len(items)
         table_bytes = ctypes.sizeof(_lib.ResizeDesc) * B
-        base = _round16(table_bytes)
+        base = round16(table_bytes)
         descs, at = [], 0
         for it in items:
             _, (im_h, im_w) = self._projection(it["date"], 2)

@@ -172,7 +172,7 @@ def depth_export(pred_disps, sizes, ratios=None, pred_depth_scale_factor=1.0, wa
     (with ``want_depth``) adds a third element: per chunk, ``(packed float32 device tensor, EXPORT_DESC array)`` - what the depth list
     is made of views of, in the form ``points_export(packed=...)`` takes without another launch or copy.  ``want_device``: the uint16
     maps stay on the device - N ``torch.uint16`` [H_i,W_i] tensors, views into one buffer per chunk, and no download - for
-    ``data_ops.encode_png_batch``."""
+    ``image_codecs.encode_png_batch``."""
     if want_packed and not want_depth:
         raise ValueError("depth_export: want_packed needs want_depth")
     if not torch.cuda.is_available():

@@ -17,7 +17,7 @@ disparities, ground truth ``<splits_dir>/detection/gt_depths.npz`` (``detection.
     callback quantises each corrected map (``detection.quantize_u16``).
   * the maps go to ``<data_path>/<folder of the line>/<det_name>/{:06d}.png``, written with PIL on a pool of at most 16 host threads
     while the next chunk runs on the device.  ``--png_encoder device`` (this script's flag; ``evaluate(..., png_encoder="device")``;
-    default ``pil``): the uint16 payload stays on the device and ``data_ops.encode_png_batch`` encodes it there, chunk by chunk (one
+    default ``pil``): the uint16 payload stays on the device and ``image_codecs.encode_png_batch`` encodes it there, chunk by chunk (one
     map at a time with ``--eval_gdc``); the pool writes the files from the encoder's pinned buffer.  The files differ from Pillow's in
     their bytes, not in a single decoded value; maps, scores and clouds are untouched.  As in the reference (:388), the map is saved BEFORE the [1e-3, 80] clamp of the scorer.
 
@@ -84,8 +84,8 @@ def _save_bytes(path, data):
 
 def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0, png_encoder="pil"):
     """See the module docstring."""
-    from . import data_ops
-    data_ops.check_png_encoder(png_encoder, "export_detection: --png_encoder")
+    from . import image_codecs
+    image_codecs.check_png_encoder(png_encoder, "export_detection: --png_encoder")
     on_device = png_encoder == "device"
     ED._refuse_uncovered(opt)
     if not opt.det_name:
@@ -179,7 +179,7 @@ def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0, png_encode
 
             def on_depth(i, depth):                              # after scaling and GDC, before the clamp (:388)
                 if on_device:
-                    (data,), _ = data_ops.encode_png_batch([detection.quantize_u16(depth, want_device=True)], pool)
+                    (data,), _ = image_codecs.encode_png_batch([detection.quantize_u16(depth, want_device=True)], pool)
                     writes.append(pool.submit(_save_bytes, paths[i], data))
                 else:
                     writes.append(pool.submit(_save_png, paths[i], detection.quantize_u16(depth)))
@@ -209,7 +209,7 @@ def evaluate(opt, splits_dir="splits", pl_name=None, pl_max_high=1.0, png_encode
                     clouds = detection.points_export(None, pl_calibs[a:b], pl_max_high, packed=pack)
                     writes += [pool.submit(_save_bin, pl_paths[a + k], c) for k, c in enumerate(clouds)]
                 if on_device:                                    # the payload never leaves the device unencoded
-                    files, _ = data_ops.encode_png_batch(maps, pool)
+                    files, _ = image_codecs.encode_png_batch(maps, pool)
                     writes += [pool.submit(_save_bytes, paths[a + k], f) for k, f in enumerate(files)]
                 else:
                     writes += [pool.submit(_save_png, paths[a + k], m) for k, m in enumerate(maps)]

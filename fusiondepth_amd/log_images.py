@@ -158,7 +158,7 @@ def render(inputs, outputs, frame_ids, scales, J, Ts=None, first=0, automask=Tru
     Returns ``(sheets, tiles)``: the uint8 array [J,Hs,Ws,3] (a view of the pinned download) and ``{tag: view into its sheet}``, [h,w,3]
     each; with ``want_stats`` also ``{disparity tag: (mi, ma)}`` as float32, the minimum and maximum the call used (NaN, NaN where
     the tile holds a NaN).  ``encode`` (not with ``want_stats``): the sheets are encoded on the device
-    (``data_ops.encode_png_batch``) and what comes down is their PNG files - ``(files, None)``, one ``memoryview`` per sheet into one
+    (``image_codecs.encode_png_batch``) and what comes down is their PNG files - ``(files, None)``, one ``memoryview`` per sheet into one
     pinned buffer, each decoding to the sheet the call without ``encode`` returns."""
     if encode and want_stats:
         raise ValueError("render: encode and want_stats cannot be combined")
@@ -257,8 +257,8 @@ def render(inputs, outputs, frame_ids, scales, J, Ts=None, first=0, automask=Tru
         _lib.call("fd_log_sheets", ctypes.addressof(table), table_d.data_ptr(), J, NT, ctypes.addressof(cfg), sheets.data_ptr(),
                   ws.data_ptr(), _lib.stream())
         if encode:                                               # the sheets leave the device as PNG files: no pixel download
-            from . import data_ops
-            files, _ = data_ops.encode_png_batch([sheets[j] for j in range(J)])
+            from . import image_codecs
+            files, _ = image_codecs.encode_png_batch([sheets[j] for j in range(J)])
             return files, None
         host = torch.empty(sheets.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(sheets)                                       # the one download; synchronises, the sources are free to go afterwards

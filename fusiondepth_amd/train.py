@@ -44,7 +44,7 @@ Deviations from the reference, on purpose
     reference's image summaries (trainer.py:656-681) at every log event: one contact sheet per item, rendered on the device
     (log_images.py), as ``<log_path>/{train,val}/images/{step:07d}_{j}.png``; ``Trainer.image_sink`` takes a tensorboard or wandb
     writer instead.  Rank 0 alone logs, so the switch is set on rank 0 alone.  ``--png_encoder device`` (default ``pil``) encodes
-    the sheets on the device (``data_ops.encode_png_batch``) instead of with PIL on the sink's thread: the default sink then receives
+    the sheets on the device (``image_codecs.encode_png_batch``) instead of with PIL on the sink's thread: the default sink then receives
     and writes encoded files, which decode to the same pixels; a sink of your own keeps receiving arrays and tiles; the training
     state is not touched either way.
 """

@@ -196,7 +196,7 @@ class Trainer:
     # ---- the image summaries of trainer.py:656-681 (log_pictures); off unless a caller sets the switch ----
     log_images = False         # every log event of run_epoch also renders the pictures of the batch that was due (log_images.py)
     image_sink = None          # callable (mode, step, sheets, tiles); None: log_images.PngSink(log_path), made at the first event
-    png_encoder = "pil"        # "device": the default sink's sheets are encoded on the device (data_ops.encode_png_batch)
+    png_encoder = "pil"        # "device": the default sink's sheets are encoded on the device (image_codecs.encode_png_batch)
     _last_val_io = None        # (inputs, outputs) of the last validation batch, kept only while log_images is on
 
     # ---- what the commands set: --shard_val, and what --resume continued ----

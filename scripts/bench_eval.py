@@ -715,19 +715,19 @@ def completion_val_step(a):
 
 
 def png_encode_step(a):
-    """Batch PNG encoding: data_ops.encode_png_batch against Pillow on 16 threads, the routes alternating, after a decode-and-compare
+    """Batch PNG encoding: image_codecs.encode_png_batch against Pillow on 16 threads, the routes alternating, after a decode-and-compare
     of both outputs.  Maps: fd_depth_export's uint16 payload of textured synthetic disparities; sheets: 768x4480 RGB contact sheets
     with a black background (textured tiles and a flat grey one)."""
     import concurrent.futures
     import ctypes
     import io
     from PIL import Image
-    from fusiondepth_amd import data_ops as DO
+    from fusiondepth_amd import image_codecs as DO
     from fusiondepth_amd import detection as D
     H, W, h, w = 375, 1242, 192, 640
     rng = np.random.RandomState(5)
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=16)
-    lines = ["PNG encoding, data_ops.encode_png_batch (3 launches) against Image.save on 16 threads after the download; median of %d "
+    lines = ["PNG encoding, image_codecs.encode_png_batch (3 launches) against Image.save on 16 threads after the download; median of %d "
              "(min, max) after one warm-up round, the routes alternating" % a.reps]
 
     def pil_one(arr):
@@ -756,9 +756,9 @@ def png_encode_step(a):
         assert st["fallback"] == 0 and all(torch.equal(b, x) for b, x in zip(back, images)), "decode_png_batch of the files differs"
         # the launches alone: the two library calls on resident buffers, with the plan of the first run
         job = DO.PngEncodeJob(images, pool)
-        job._event.synchronize()
+        words = job.stats_words()
         blocks = torch.empty((job.sizes.blocks * ctypes.sizeof(DO._lib.PngEncBlock),), dtype=torch.uint8, pin_memory=True)
-        _, total = DO.png_enc_plan(job.table, n, job._stats.numpy().view(np.uint32), blocks.data_ptr())
+        _, total = DO.png_enc_plan(job.table, n, words, blocks.data_ptr())
         room = (total + 3) // 4 * 4 + 4
         out = torch.empty((room,), dtype=torch.uint8, device="cuda")
 

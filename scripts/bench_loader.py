@@ -44,20 +44,20 @@ fd_velo_rasterize_batch) the same way, as a run of its own:
                           times under ``rocprofv3 --kernel-trace --stats`` (a run of its own).
 
  12. ``jpeg``             ``--step jpeg`` (a run of its own, ``| tee profiles/jpeg_decode_time.log``): 36 JPEG frames of 1242x375 (4:2:2, quality
-                          92) through ``data_ops.decode_jpeg_batch`` and through pil_loader on 16 threads + np.stack + upload, alternating; the
+                          92) through ``image_codecs.decode_jpeg_batch`` and through pil_loader on 16 threads + np.stack + upload, alternating; the
                           host Huffman phase, the upload and the two kernels against their traffic bound; the entropy decoder against
                           Pillow's whole decode on one thread; ``KITTIRAWBatches`` items/s and Trainer images/s fed by either ``decoder=``.
                           The kernels' own times: ``rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_loader.py --step
                           jpeg_kernels``, then ``--step jpeg_trace_report --trace_dir DIR``.
 
  13. ``png``              ``--step png`` (a run of its own, ``| tee profiles/png_decode_time.log``): step 12's workload as PNG files written by
-                          Pillow with its default settings, through ``data_ops.decode_png_batch`` and through pil_loader on 16 threads +
+                          Pillow with its default settings, through ``image_codecs.decode_png_batch`` and through pil_loader on 16 threads +
                           np.stack + upload, alternating; the host inflate phase, the upload and the two kernels against their traffic bound
                           and as a share of the batch; ``fd_png_inflate`` against ``zlib.decompress`` and Pillow's whole decode on one
                           thread; the completion loader's 16 depth planes by either route; ``KITTIRAWBatches`` items/s and Trainer
                           images/s fed by either ``png_decoder=``.
  14. ``jpeg_enc``         ``--step jpeg_enc`` (a run of its own, ``| tee -a profiles/jpeg_encode_time.log``): 36 frames of step 12's content
-                          through ``data_ops.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, ``fd_jpeg_enc_encode`` alone against
+                          through ``image_codecs.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, ``fd_jpeg_enc_encode`` alone against
                           its traffic bound, and ``convert_frames`` end to end against ``--encoder pil --png_decoder pil``.
 
 The worker pool is 16, never ``os.cpu_count()``.  Nothing here is imported by the package; bench.py is untouched.
@@ -377,13 +377,13 @@ def _spread(v):
 
 
 def step_jpeg(args):
-    """[12] ``data_ops.decode_jpeg_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
+    """[12] ``image_codecs.decode_jpeg_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
     builder and the trainer fed by either route.  The routes alternate inside this one run."""
     import concurrent.futures
     import ctypes
     import torch
     sys.path.insert(0, ROOT)
-    from fusiondepth_amd import _lib, data_ops
+    from fusiondepth_amd import _lib, image_codecs
     from fusiondepth_amd.datasets import KITTIRAWBatches, pil_loader
     N = 36
     with tempfile.TemporaryDirectory() as root:
@@ -394,7 +394,7 @@ def step_jpeg(args):
         pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
 
         def route_device():
-            frames, stats = data_ops.decode_jpeg_batch(batch_paths, pool=pool)
+            frames, stats = image_codecs.decode_jpeg_batch(batch_paths, pool=pool)
             torch.cuda.synchronize()
             assert stats["fallback"] == 0, stats
             return frames
@@ -419,13 +419,13 @@ def step_jpeg(args):
 
         # one thread, per frame: the entropy decoder alone against Pillow's whole decode
         datas = [open(p, "rb").read() for p in batch_paths]
-        info = data_ops.jpeg_probe(datas[0])[1]
+        info = image_codecs.jpeg_probe(datas[0])[1]
         coef, qt = np.empty(info.coef_count, np.int16), np.empty(192, np.uint16)
         one = {"entropy": [], "pillow": []}
         for _ in range(3):
             t0 = time.perf_counter()
             for d in datas:
-                assert data_ops.jpeg_entropy_decode(d, coef, qt)[0] == 0
+                assert image_codecs.jpeg_entropy_decode(d, coef, qt)[0] == 0
             one["entropy"].append(1e3 * (time.perf_counter() - t0) / N)
             t0 = time.perf_counter()
             for p in batch_paths:
@@ -439,7 +439,7 @@ def step_jpeg(args):
         host_ms, up_ms, k_ms = [], [], []
         for _ in range(args.iters):
             t0 = time.perf_counter()
-            job = data_ops.JpegBatchJob(batch_paths, pool)
+            job = image_codecs.JpegBatchJob(batch_paths, pool)
             lay = job.wait_host()
             host_ms.append(1e3 * (time.perf_counter() - t0))
             job.finish("cuda")                                   # writes the descriptor table into the staging buffer
@@ -539,11 +539,11 @@ def step_jpeg_kernels(args):
     """3 + ``--iters`` batches of 36 frames through ``decode_jpeg_batch``, for ``rocprofv3 --kernel-trace --stats -d DIR -- ...``."""
     import torch
     sys.path.insert(0, ROOT)
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     with tempfile.TemporaryDirectory() as root:
         _, paths, _ = write_jpeg_tree(root, 36)
         for _ in range(3 + args.iters):
-            data_ops.decode_jpeg_batch(paths)
+            image_codecs.decode_jpeg_batch(paths)
             torch.cuda.synchronize()
 
 
@@ -571,7 +571,7 @@ def write_png_tree(root, n_frames):
 
 
 def step_png(args):
-    """[13] ``data_ops.decode_png_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
+    """[13] ``image_codecs.decode_png_batch`` against the parent route (pil_loader on 16 threads + np.stack + upload), its phases, the
     inflate alone against zlib and Pillow on one thread, the builder and the trainer fed by either route, and the completion loader's
     depth planes.  The routes alternate inside this one run."""
     import concurrent.futures
@@ -580,7 +580,7 @@ def step_png(args):
     import torch
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from fusiondepth_amd import _lib, completion_data as CD, data_ops
+    from fusiondepth_amd import _lib, completion_data as CD, image_codecs
     from fusiondepth_amd.datasets import KITTIRAWBatches, pil_loader
     import png_ref
     N = 36
@@ -595,7 +595,7 @@ def step_png(args):
         pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
 
         def route_device():
-            frames, stats = data_ops.decode_png_batch(batch_paths, pool=pool)
+            frames, stats = image_codecs.decode_png_batch(batch_paths, pool=pool)
             torch.cuda.synchronize()
             assert stats["fallback"] == 0, stats
             return frames
@@ -619,14 +619,14 @@ def step_png(args):
             say("    %-88s %7.1f frames/s, ms per batch of %d: %s  (%d alternating runs)" % (label + ":", 1e3 * N / med, N, _spread(t[name]), args.iters))
 
         # one thread, per frame: the inflate alone against zlib's and against Pillow's whole decode
-        info = data_ops.png_probe(datas[0])[1]
+        info = image_codecs.png_probe(datas[0])[1]
         dst = np.empty(info.raw_bytes, np.uint8)
         streams = [png_ref.idat(d) for d in datas]
         one = {"inflate": [], "zlib": [], "pillow": []}
         for _ in range(3):
             t0 = time.perf_counter()
             for d in datas:
-                assert data_ops.png_inflate(d, dst)[0] == 0
+                assert image_codecs.png_inflate(d, dst)[0] == 0
             one["inflate"].append(1e3 * (time.perf_counter() - t0) / N)
             t0 = time.perf_counter()
             for s in streams:
@@ -646,7 +646,7 @@ def step_png(args):
         rgb_bytes = N * 3 * H0 * W0
         for _ in range(args.iters):
             t0 = time.perf_counter()
-            job = data_ops.PngBatchJob(batch_paths, pool)
+            job = image_codecs.PngBatchJob(batch_paths, pool)
             lay = job.wait_host()
             host_ms.append(1e3 * (time.perf_counter() - t0))
             table, _, _, _, out_bytes = job.layout()
@@ -695,7 +695,7 @@ def step_png(args):
             return dev.view(torch.int16).view(len(depth_paths), plane)[:, :H0 * W0]
 
         def depth_device():
-            frames, stats = data_ops.decode_png_batch(depth_paths, pool=pool, mode="gray16")
+            frames, stats = image_codecs.decode_png_batch(depth_paths, pool=pool, mode="gray16")
             high = torch.stack([f.view(torch.uint8).view(-1)[1::2].amax() for f in frames]).cpu()          # the loader's 16-bit assertion
             assert stats["fallback"] == 0 and bool((high > 0).all())
             return frames
@@ -1357,7 +1357,7 @@ def drive(args):
 
 # ---------------------------------------------------------------------------------------------------- 14. JPEG outputs on the device
 def step_jpeg_enc(args):
-    """[14] ``data_ops.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, the library call alone against its traffic bound, and
+    """[14] ``image_codecs.encode_jpeg_batch`` against Pillow's ``save`` on 16 threads, the library call alone against its traffic bound, and
     ``convert_frames`` end to end on a synthetic PNG tree against ``--encoder pil --png_decoder pil``.  The routes alternate inside
     this one run, after a byte comparison; run it twice for the run-to-run spread."""
     import concurrent.futures
@@ -1366,7 +1366,7 @@ def step_jpeg_enc(args):
     import torch
     from PIL import Image
     sys.path.insert(0, ROOT)
-    from fusiondepth_amd import _lib, convert_frames, data_ops
+    from fusiondepth_amd import _lib, convert_frames, image_codecs
     N, Q, S = 36, 92, "2x2"
     note = say
 
@@ -1375,7 +1375,7 @@ def step_jpeg_enc(args):
     pool = concurrent.futures.ThreadPoolExecutor(WORKERS)
 
     def route_device():
-        return data_ops.encode_jpeg_batch(dev, quality=Q, sampling=S, pool=pool)[0]
+        return image_codecs.encode_jpeg_batch(dev, quality=Q, sampling=S, pool=pool)[0]
 
     def pil_one(a):
         f = io.BytesIO()
@@ -1404,7 +1404,7 @@ def step_jpeg_enc(args):
         note("    %-72s %8.1f frames/s, ms per batch of %d: %s  (%d alternating runs)" % (label + ":", 1e3 * N / med, N, _spread(t[name]), iters))
 
     # the library call alone: the two small uploads, the clear and the seven launches
-    table, sizes = data_ops.jpeg_enc_layout([(W0, H0, 2, 2)] * N)
+    table, sizes = image_codecs.jpeg_enc_layout([(W0, H0, 2, 2)] * N)
     for d, x in zip(table, dev):
         d.src = x.data_ptr()
     work = torch.empty((sizes.work_bytes,), dtype=torch.uint8, device="cuda")
@@ -1413,8 +1413,8 @@ def step_jpeg_enc(args):
     ms = []
     for k in range(iters + 2):
         ev[0].record()
-        data_ops.call("fd_jpeg_enc_encode", work.data_ptr(), sizes.work_bytes, ctypes.addressof(table), N, Q, out.data_ptr(), sizes.out_bytes,
-                      _lib.stream())
+        _lib.call("fd_jpeg_enc_encode", work.data_ptr(), sizes.work_bytes, ctypes.addressof(table), N, Q, out.data_ptr(), sizes.out_bytes,
+                  _lib.stream())
         ev[1].record()
         torch.cuda.synchronize()
         if k >= 2:

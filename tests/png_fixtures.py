@@ -184,8 +184,8 @@ def fixtures():
     """[(name, bytes)], all inside the covered set; a name starts with its format (rgb8, g8, g16)."""
     if "all" in _CACHE:
         return _CACHE["all"]
-    from fusiondepth_amd import data_ops
-    band = data_ops.PNG_BAND_ROWS                               # held to fd_png_band_rows() by tests/test_png_cpu.py
+    from fusiondepth_amd import image_codecs
+    band = image_codecs.PNG_BAND_ROWS                           # held to fd_png_band_rows() by tests/test_png_cpu.py
     rng = np.random.default_rng(2025)
     out = []
     # Pillow's writer

@@ -1,4 +1,4 @@
-"""Baseline JPEG frames on the device: ``data_ops.decode_jpeg_batch`` against Pillow on every byte (the fixtures of
+"""Baseline JPEG frames on the device: ``image_codecs.decode_jpeg_batch`` against Pillow on every byte (the fixtures of
 tests/test_jpeg_cpu.py, all inside the covered set, so a fallback cannot hide a kernel failure), the fallback for an uncovered
 stream, the descriptor rules of ``fd_jpeg_reconstruct``, and ``KITTIRAWBatches(decoder="device")`` - and one derived builder -
 against the ``decoder="pil"`` batch, key by key."""
@@ -41,9 +41,9 @@ def _check(frames, datas, names):
 
 
 def test_mixed_batch_equals_pillow_on_every_byte():
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     names, datas = zip(*JF.fixtures())
-    frames, stats = data_ops.decode_jpeg_batch(list(datas))
+    frames, stats = image_codecs.decode_jpeg_batch(list(datas))
     torch.cuda.synchronize()
     assert stats == {"device": len(datas), "fallback": 0}
     _check(frames, datas, names)
@@ -59,31 +59,31 @@ def test_mixed_batch_equals_pillow_on_every_byte():
 
 
 def test_one_file_alone(tmp_path):
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     name, data = next((n, d) for n, d in JF.fixtures() if n == "33x31-420-noise-q92")
     path = os.path.join(str(tmp_path), "one.jpg")
     with open(path, "wb") as fh:
         fh.write(data)
     for src in (data, path):
-        frames, stats = data_ops.decode_jpeg_batch([src])
+        frames, stats = image_codecs.decode_jpeg_batch([src])
         assert stats == {"device": 1, "fallback": 0}
         _check(frames, [data], [name])
 
 
 def test_uncovered_stream_falls_back_to_pillow():
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     picks = [d for n, d in JF.fixtures() if n.startswith("50x40-") or n.startswith("33x31-422")]
     prog = dict(JF.uncovered())["progressive"]
     datas = picks[:3] + [prog] + picks[3:]
-    frames, stats = data_ops.decode_jpeg_batch(datas)
+    frames, stats = image_codecs.decode_jpeg_batch(datas)
     assert stats == {"device": len(datas) - 1, "fallback": 1}
     _check(frames, datas, ["mixed %d" % i for i in range(len(datas))])
 
 
 def _staging_for(datas):
     """The host job of a batch -> (its layout, descriptor table, total bytes, out bytes), to be uploaded by hand."""
-    from fusiondepth_amd import data_ops
-    job = data_ops.JpegBatchJob(datas)
+    from fusiondepth_amd import image_codecs
+    job = image_codecs.JpegBatchJob(datas)
     lay = job.wait_host()
     job.finish("cuda")                                           # writes the descriptor table
     torch.cuda.synchronize()

@@ -1,4 +1,4 @@
-"""JPEG outputs on the device: ``data_ops.encode_jpeg_batch`` against the restatement (tests/jpeg_enc_ref.py) and against Pillow, whole
+"""JPEG outputs on the device: ``image_codecs.encode_jpeg_batch`` against the restatement (tests/jpeg_enc_ref.py) and against Pillow, whole
 files with no tolerance, on the sizes and contents of tests/jpeg_enc_fixtures.py in batches that mix sizes and samplings; against itself
 on a second call; through this project's own decoder; and ``convert_frames`` on a tiny tree against its ``pil`` run."""
 import io
@@ -22,8 +22,8 @@ QUALITIES = (10, 92, 100)
 
 @pytest.fixture(scope="module")
 def ops():
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""PNG frames on the device: ``data_ops.decode_png_batch`` against Pillow on every byte (the fixtures of tests/test_png_cpu.py, all
+"""PNG frames on the device: ``image_codecs.decode_png_batch`` against Pillow on every byte (the fixtures of tests/test_png_cpu.py, all
 inside the covered set, so a fallback cannot hide a kernel failure), the fallback for uncovered and damaged files, the descriptor
 rules of ``fd_png_unfilter``, ``KITTIRAWBatches(png_decoder="device")`` - and one derived builder - against the ``png_decoder="pil"``
 batch key by key, and the depth keys of ``KITTICompletionBatches``.  Every comparison is ``array_equal``."""
@@ -62,18 +62,18 @@ def _contiguous_views(frames):
 
 
 def _count_calls(monkeypatch):
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     seen = []
-    real = data_ops.call
-    monkeypatch.setattr(data_ops, "call", lambda name, *a: (seen.append(name), real(name, *a))[1])
+    real = image_codecs.call
+    monkeypatch.setattr(image_codecs, "call", lambda name, *a: (seen.append(name), real(name, *a))[1])
     return seen
 
 
 def test_mixed_rgb_batch_equals_pillow_on_every_byte(monkeypatch):
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     seen = _count_calls(monkeypatch)
     names, datas = zip(*_split()[0])
-    frames, stats = data_ops.decode_png_batch(list(datas))
+    frames, stats = image_codecs.decode_png_batch(list(datas))
     torch.cuda.synchronize()
     assert stats == {"device": len(datas), "fallback": 0}
     assert seen == ["fd_png_unfilter"]                           # one call per batch
@@ -82,10 +82,10 @@ def test_mixed_rgb_batch_equals_pillow_on_every_byte(monkeypatch):
 
 
 def test_gray16_batch_equals_pillow_on_every_value(monkeypatch):
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     seen = _count_calls(monkeypatch)
     names, datas = zip(*_split()[1])
-    frames, stats = data_ops.decode_png_batch(list(datas), mode="gray16")
+    frames, stats = image_codecs.decode_png_batch(list(datas), mode="gray16")
     torch.cuda.synchronize()
     assert stats == {"device": len(datas), "fallback": 0} and seen == ["fd_png_unfilter"]
     _check(frames, datas, names, torch.uint16)
@@ -94,46 +94,56 @@ def test_gray16_batch_equals_pillow_on_every_value(monkeypatch):
 
 
 def test_one_file_alone(tmp_path):
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     name, data = next((n, d) for n, d in PF.fixtures() if n == "rgb8-texture-300x200")
     path = os.path.join(str(tmp_path), "one.png")
     with open(path, "wb") as fh:
         fh.write(data)
     for src in (data, path):
-        frames, stats = data_ops.decode_png_batch([src])
+        frames, stats = image_codecs.decode_png_batch([src])
         assert stats == {"device": 1, "fallback": 0}
         _check(frames, [data], [name])
 
 
 def test_uncovered_and_damaged_files_fall_back_to_pillow():
-    from fusiondepth_amd import data_ops
+    from fusiondepth_amd import image_codecs
     eight, sixteen = _split()
     picks = [d for n, d in eight if "-wbits" in n or "-strategy-" in n]
     uncovered = [d for _, d in PF.uncovered()]
     damaged = bytearray(picks[0])
     damaged[-5] ^= 0x40                                          # IEND's CRC: this decoder refuses the file, Pillow reads it
     datas = picks[:3] + uncovered[:3] + [bytes(damaged), sixteen[0][1]] + uncovered[3:] + picks[3:]
-    frames, stats = data_ops.decode_png_batch(datas)
+    frames, stats = image_codecs.decode_png_batch(datas)
     assert stats == {"device": len(picks), "fallback": len(uncovered) + 2}       # a 16-bit file in rgb mode is Pillow's too
     _check(frames, datas, ["mixed %d" % i for i in range(len(datas))])
     # gray16 mode: an 8-bit grey file is Pillow's (np.asarray gives uint8 values), an RGB file is refused as the loader refuses it
     g8 = next(d for n, d in eight if n.startswith("g8-pillow"))
-    frames, stats = data_ops.decode_png_batch([sixteen[1][1], g8], mode="gray16")
+    frames, stats = image_codecs.decode_png_batch([sixteen[1][1], g8], mode="gray16")
     assert stats == {"device": 1, "fallback": 1}
     assert np.array_equal(frames[1].cpu().numpy(), PF.pillow_rgb(g8)[:, :, 0].astype(np.uint16))
     with pytest.raises(RuntimeError, match="single-channel integer"):
-        data_ops.decode_png_batch([picks[0]], mode="gray16")
+        image_codecs.decode_png_batch([picks[0]], mode="gray16")
     with pytest.raises(ValueError, match="mode"):
-        data_ops.decode_png_batch([picks[0]], mode="rgba")
+        image_codecs.decode_png_batch([picks[0]], mode="rgba")
 
 
 def _staging_for(datas, mode):
     """The host job of a batch -> (its layout, descriptor table, out bytes), to be uploaded by hand."""
-    from fusiondepth_amd import data_ops
-    job = data_ops.PngBatchJob(datas, None, mode)
+    from fusiondepth_amd import image_codecs
+    job = image_codecs.PngBatchJob(datas, None, mode)
     lay = job.wait_host()
     table, _, _, _, out_bytes = job.layout()
     return lay, table, out_bytes
+
+
+def test_sizes_are_pillow_s_after_wait_host():
+    from fusiondepth_amd import image_codecs
+    by_name = dict(PF.fixtures())
+    small = next(d for _, d in PF.uncovered() if max(PF.pillow_rgb(d).shape[:2]) <= 65)      # its size comes from Pillow's header read
+    datas = [by_name["rgb8-random-65x65"], small, by_name["rgb8-first4-5x3"], by_name["rgb8-random-65x65"]]
+    job = image_codecs.PngBatchJob(datas)
+    job.wait_host()
+    assert job.sizes() == [PF.pillow_rgb(d).shape[:2] for d in datas]
 
 
 def _unfilter(lay, table, out_bytes, fill=0x77, staging_bytes=None, out_size=None, twice=False):

@@ -1,4 +1,4 @@
-"""PNG outputs on the device: ``data_ops.encode_png_batch`` against the restatement's bytes (tests/png_enc_ref.py) with no tolerance, on
+"""PNG outputs on the device: ``image_codecs.encode_png_batch`` against the restatement's bytes (tests/png_enc_ref.py) with no tolerance, on
 every fixture of tests/png_enc_fixtures.py in batches that mix sizes and kinds; against itself on a second call; through this
 project's own decoder; and the two commands that write PNGs, each against its ``pil`` run."""
 import io
@@ -17,8 +17,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def ops():
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 @pytest.fixture(scope="module")

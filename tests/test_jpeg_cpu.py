@@ -15,8 +15,8 @@ GUARD = 4096
 def ops():
     from fusiondepth_amd import build
     build.build(verbose=False)
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 @pytest.fixture(scope="module")

@@ -18,8 +18,8 @@ import jpeg_ref as JR
 def ops():
     from fusiondepth_amd import build
     build.build(verbose=False)
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 @pytest.fixture(scope="module")

@@ -18,8 +18,8 @@ GUARD = 4096
 def ops():
     from fusiondepth_amd import build
     build.build(verbose=False)
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 def inflate_guarded(ops, data, cap):
@@ -176,8 +176,8 @@ def test_the_fixtures_hold_what_they_are_there_for():
     sync = PR.idat(by_name["rgb8-syncflush"])
     assert sync.count(b"\x00\x00\xff\xff") >= 5                  # the empty stored blocks Z_SYNC_FLUSH leaves
     heights = {PR.header(d)["height"] for n, d in PF.fixtures() if "-band-" in n}
-    from fusiondepth_amd import data_ops
-    assert heights == {data_ops.PNG_BAND_ROWS - 1, data_ops.PNG_BAND_ROWS, data_ops.PNG_BAND_ROWS + 1}
+    from fusiondepth_amd import image_codecs
+    assert heights == {image_codecs.PNG_BAND_ROWS - 1, image_codecs.PNG_BAND_ROWS, image_codecs.PNG_BAND_ROWS + 1}
 
 
 def test_png_decoder_flag_and_loader_argument(tmp_path):

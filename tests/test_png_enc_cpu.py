@@ -23,8 +23,8 @@ MODES = {"rgb8": "RGB", "g8": "L", "g16": "I;16"}
 def ops():
     from fusiondepth_amd import build
     build.build(verbose=False)
-    from fusiondepth_amd import data_ops
-    return data_ops
+    from fusiondepth_amd import image_codecs
+    return image_codecs
 
 
 def test_constants_are_the_library_s(ops):
