@@ -52,6 +52,12 @@ __device__ __forceinline__ void for_channel_slice(int N, long HW, int C, int c, 
 }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// The forward's rectifier: torch.relu, which keeps NaN (a diverged channel must not come out as zeros).  Every other value gets the
+// bits of `v > 0.f ? v : 0.f`.  The backward masks stay `> 0`: NaN passes no gradient on either mask path.
+__device__ __forceinline__ float bn_relu(float v) { return v <= 0.f ? 0.f : v; }      // one compare: NaN fails it and stays
+// The single-pass variance, clamped at 0 against cancellation.  fmaxf would also turn NaN (a channel that holds a NaN or an infinity)
+// into 0 and hand on a finite invstd; this keeps it.
+__device__ __forceinline__ float bn_var(float v) { return v < 0.f ? 0.f : v; }
 
 // Shift of the single-pass statistics of one (group, channel): the MEDIAN of 9 samples spread over the group's first plane.
 // var = E[d^2] - E[d]^2 (d = x - shift) loses eps * (mean - shift)^2 / var: the shift has to sit within a few standard
@@ -107,7 +113,7 @@ __device__ __forceinline__ BnStat bn_finalize(const float* __restrict__ part, co
     const float m = s1 / M;
     BnStat st;
     st.mean = shift + m;
-    st.var = fmaxf(s2 / M - m * m, 0.f);
+    st.var = bn_var(s2 / M - m * m);
     return st;
 }
 
@@ -149,7 +155,7 @@ __global__ void __launch_bounds__(NT) k_bn_apply_train(const float* __restrict__
             float4 v = ld4(x + base + 4 * i);
             v.x = fmaf(v.x, a, b); v.y = fmaf(v.y, a, b); v.z = fmaf(v.z, a, b); v.w = fmaf(v.w, a, b);
             if (residual) { const float4 r = ld4(residual + base + 4 * i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-            if (relu) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
+            if (relu) { v.x = bn_relu(v.x); v.y = bn_relu(v.y); v.z = bn_relu(v.z); v.w = bn_relu(v.w); }
             st4(y + base + 4 * i, v);
         }
         return;
@@ -157,7 +163,7 @@ __global__ void __launch_bounds__(NT) k_bn_apply_train(const float* __restrict__
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < HW; i += (long)gridDim.x * NT) {
         float v = fmaf(x[base + i], a, b);
         if (residual) v += residual[base + i];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = bn_relu(v);
         y[base + i] = v;
     }
 }
@@ -224,7 +230,7 @@ __global__ void __launch_bounds__(NT) k_bn_apply_parts(const float* __restrict__
             float4 v = ld4(x + base + 4 * i);
             v.x = fmaf(v.x, a, b); v.y = fmaf(v.y, a, b); v.z = fmaf(v.z, a, b); v.w = fmaf(v.w, a, b);
             if (residual) { const float4 r = ld4(residual + base + 4 * i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-            if (relu) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
+            if (relu) { v.x = bn_relu(v.x); v.y = bn_relu(v.y); v.z = bn_relu(v.z); v.w = bn_relu(v.w); }
             st4(y + base + 4 * i, v);
         }
         return;
@@ -232,7 +238,7 @@ __global__ void __launch_bounds__(NT) k_bn_apply_parts(const float* __restrict__
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < HW; i += (long)gridDim.x * NT) {
         float v = fmaf(x[base + i], a, b);
         if (residual) v += residual[base + i];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = bn_relu(v);
         y[base + i] = v;
     }
 }
@@ -250,7 +256,7 @@ __global__ void __launch_bounds__(NT) k_bn_apply_eval(const float* __restrict__ 
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < HW; i += (long)gridDim.x * NT) {
         float v = fmaf(x[base + i], a, b);
         if (residual) v += residual[base + i];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = bn_relu(v);
         y[base + i] = v;
     }
 }
@@ -415,7 +421,7 @@ __global__ void __launch_bounds__(NT) k_bn_train_small(const float* __restrict__
         block_sum2(s1, s2, red);
         const float m = s1 / M;
         const float mean = shift + m;
-        float var = fmaxf(s2 / M - m * m, 0.f);
+        float var = bn_var(s2 / M - m * m);
         if (m * m > 16.f * var) {                                   // uniform: s1, s2 are broadcast values
             float t2 = 0.f, dummy = 0.f;
 #pragma unroll
@@ -439,7 +445,7 @@ __global__ void __launch_bounds__(NT) k_bn_train_small(const float* __restrict__
             float4 r = v[k];
             r.x = fmaf(r.x, a, b); r.y = fmaf(r.y, a, b); r.z = fmaf(r.z, a, b); r.w = fmaf(r.w, a, b);
             if (residual) { const float4 z = ld4(residual + off[k]); r.x += z.x; r.y += z.y; r.z += z.z; r.w += z.w; }
-            if (relu) { r.x = r.x > 0.f ? r.x : 0.f; r.y = r.y > 0.f ? r.y : 0.f; r.z = r.z > 0.f ? r.z : 0.f; r.w = r.w > 0.f ? r.w : 0.f; }
+            if (relu) { r.x = bn_relu(r.x); r.y = bn_relu(r.y); r.z = bn_relu(r.z); r.w = bn_relu(r.w); }
             st4(y + off[k], r);
         }
     }
@@ -518,7 +524,7 @@ __global__ void __launch_bounds__(NT) k_bn_train_small_slabs(const float* __rest
         block_sum2(s1, s2, red);
         const float m = s1 / M;
         const float mean = shift + m;
-        float var = fmaxf(s2 / M - m * m, 0.f);
+        float var = bn_var(s2 / M - m * m);
         if (m * m > 16.f * var) {
             float t2 = 0.f, dummy = 0.f;
 #pragma unroll
@@ -542,7 +548,7 @@ __global__ void __launch_bounds__(NT) k_bn_train_small_slabs(const float* __rest
             float4 r = v[k];
             r.x = fmaf(r.x, a, b); r.y = fmaf(r.y, a, b); r.z = fmaf(r.z, a, b); r.w = fmaf(r.w, a, b);
             if (residual) { const float4 z = ld4(residual + off[k]); r.x += z.x; r.y += z.y; r.z += z.z; r.w += z.w; }
-            if (relu) { r.x = r.x > 0.f ? r.x : 0.f; r.y = r.y > 0.f ? r.y : 0.f; r.z = r.z > 0.f ? r.z : 0.f; r.w = r.w > 0.f ? r.w : 0.f; }
+            if (relu) { r.x = bn_relu(r.x); r.y = bn_relu(r.y); r.z = bn_relu(r.z); r.w = bn_relu(r.w); }
             st4(y + off[k], r);
         }
         __syncthreads();                                  // sh_shift is rewritten by the next group
@@ -632,7 +638,7 @@ inline bool bn_small(int Ng, long HW, int groups, bool vec) {
 //   backward  d = relu'(.) * (max-pool adjoint of g_pooled [+ g_f0]) is formed from g_pooled, the argmax bytes and x in both the
 //             reduction and the apply pass: 2 reads of x + 1 write of gx.
 // One thread owns a 2x2 block of full-resolution pixels = the taps (1..2, 1..2) of pooling window (p, q), as k_maxpool_bwd.
-__device__ __forceinline__ float bn_act(float x, float a, float b) { return fmaxf(fmaf(x, a, b), 0.f); }
+__device__ __forceinline__ float bn_act(float x, float a, float b) { return bn_relu(fmaf(x, a, b)); }
 
 __global__ void __launch_bounds__(NT) k_bn_relu_pool_fwd(const float* __restrict__ x, const float* __restrict__ weight,
                                                          const float* __restrict__ bias, float* __restrict__ feat,
@@ -940,6 +946,8 @@ inline bool stem_vec_ok(int W, const void* a, const void* b, const void* c, cons
     auto al = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
     return (W & 3) == 0 && al(a) && al(b) && al(c) && al(d) && al(e);
 }
+// the apply kernels enumerate the (sample, channel) planes in gridDim.y
+constexpr int BN_MAX_PLANES = 65535;
 inline int plane_blocks(long HW) {
     long b = (HW + NT * 4 - 1) / (NT * 4);
     return (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
@@ -985,6 +993,7 @@ extern "C" int fd_bn_train_fwd(const float* x, const float* weight, const float*
         FD_LAUNCH_CHECK("fd_bn_train_fwd(small)");
         return 0;
     }
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_train_fwd: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     auto stats = vec ? k_bn_stats<true> : k_bn_stats<false>;
     auto apply = vec ? k_bn_apply_train<true> : k_bn_apply_train<false>;
     float* shifts = ws + (long)groups * C * sp * 2;              // [group][channel], behind the partial sums
@@ -1005,6 +1014,7 @@ extern "C" int fd_bn_train_fwd_parts(const float* x, const float* weight, const 
                "fd_bn_train_fwd_parts: bad args");
     FD_REQUIRE(groups >= 1 && groups <= 16 && N % groups == 0, "fd_bn_train_fwd_parts: batch %d is not divisible into %d groups (<= 16)", N, groups);
     FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "fd_bn_train_fwd_parts: running stats must come in pairs");
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_train_fwd_parts: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     const long HW = (long)H * W;
     const bool vec = bn_vec_ok(HW, x, y, residual, nullptr, nullptr);
     auto apply = vec ? k_bn_apply_parts<true> : k_bn_apply_parts<false>;
@@ -1022,6 +1032,7 @@ extern "C" int fd_bn_eval_fwd(const float* x, const float* weight, const float* 
                               const float* running_mean, const float* running_var, int N, int C, int H, int W, float eps,
                               int relu, void* stream) {
     FD_REQUIRE(x && y && running_mean && running_var && N > 0 && C > 0 && H > 0 && W > 0, "fd_bn_eval_fwd: bad args");
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_eval_fwd: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     const long HW = (long)H * W;
     hipLaunchKernelGGL(k_bn_apply_eval, dim3(plane_blocks(HW), N * C), dim3(NT), 0, (hipStream_t)stream, x, weight, bias,
                        residual, y, running_mean, running_var, C, HW, eps, relu);
@@ -1048,6 +1059,7 @@ static int bn_train_bwd_impl(const float* x, const float* y, const float* gy, co
         FD_LAUNCH_CHECK("fd_bn_train_bwd(small)");
         return 0;
     }
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_train_bwd: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     auto reduce = vec ? k_bn_bwd_reduce<true> : k_bn_bwd_reduce<false>;
     auto apply = vec ? k_bn_bwd_apply<true> : k_bn_bwd_apply<false>;
     hipLaunchKernelGGL(reduce, dim3(C, sp, groups), dim3(NT), 0, st, x, y, gy, save_mean, save_invstd, ws, Ng, C, HW,
@@ -1081,6 +1093,7 @@ extern "C" int fd_bn_relu_maxpool_fwd(const float* x, const float* weight, const
     FD_REQUIRE(groups >= 1 && N % groups == 0, "fd_bn_relu_maxpool_fwd: batch %d is not divisible into %d groups", N, groups);
     FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "fd_bn_relu_maxpool_fwd: running stats must come in pairs");
     FD_REQUIRE((long)H * W < (1L << 30), "fd_bn_relu_maxpool_fwd: plane too large");
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_relu_maxpool_fwd: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     const int Ng = N / groups;
@@ -1112,6 +1125,7 @@ extern "C" int fd_bn_relu_maxpool_bwd(const float* x, const float* g_pooled, con
                                       float* gbias, float* ws, int N, int C, int H, int W, int groups, int accumulate, void* stream) {
     FD_REQUIRE(x && g_pooled && idx && save_mean && save_invstd && gx && ws && N > 0 && C > 0 && H > 0 && W > 0, "fd_bn_relu_maxpool_bwd: bad args");
     FD_REQUIRE(groups >= 1 && N % groups == 0, "fd_bn_relu_maxpool_bwd: batch %d is not divisible into %d groups", N, groups);
+    FD_REQUIRE((long)N * C <= BN_MAX_PLANES, "fd_bn_relu_maxpool_bwd: N * C = %ld planes exceed the %d a launch can enumerate (one grid row per plane)", (long)N * C, BN_MAX_PLANES);
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     const int Ng = N / groups;

@@ -415,7 +415,10 @@ int fd_act_bwd(const float* y, const float* gy, float* gpre, long n, int act, vo
  * separate forward passes would do (predict_poses runs the pose encoders once per source frame, trainer.py:336-351; the
  * trainer batches those passes) — including G in-order momentum updates of the running statistics.
  * save_mean / save_invstd [G*C] are written for the backward; running_mean / running_var are updated in place
- * with `momentum` (unbiased variance), as torch does.  ws: fd_bn_ws_floats(N,C,H,W,G). */
+ * with `momentum` (unbiased variance), as torch does.  ws: fd_bn_ws_floats(N,C,H,W,G).
+ * Non-finite input: a NaN or an infinity in a (group, channel) makes that channel's y, save_invstd and running_var NaN (the mean
+ * of a channel with an infinity is that infinity), with or without the ReLU, as torch does; other channels are untouched.
+ * Every fd_bn_* entry point that launches one grid row per (sample, channel) plane refuses N * C > 65535 (status -1). */
 long fd_bn_ws_floats(int N, int C, int H, int W, int groups);
 int fd_bn_train_fwd(const float* x, const float* weight, const float* bias, const float* residual, float* y,
                     float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* ws, int N, int C,
