@@ -277,6 +277,9 @@ SIGNATURES = {
     "fd_adam_step": ("ppppl" "fffffff" "p", "i"),
     "fd_adam_step_dev": ("ppppl" "p" "ffff" "p", "i"),
     "fd_adam_step_dev_zero": ("ppppl" "p" "ffff" "p", "i"),
+    "fd_grad_stats_ws_bytes": ("li", "l"),
+    "fd_grad_stats": ("plpi" "ffi" "pppp" "p", "i"),
+    "fd_adam_step_guarded": ("ppppl" "p" "ffff" "pi" "p", "i"),
     "fd_replay_function_count": ("", "i"),
     "fd_replay_function_name": ("i", "s"),
     "fd_replay_function_signature": ("i", "s"),

@@ -2,7 +2,8 @@
 
     python -m fusiondepth_amd.complete [reference flags] [--seed N] [--val_limit N] [--no_val] [--val_route fused|per_batch]
                                        [--image_decoder pil|device] [--png_decoder pil|device] [--resume PATH|latest]
-                                       [--pretrained_path FILE|DIR]
+                                       [--pretrained_path FILE|DIR] [--grad_guard off|skip] [--clip_grad_norm X]
+                                       [--max_skipped_steps N]          (the guard flags: fusiondepth_amd/train.py)
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.complete ...       # data parallel, one rank per GPU
 
   * ``build_loaders(opt, rank, world_size, ...)``  completor.py:132-152: both loaders are ``KITTICompletionBatches`` over
@@ -41,11 +42,11 @@ from . import dp
 from .evaluate_completion import canvas_size
 from .evaluate_depth import split_off_flags
 from . import resume as run_state
-from .train import decode_workers, start_epoch_of, take_image_decoder, write_summary
+from .train import apply_guard_flags, decode_workers, start_epoch_of, take_guard_flags, take_image_decoder, write_summary
 
 DEFAULT_VAL_ROUTE = "fused"            # decided by profiles/completion_val_time.log
 EXTRA_VALUED = {"seed": "0", "val_limit": None, "val_route": DEFAULT_VAL_ROUTE, "image_decoder": None, "png_decoder": None,
-                "resume": None, "pretrained_path": None}
+                "resume": None, "pretrained_path": None, "grad_guard": None, "clip_grad_norm": None, "max_skipped_steps": None}
 EXTRA_SWITCHES = ("no_val",)
 
 
@@ -60,6 +61,7 @@ def split_off_extra(argv):
     take_image_decoder(found)
     run_state.take_flags(found)
     run_state.check_flags(found, rest)
+    take_guard_flags(found)
     found["seed"] = int(found["seed"])
     if found["val_limit"] is not None:
         found["val_limit"] = int(found["val_limit"])
@@ -112,6 +114,7 @@ def main(argv=None):
         opt.pretrained_path = extra["pretrained_path"]
     torch.manual_seed(extra["seed"])
     completor = Completor(opt, rank=rank, world_size=world)
+    apply_guard_flags(completor, extra)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     train_loader, val_loader = build_loaders(completor.opt, rank, world, seed=extra["seed"], val_limit=extra["val_limit"],
                                              no_val=extra["no_val"] or rank != 0, local_world_size=local_world, device=completor.device,

@@ -326,6 +326,147 @@ __global__ void __launch_bounds__(NT) k_adam_dev_zero(float* __restrict__ p, flo
     }
 }
 
+// ---- guarded Adam: one deterministic reduction over the flat gradient, then an Adam launch that obeys its decision ----
+// Partial sums: the grid is a function of n alone (never of the device), every thread walks its elements in a fixed order and
+// the partials meet in fixed trees, so two calls on one buffer give the same bits on any device.  Segment by segment: the head
+// up to the next 16-byte address one float per thread, the body as 16-byte loads (four in flight per thread), the tail one
+// float per thread.
+constexpr int GS_MAX_BLOCKS = 1024;            // partial-sum blocks at most: ws rows of fd_grad_stats_ws_bytes
+constexpr int GS_UNROLL = 4;                   // 16-byte loads in flight per thread
+inline int gs_blocks(long n) {
+    const long per = (long)NT * 4 * GS_UNROLL;
+    const long b = (n + per - 1) / per;
+    return (int)(b < 1 ? 1 : (b > GS_MAX_BLOCKS ? GS_MAX_BLOCKS : b));
+}
+__device__ __forceinline__ double gs_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, FD_WAVE);
+    return v;  // valid in lane 0
+}
+__device__ __forceinline__ void gs_take(float g, float gscale, double& acc, long& bad) {
+    const float x = g * gscale;                // the product Adam forms
+    bad += !(fabsf(x) <= 3.402823466e+38f);    // NaN and +-inf
+    const double d = (double)x;
+    acc += d * d;
+}
+__global__ void __launch_bounds__(NT) k_grad_stats_part(const float* __restrict__ g, long n, const long* __restrict__ seg, int n_seg,
+                                                        float gscale, double* __restrict__ ws) {
+    __shared__ double red[FD_GUARD_MAX_SEGMENTS + 1][NT / FD_WAVE];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long gtid = (long)blockIdx.x * NT + tid, gstride = (long)gridDim.x * NT;
+    long bad = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        long a = seg[s], b = seg[s + 1];       // a table that is not 0 .. n and ascending reads less, never outside grad[0 .. n)
+        a = a < 0 ? 0 : (a > n ? n : a);
+        b = b < a ? a : (b > n ? n : b);
+        double acc = 0.0;
+        long head = (long)(((16u - (unsigned)((uintptr_t)(g + a) & 15u)) & 15u) >> 2);
+        head = head > b - a ? b - a : head;
+        if (gtid < head) gs_take(g[a + gtid], gscale, acc, bad);
+        const float4* __restrict__ gv = reinterpret_cast<const float4*>(g + a + head);
+        const long nv = (b - a - head) >> 2;
+        long v = gtid;
+        for (; v + (GS_UNROLL - 1) * gstride < nv; v += GS_UNROLL * gstride) {
+            float4 x[GS_UNROLL];
+#pragma unroll
+            for (int u = 0; u < GS_UNROLL; ++u) x[u] = gv[v + u * gstride];
+#pragma unroll
+            for (int u = 0; u < GS_UNROLL; ++u) {
+                gs_take(x[u].x, gscale, acc, bad); gs_take(x[u].y, gscale, acc, bad);
+                gs_take(x[u].z, gscale, acc, bad); gs_take(x[u].w, gscale, acc, bad);
+            }
+        }
+        for (; v < nv; v += gstride) {
+            const float4 x = gv[v];
+            gs_take(x.x, gscale, acc, bad); gs_take(x.y, gscale, acc, bad);
+            gs_take(x.z, gscale, acc, bad); gs_take(x.w, gscale, acc, bad);
+        }
+        const long tail = a + head + nv * 4;
+        if (tail + gtid < b) gs_take(g[tail + gtid], gscale, acc, bad);
+        acc = gs_wave_sum(acc);
+        if (lane == 0) red[s][wv] = acc;
+    }
+    const double nbad = gs_wave_sum((double)bad);                // counts are exact in float64 (n < 2^53)
+    if (lane == 0) red[n_seg][wv] = nbad;
+    __syncthreads();
+    if (tid <= n_seg) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < NT / FD_WAVE; ++w) t += red[tid][w];
+        ws[(long)tid * gridDim.x + blockIdx.x] = t;              // row s: the partials of segment s; row n_seg: the counts
+    }
+}
+// One block: row by row the partials through a fixed tree (thread t adds rows' entries t, t + 256, ..., then the block's tree),
+// then thread 0 forms norm / count / coef / skip and advances the counters.
+__global__ void __launch_bounds__(NT) k_grad_stats_fin(const double* __restrict__ ws, int nblk, int n_seg, float max_norm,
+                                                       int skip_nonfinite, double* __restrict__ stats, long long* __restrict__ counters,
+                                                       const float* __restrict__ adam_state) {
+    __shared__ double red[NT / FD_WAVE];
+    __shared__ double rows[FD_GUARD_MAX_SEGMENTS + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int s = 0; s <= n_seg; ++s) {
+        double t = 0.0;
+        for (int i = tid; i < nblk; i += NT) t += ws[(long)s * nblk + i];
+        t = gs_wave_sum(t);
+        if (lane == 0) red[wv] = t;
+        __syncthreads();
+        if (tid == 0) {
+            double r = 0.0;
+#pragma unroll
+            for (int w = 0; w < NT / FD_WAVE; ++w) r += red[w];
+            rows[s] = r;
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    double total = 0.0;
+    for (int s = 0; s < n_seg; ++s) {
+        total += rows[s];
+        stats[4 + s] = sqrt(rows[s]);
+    }
+    const double norm = sqrt(total), count = rows[n_seg];
+    const bool skip = skip_nonfinite && count > 0.0;
+    double coef = 1.0;
+    if (max_norm > 0.f && !skip) {
+        const double r = (double)max_norm / (norm + 1e-6);       // torch.nn.utils.clip_grad_norm_
+        coef = (double)(float)(r < 1.0 ? r : 1.0);               // rounded to float32 once: the factor the update multiplies by
+    }
+    stats[0] = norm; stats[1] = count; stats[2] = coef; stats[3] = skip ? 1.0 : 0.0;
+    if (skip) {
+        const long long step = (long long)adam_state[0] + 1;     // the optimiser step this call would have been
+        counters[0] += 1;
+        if (counters[1] < 0) counters[1] = step;
+        counters[2] = step;
+    }
+}
+
+__global__ void k_adam_tick_guarded(float* __restrict__ state, const double* __restrict__ stats) {
+    if (stats[3] == 0.0) state[0] += 1.0f;
+}
+// k_adam_dev / k_adam_dev_zero behind the decision of fd_grad_stats: the gradient is multiplied by coef after grad_scale, the rest
+// is their update statement for statement; a skipped step writes nothing but the zeros of the gradient.
+template <bool ZERO>
+__global__ void __launch_bounds__(NT) k_adam_guarded(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, long n, const float* __restrict__ state, float b1,
+                                                     float b2, float eps, float gscale, const double* __restrict__ stats) {
+    if (stats[3] != 0.0) {
+        if (ZERO) GRID_STRIDE(i, n) g[i] = 0.f;
+        return;
+    }
+    const float coef = (float)stats[2];
+    const float step = state[0], lr = state[1];
+    const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
+    const float step_size = lr / bc1, sqrt_bc2 = sqrtf(bc2);
+    GRID_STRIDE(i, n) {
+        const float gi = (g[i] * gscale) * coef;
+        if (ZERO) g[i] = 0.f;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        p[i] -= step_size * (mi / (sqrtf(vi) / sqrt_bc2 + eps));
+    }
+}
+
 }  // namespace
 
 extern "C" int fd_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int N, int C, int H, int W, void* stream) {
@@ -504,6 +645,46 @@ extern "C" int fd_adam_step_dev_zero(float* param, float* grad, float* exp_avg, 
     hipLaunchKernelGGL(k_adam_dev_zero, dim3(ew_blocks(n)), dim3(NT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
                        state, beta1, beta2, eps, grad_scale);
     FD_LAUNCH_CHECK("fd_adam_step_dev_zero");
+    return 0;
+}
+
+extern "C" long fd_grad_stats_ws_bytes(long n, int n_seg) {
+    if (n < 0 || n_seg < 1 || n_seg > FD_GUARD_MAX_SEGMENTS) return -1;
+    return (long)(n_seg + 1) * gs_blocks(n) * (long)sizeof(double);
+}
+
+extern "C" int fd_grad_stats(const float* grad, long n, const long* seg_offsets, int n_seg, float grad_scale, float max_norm,
+                             int skip_nonfinite, void* ws, double* stats, long* counters, const float* adam_state, void* stream) {
+    FD_REQUIRE(grad && seg_offsets && ws && stats && counters && adam_state && n >= 0, "fd_grad_stats: bad args");
+    FD_REQUIRE(n_seg >= 1 && n_seg <= FD_GUARD_MAX_SEGMENTS, "fd_grad_stats: %d segments (1 .. %d are covered)", n_seg,
+               FD_GUARD_MAX_SEGMENTS);
+    FD_REQUIRE(((uintptr_t)grad & 3) == 0 && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0 && ((uintptr_t)counters & 7) == 0 &&
+               ((uintptr_t)seg_offsets & 7) == 0, "fd_grad_stats: misaligned pointer");
+    FD_REQUIRE(max_norm == max_norm, "fd_grad_stats: max_norm is NaN");
+    const int nblk = gs_blocks(n);
+    hipLaunchKernelGGL(k_grad_stats_part, dim3(nblk), dim3(NT), 0, (hipStream_t)stream, grad, n, seg_offsets, n_seg, grad_scale,
+                       (double*)ws);
+    FD_LAUNCH_CHECK("fd_grad_stats(partials)");
+    hipLaunchKernelGGL(k_grad_stats_fin, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)ws, nblk, n_seg, max_norm,
+                       skip_nonfinite, stats, (long long*)counters, adam_state);
+    FD_LAUNCH_CHECK("fd_grad_stats");
+    return 0;
+}
+
+extern "C" int fd_adam_step_guarded(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float* state, float beta1,
+                                    float beta2, float eps, float grad_scale, const double* stats, int zero_grad, void* stream) {
+    FD_REQUIRE(param && grad && exp_avg && exp_avg_sq && state && stats && n >= 0 && ((uintptr_t)stats & 7) == 0,
+               "fd_adam_step_guarded: bad args");
+    hipLaunchKernelGGL(k_adam_tick_guarded, dim3(1), dim3(1), 0, (hipStream_t)stream, state, stats);
+    FD_LAUNCH_CHECK("fd_adam_step_guarded(tick)");
+    if (n == 0) return 0;
+    if (zero_grad)
+        hipLaunchKernelGGL(k_adam_guarded<true>, dim3(ew_blocks(n)), dim3(NT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           n, state, beta1, beta2, eps, grad_scale, stats);
+    else
+        hipLaunchKernelGGL(k_adam_guarded<false>, dim3(ew_blocks(n)), dim3(NT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           n, state, beta1, beta2, eps, grad_scale, stats);
+    FD_LAUNCH_CHECK("fd_adam_step_guarded");
     return 0;
 }
 

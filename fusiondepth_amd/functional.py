@@ -883,3 +883,48 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, betas=(0.9, 0.999), e
     call("fd_adam_step_dev_zero" if zero_grad else "fd_adam_step_dev", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
          param.numel(), ptr(state), betas[0], betas[1], float(eps), float(grad_scale), stream())
     refresh_weight_layouts()
+
+
+GUARD_MAX_SEGMENTS = 16      # FD_GUARD_MAX_SEGMENTS
+
+
+def _guard_ptr(t, dtype, numel, what):
+    """Device pointer of a contiguous ``dtype`` CUDA tensor of at least ``numel`` elements (the guard's small tables)."""
+    _need_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel:
+        raise RuntimeError("%s must be a contiguous %s tensor of at least %d elements, got %s[%d]" % (what, dtype, numel, t.dtype, t.numel()))
+    return t.data_ptr()
+
+
+def grad_stats_ws_bytes(n, n_seg):
+    """Bytes of the ``ws`` that ``grad_stats`` of ``n`` gradient elements in ``n_seg`` segments needs (fd_grad_stats_ws_bytes)."""
+    size = query("fd_grad_stats_ws_bytes", int(n), int(n_seg))
+    if size < 0:
+        raise ValueError("grad_stats: %d elements in %d segments (1 .. %d segments are covered)" % (n, n_seg, GUARD_MAX_SEGMENTS))
+    return size
+
+
+def grad_stats(grad, seg_offsets, ws, stats, counters, adam_state, grad_scale=1.0, max_norm=0.0, skip_nonfinite=True):
+    """fd_grad_stats: the float64 norms (overall and per segment), the non-finite count, the clip factor and the skip decision of
+    ``grad * grad_scale``, left in ``stats`` (float64, 4 + n_seg) and ``counters`` (int64, 3) on the device; no host read.
+    ``seg_offsets``: int64 device tensor of n_seg + 1 element offsets, 0 first, ``grad.numel()`` last."""
+    n_seg = seg_offsets.numel() - 1
+    n = grad.numel()
+    need = grad_stats_ws_bytes(n, n_seg)
+    _need_cuda(ws)
+    if not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.data_ptr() % 8:
+        raise RuntimeError("grad_stats: ws must be contiguous, 8-byte aligned and hold %d bytes" % need)
+    call("fd_grad_stats", ptr(grad), n, _guard_ptr(seg_offsets, torch.int64, 2, "seg_offsets"), n_seg, float(grad_scale),
+         float(max_norm), int(bool(skip_nonfinite)), ws.data_ptr(), _guard_ptr(stats, torch.float64, 4 + n_seg, "stats"),
+         _guard_ptr(counters, torch.int64, 3, "counters"), ptr(adam_state), stream())
+
+
+def adam_step_guarded(param, grad, exp_avg, exp_avg_sq, state, stats, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, zero_grad=False):
+    """``adam_step_dev`` behind the decision ``grad_stats`` left in ``stats``: the gradient is also multiplied by ``stats[2]`` (the clip
+    factor), and with ``stats[3]`` set neither the parameters, the moments nor the step count change (fd_adam_step_guarded).
+    ``zero_grad`` clears the gradient in both cases."""
+    sync_late_layouts()
+    bump_weights_epoch()
+    call("fd_adam_step_guarded", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(state), betas[0], betas[1],
+         float(eps), float(grad_scale), _guard_ptr(stats, torch.float64, 4, "stats"), int(bool(zero_grad)), stream())
+    refresh_weight_layouts()

@@ -2,6 +2,7 @@
 
     python -m fusiondepth_amd.refine [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
                                      [--image_decoder pil|device] [--png_decoder pil|device] [--resume PATH|latest] [--shard_val]
+                                     [--grad_guard off|skip] [--clip_grad_norm X] [--max_skipped_steps N]   (fusiondepth_amd/train.py)
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.refine ...         # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  refiner.py:168-200: the training lines of
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 
 from . import dp
-from .train import _read_lines, decode_workers, shard_val_lines, split_off_extra, start_epoch_of, write_summary
+from .train import _read_lines, apply_guard_flags, decode_workers, shard_val_lines, split_off_extra, start_epoch_of, write_summary
 
 
 def build_loaders(opt, splits_dir="splits", rank=0, world_size=1, seed=0, lidar_source="files", val_limit=None, no_val=False,
@@ -77,6 +78,7 @@ def main(argv=None):
     torch.manual_seed(extra["seed"])
     refiner = Refiner(opt, rank=rank, world_size=world)
     refiner.shard_val = bool(extra.get("shard_val")) and world > 1
+    apply_guard_flags(refiner, extra)
     if epochs_given is not None:
         refiner.opt.num_epochs = epochs_given
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))

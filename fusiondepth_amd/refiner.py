@@ -320,6 +320,9 @@ class Refiner(Trainer):
                 if getattr(self, "val_loader", None) is not None:
                     self.log("val", self.val_losses(self.val_loader))
                     self.set_train()
+            if self.rank != 0 and self._log_due(batch_idx, step0):
+                self.check_skipped_steps()     # rank 0 checks inside log(); the counters are the same on every rank
+        self.check_skipped_steps()
         self.lr_scheduler_step()
 
     def train_step(self, inputs, next_inputs=None):

@@ -17,6 +17,8 @@ FILE = "run_state.rank%d.pth"
 FINGERPRINT_OPTIONS = ("num_layers", "height", "width", "scales", "frame_ids", "use_stereo", "pose_model_type", "split")
 # what must be equal between the run that wrote the file and the run that continues it, in the order it is checked
 IDENTITY_FIELDS = ("world_size", "micro_batch", "accumulate_step", "seed")
+# optional: the skip counters of the optimiser's guard, written only by a run whose guard is on
+GUARD_KEYS = ("skipped_steps", "first_skipped_step", "last_skipped_step")
 
 
 def _plain(v):

@@ -3,6 +3,7 @@
     python -m fusiondepth_amd.train [reference flags] [--splits_dir D] [--seed N] [--lidar_source files|raw] [--val_limit N] [--no_val]
                                     [--log_images] [--image_decoder pil|device] [--png_decoder pil|device]
                                     [--png_encoder pil|device] [--resume PATH|latest] [--pretrained_path FILE|DIR] [--shard_val]
+                                    [--grad_guard off|skip] [--clip_grad_norm X] [--max_skipped_steps N]
     python -m torch.distributed.run --nproc-per-node 8 -m fusiondepth_amd.train ...          # data parallel, one rank per GPU
 
   * ``build_loaders(opt, splits_dir, rank, world_size, ...)``  trainer.py:142-174: the training lines of
@@ -23,6 +24,14 @@ checkpoint (``Trainer.resume``; ``latest``: the highest-numbered complete ``weig
 remaining epochs; the result is bit for bit the uninterrupted run's (resume.py).  It is refused beside
 ``--train_load_weights_folder`` / ``--load_weights_folder`` and for a run that differs in ``world_size``, batch sizes, seed or an
 option that fixes shapes or the data order.  The summary gains ``"resumed_from"`` (the finished epochs of the checkpoint, or null).
+
+Guarding the optimiser step (off by default).  ``--grad_guard skip``: a step whose gradient holds a NaN or an
+inf is not taken - parameters, moments and the Adam step count stay, the gradient is cleared, the batch counts as consumed - instead
+of writing NaN into every parameter.  ``--clip_grad_norm X`` scales the gradient by ``min(1, X / (norm + 1e-6))`` first
+(``torch.nn.utils.clip_grad_norm_`` over all trained parameters, the norm taken in float64) and turns the guard on by itself;
+beside ``--grad_guard off`` it is refused.  The train scalars gain ``grad_norm``, ``grad_norm/<network>``, ``clip_coef``,
+``nonfinite`` and the skip counters, the summary ``"grad_guard"``; more than ``--max_skipped_steps N`` (default 10) skipped steps
+stop the run with the first and last skipped optimiser step in the message.
 
 ``--weights_init pretrained`` reads torchvision's ``resnet{n}-*.pth`` from ``--pretrained_path`` (a file or a directory), then
 ``$TORCH_HOME/hub/checkpoints``, then ``~/.cache/torch/hub/checkpoints``; it never downloads (networks/resnet_encoder.py).
@@ -60,7 +69,8 @@ from . import resume as run_state
 from .evaluate_depth import split_off_flags
 
 EXTRA_VALUED = {"splits_dir": "splits", "seed": "0", "lidar_source": "files", "val_limit": None, "image_decoder": None, "png_decoder": None,
-                "png_encoder": None, "resume": None, "pretrained_path": None}
+                "png_encoder": None, "resume": None, "pretrained_path": None, "grad_guard": None, "clip_grad_norm": None,
+                "max_skipped_steps": None}
 EXTRA_SWITCHES = ("no_val", "log_images", "shard_val")
 
 
@@ -68,13 +78,15 @@ def split_off_extra(argv):
     """The flags of this command that ``MonodepthOptions`` does not know, typed -> ({splits_dir, seed, lidar_source, val_limit,
     no_val}, the remaining arguments); ``log_images: True`` joins the dict where ``--log_images`` is given, and only there, and so
     do ``image_decoder``, ``png_decoder`` and ``png_encoder`` ('pil' or 'device'), ``resume`` ('latest' or a folder),
-    ``pretrained_path`` and ``shard_val: True``.  ``--resume`` beside a weights folder of the command line is a ``ValueError``."""
+    ``pretrained_path`` and ``shard_val: True``, and ``grad_guard`` / ``clip_grad_norm`` / ``max_skipped_steps`` (``take_guard_flags``).
+    ``--resume`` beside a weights folder of the command line is a ``ValueError``."""
     found, rest = split_off_flags(argv, EXTRA_VALUED, EXTRA_SWITCHES)
     if not found["log_images"]:
         del found["log_images"]
     take_image_decoder(found)
     run_state.take_flags(found)
     run_state.check_flags(found, rest)
+    take_guard_flags(found)
     found["seed"] = int(found["seed"])
     if found["val_limit"] is not None:
         found["val_limit"] = int(found["val_limit"])
@@ -93,6 +105,40 @@ def take_image_decoder(found):
             found.pop(name, None)
         elif found[name] not in ("pil", "device"):
             raise ValueError("--%s must be 'pil' or 'device', got %r" % (name, found[name]))
+
+
+def take_guard_flags(found):
+    """``--grad_guard off|skip``, ``--clip_grad_norm X`` and ``--max_skipped_steps N``: typed and validated
+    where given, dropped from ``found`` where not.  ``--clip_grad_norm X`` with X > 0 sets ``grad_guard`` to 'skip' by itself;
+    beside ``--grad_guard off`` it is a ``ValueError``, and so are another mode name, a negative or non-finite X and a negative N -
+    all before a GPU is touched."""
+    from .optim import check_guard
+    for name in ("grad_guard", "clip_grad_norm", "max_skipped_steps"):
+        if found.get(name) is None:
+            found.pop(name, None)
+    if "clip_grad_norm" in found:
+        try:
+            found["clip_grad_norm"] = float(found["clip_grad_norm"])
+        except ValueError:
+            raise ValueError("--clip_grad_norm must be a number, got %r" % (found["clip_grad_norm"],)) from None
+        if found["clip_grad_norm"] > 0 and "grad_guard" not in found:
+            found["grad_guard"] = "skip"
+    if "grad_guard" in found or "clip_grad_norm" in found:
+        try:
+            check_guard(found.get("grad_guard", "off"), found.get("clip_grad_norm", 0.0))
+        except ValueError as e:
+            raise ValueError("--grad_guard / --clip_grad_norm: %s" % e) from None
+    if "max_skipped_steps" in found:
+        found["max_skipped_steps"] = int(found["max_skipped_steps"])
+        if found["max_skipped_steps"] < 0:
+            raise ValueError("--max_skipped_steps must be >= 0, got %d" % found["max_skipped_steps"])
+
+
+def apply_guard_flags(trainer, extra):
+    """The guard flags of the command line -> the attributes ``Trainer.optimizer_step`` reads."""
+    for name in ("grad_guard", "clip_grad_norm", "max_skipped_steps"):
+        if name in extra:
+            setattr(trainer, name, extra[name])
 
 
 def _read_lines(path):
@@ -178,6 +224,7 @@ def write_summary(trainer, train_loader, rank, loss_scale=None):
     res = {"rank": rank, "world_size": trainer.world_size, "steps": trainer.step, "epochs": len(train_loader.served),
            "batches_per_epoch": len(train_loader), "batch_size": train_loader.batch_size, "last_loss": loss,
            "param_checksum": param_checksum(trainer), "best": float(trainer.best), "resumed_from": trainer.resumed_from,
+           "grad_guard": trainer.guard_summary(),
            "items": [order for _, order in train_loader.served]}
     os.makedirs(trainer.log_path, exist_ok=True)
     path = os.path.join(trainer.log_path, "train_summary.rank%d.json" % rank)
@@ -198,6 +245,7 @@ def main(argv=None):
     torch.manual_seed(extra["seed"])
     trainer = Trainer(opt, rank=rank, world_size=world)
     trainer.shard_val = bool(extra.get("shard_val")) and world > 1
+    apply_guard_flags(trainer, extra)
     if epochs_given is not None:
         trainer.opt.num_epochs = epochs_given
     if extra.get("log_images") and rank == 0:                    # the other ranks do not log

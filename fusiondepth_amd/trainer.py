@@ -151,7 +151,8 @@ class Trainer:
             if k in trained:
                 FD.enable_side_wgrad(self.models[k].parameters())
         FD.enable_weight_cache(frozen, frozen=True)      # kernel-side weight layouts derived once, not on every call
-        self.optim = FlatAdam(self.flat, self.learning_rate, hp["scheduler_step_size"])
+        self.optim = FlatAdam(self.flat, self.learning_rate, hp["scheduler_step_size"],
+                              segments=[(k, len(list(self.models[k].parameters()))) for k in trained])
         self._graphed = None                   # graph_step.GraphedStep, from the first train_step_graphed on
         self._streams = []
         self.parallel_streams = True
@@ -202,6 +203,11 @@ class Trainer:
     # ---- what the commands set: --shard_val, and what --resume continued ----
     shard_val = False          # every rank validates lines rank::world_size (val_gt holds their maps); val_metrics gathers the rows
     resumed_from = None        # the finished epochs of the checkpoint ``resume`` loaded
+
+    # ---- the guard of the optimiser step; set before the first step, like the switches above ----
+    grad_guard = "off"         # "skip": a step whose gradient holds a NaN or an inf is not taken (parameters, moments, Adam step count)
+    clip_grad_norm = 0.0       # > 0: the gradient is scaled by min(1, X / (global norm + 1e-6)) first; needs grad_guard "skip"
+    max_skipped_steps = 10     # more skipped steps than this stop the run (checked at every log event and at the end of every epoch)
 
     # ---- the steps of __init__ that the sibling drivers of the reference (completor.py, refiner.py) take differently ----
     _SI_CONSTANTS = {}         # FD.PhotoOptions' si_* keywords where they are not the trainer's
@@ -334,6 +340,7 @@ class Trainer:
         gradient exchange for the window's last pass and count the batches; the captured step (graph_step.py) does neither."""
         stacked = self.stack_microbatches
         passes = [batches] if stacked else batches
+        self._apply_guard_settings()           # the guard's device tables exist before a capture of this step begins
         if eager and stacked:
             self.grad_sync.arm()
         for i, inputs in enumerate(passes):
@@ -361,10 +368,43 @@ class Trainer:
     def optimizer_step(self, grad_scale=1.0):
         """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step(); zero_grad()  as one fused kernel (optim.FlatAdam), which
         clears the gradient buffer as it reads it; with ``tuning.host.adam_zero`` off the buffer is filled by a pass of its own."""
+        self._apply_guard_settings()
         if self.optim.step(grad_scale):
             self.flat.attach_grads()
         else:
             self.flat.zero_grad()
+
+    # ---- the guard: attributes -> optim.FlatAdam.configure_guard; the report in the log; the stop ----
+    guard_on = property(lambda self: self.grad_guard != "off" or self.clip_grad_norm > 0)
+
+    def _apply_guard_settings(self):
+        """``grad_guard`` / ``clip_grad_norm`` as they stand now reach the optimiser (a tuple comparison when nothing changed).  A
+        norm to clip to beside ``grad_guard = "off"``, another mode name or a bad norm is a ``ValueError`` (optim.check_guard)."""
+        if (self.grad_guard, self.clip_grad_norm) != (self.optim.guard_mode, self.optim.max_norm):
+            self.optim.configure_guard(self.grad_guard, self.clip_grad_norm)
+
+    def guard_report(self):
+        """``optim.FlatAdam.guard_report()`` ({} with the guard off); synchronises."""
+        self._apply_guard_settings()
+        return self.optim.guard_report()
+
+    def check_skipped_steps(self, report=None):
+        """A run that keeps skipping has weights that are broken already: more than ``max_skipped_steps`` skipped steps stop it."""
+        if not self.guard_on:
+            return
+        rep = self.guard_report() if report is None else report
+        if rep and rep["skipped_steps"] > self.max_skipped_steps:
+            raise RuntimeError("grad_guard: %d optimiser steps were skipped for a gradient that was not finite (max_skipped_steps = %d); "
+                               "the first was optimiser step %d, the last %d" % (rep["skipped_steps"], self.max_skipped_steps,
+                                                                                 rep["first_skipped_step"], rep["last_skipped_step"]))
+
+    def guard_summary(self):
+        """What ``train_summary.rank<k>.json`` holds under "grad_guard": the mode, ``max_norm`` and the counters; None when off."""
+        if not self.guard_on:
+            return None
+        rep = self.guard_report()
+        return {"mode": self.grad_guard, "max_norm": float(self.clip_grad_norm), "skipped_steps": rep["skipped_steps"],
+                "first_skipped_step": rep["first_skipped_step"], "last_skipped_step": rep["last_skipped_step"]}
 
     def lr_scheduler_step(self):
         """StepLR(step_size, 0.1).step()  (trainer.py:266)."""
@@ -444,7 +484,8 @@ class Trainer:
             losses = self.train_step(window)
             window = []
             # the decision is a function of (batch_idx, step) alone: with shard_val every rank takes it, and enters validation
-            due = (self.rank == 0 or self.shard_val) and any(self._log_due(first + k, step0 + k) for k in range(self.accumulate_step))
+            event = any(self._log_due(first + k, step0 + k) for k in range(self.accumulate_step))
+            due = (self.rank == 0 or self.shard_val) and event
             if due and self.rank != 0:
                 self._validate_shard()
             elif due:
@@ -466,6 +507,9 @@ class Trainer:
                         self.log_pictures("val", *self._last_val_io, val=True)
                         self._last_val_io = None
                     self.set_train()
+            if event and self.rank != 0:
+                self.check_skipped_steps()     # rank 0 checks inside log(); the counters are the same on every rank (section 28)
+        self.check_skipped_steps()
         self.lr_scheduler_step()
 
     def val_losses(self, batches):
@@ -498,8 +542,13 @@ class Trainer:
         rec = {"step": self.step, "epoch": self.epoch, "lr": self.lr}
         for k, v in losses.items():
             rec[k] = float(v)
+        report = self.guard_report() if mode == "train" and self.guard_on else None
+        if report:
+            rec.update(report)                 # grad_norm, grad_norm/<network>, clip_coef, nonfinite and the skip counters
         with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
             f.write(json.dumps(rec) + "\n")
+        if report:
+            self.check_skipped_steps(report)
 
     def log_pictures(self, mode, inputs, outputs, val=False):
         """trainer.py:656-681: the image summaries of one log event, rendered on the device by one ``fd_log_sheets`` call
@@ -1219,6 +1268,9 @@ class Trainer:
         state = dict(self._run_identity(loader), rank=self.rank, epochs_done=self.epoch + 1, step=self.step, batch_idx=self.batch_idx,
                      best=float(self.best), scheduler_epochs=self.optim.scheduler_epochs, loader_epoch=getattr(loader, "_epoch", None),
                      torch_rng=torch.get_rng_state(), cuda_rng=torch.cuda.get_rng_state(self.device))
+        if self.guard_on:                      # optional keys: a file without them reads as "nothing skipped"
+            self._apply_guard_settings()
+            state.update(zip(run_state.GUARD_KEYS, self.optim.guard_counters_host()))
         return run_state.write_state(state, folder, self.rank)
 
     def resume(self, folder, train_loader):
@@ -1241,6 +1293,9 @@ class Trainer:
         FD.refresh_weight_layouts()
         self.load_optimizer_state_dict(torch.load(adam, map_location="cpu"))       # the device-side [step, lr] pair too
         self.optim.scheduler_epochs = int(state["scheduler_epochs"])
+        if self.guard_on:
+            self._apply_guard_settings()
+            self.optim.load_guard_counters([state.get(k, d) for k, d in zip(run_state.GUARD_KEYS, (0, -1, -1))])
         self.step, self.batch_idx, self.best = int(state["step"]), int(state["batch_idx"]), float(state["best"])
         if state["loader_epoch"] is not None:
             train_loader.set_epoch(state["loader_epoch"])

@@ -523,6 +523,31 @@ int fd_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp
 int fd_adam_step_dev_zero(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float* state, float beta1,
                           float beta2, float eps, float grad_scale, void* stream);
 
+/* Guarded Adam: a reduction over the flat gradient in front of the update, and an update that obeys the
+ * decision the reduction left in device memory - no host read, no allocation, capturable.
+ *
+ * fd_grad_stats: x = grad[i] * grad_scale in float32 (the product Adam forms); per segment the sum of (double)x * (double)x in
+ * float64, and the count of elements with !isfinite(x).  seg_offsets: n_seg + 1 ascending longs on the device, 0 first, n last
+ * (1 <= n_seg <= FD_GUARD_MAX_SEGMENTS; a segment may be empty; entries outside 0 .. n are clamped, nothing outside grad is read).
+ * Blocks write partial sums to ws (fd_grad_stats_ws_bytes(n, n_seg) bytes, 8-byte aligned), one block adds them through a fixed
+ * tree: no atomics, a grid that depends on n alone, the same bits from two calls on any device.  Two launches.
+ *   stats    (double): [0] norm = sqrt(sum of the segment sums, in segment order), [1] non-finite count, [2] coef, [3] skip (0 / 1),
+ *                      [4 .. 4 + n_seg) the segments' norms
+ *   counters (int64) : [0] steps skipped so far, [1] optimiser step of the first skip, [2] of the last skip (the caller starts
+ *                      them at 0, -1, -1); the optimiser step is adam_state[0] + 1, the step this call would have been
+ * skip = skip_nonfinite && count > 0.  coef = 1 if max_norm <= 0 or skip, else (double)(float)min(1, max_norm / (norm + 1e-6)):
+ * torch.nn.utils.clip_grad_norm_'s factor, rounded to float32 once (a NaN norm that is not skipped gives 1).  n == 0 is legal. */
+#define FD_GUARD_MAX_SEGMENTS 16
+long fd_grad_stats_ws_bytes(long n, int n_seg);
+int fd_grad_stats(const float* grad, long n, const long* seg_offsets, int n_seg, float grad_scale, float max_norm,
+                  int skip_nonfinite, void* ws, double* stats, long* counters, const float* adam_state, void* stream);
+/* The update behind that decision: state[0] advances only when stats[3] == 0; the gradient is (grad[i] * grad_scale) * (float)stats[2],
+ * the rest is the update above statement for statement - with coef 1 and no skip the bits of param, both moments, grad and state are
+ * those of the unguarded call with the same zero_grad.  A skipped step writes nothing to param or the moments; with zero_grad the
+ * gradient is cleared in both cases, so that what was not finite does not reach the next window. */
+int fd_adam_step_guarded(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float* state, float beta1,
+                         float beta2, float eps, float grad_scale, const double* stats, int zero_grad, void* stream);
+
 /* ------------------------------------------------------------------ sparse LiDAR --------------- */
 
 /* gen2channel.py:60-117 get_4beam_2channel, gather formulation (race-free, bit-exact vs the
